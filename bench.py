@@ -225,7 +225,12 @@ def parse():
     ap.add_argument("--plan-only", action="store_true",
                     help="print this rank's share of the workload as JSON and exit without touching the GPU")
     ap.add_argument("--out-dir", default=None, help="sweep: where rank 0 writes the feature files (default: a fresh temp dir, removed afterwards)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="analysis_synthesis: after the timed steps, write what rank 0's last timed step computed (t, f0, "
+                         "sp, ap, y; float64, a fixed sample of the larger ones, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "analysis_synthesis":
+        ap.error("--dump-outputs is implemented for --workload analysis_synthesis only")
     if args.utts <= 0:
         args.utts = {"sweep": 1000, "harvest": 64, "synthesis": 1024}.get(args.workload, 256)
     args.coded = not args.raw
@@ -491,6 +496,8 @@ def headline_bench(env, ctx, xs, fs, fp, cpu_all, side_data):
     elapsed = time.perf_counter() - t0
     kernel_ms = {k: ctx.timing_query(k) for k in ANALYSIS_KERNELS + SYNTHESIS_KERNELS}
     ctx.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outs, y)
     elapsed_max, total_frames = env.reduce(elapsed, frames)
     with_gather = with_gather_raw = None
     if world > 1 and not args.gather:
@@ -611,6 +618,44 @@ def headline_bench(env, ctx, xs, fs, fp, cpu_all, side_data):
     else:
         batch.close()
     return line
+
+
+# --dump-outputs: float64, at most 64 MB in all.  t and f0 whole up to 512 Ki frames, sp and ap 16 MiB of rows each,
+# y 1 Mi samples; each array is written beside an index file naming the elements it holds.
+DUMP_SEED = 20250101
+DUMP_FRAMES = 1 << 19
+DUMP_ROW_BYTES = 16 << 20
+DUMP_SAMPLES = 1 << 20
+
+
+def output_sample(n, k, stream):
+    """k distinct indices of range(n), ascending: one in each of k equal strata, drawn by synth_data.uniform from a fixed
+    seed -- the same for the same (n, k) in every run.  All of range(n) when k >= n."""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    sd = importlib.import_module("hts-train-world_amd").synth_data
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    return edges[:-1] + (sd.uniform(DUMP_SEED, stream, k) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(path, t, f0, sp, ap, y):
+    """What the timed path's caller holds after its last step, as float64 .npy files under `path`."""
+    import torch
+    frames, bins = sp.shape
+    fi = output_sample(frames, DUMP_FRAMES, 1)
+    ri = output_sample(frames, max(1, DUMP_ROW_BYTES // (8 * bins)), 2)
+    yi = output_sample(y.numel(), DUMP_SAMPLES, 3)
+
+    def take(v, idx):
+        return v.index_select(0, torch.from_numpy(idx).to(v.device)).double().cpu().numpy()
+
+    files = {"t": take(t, fi), "f0": take(f0, fi), "frame_index": fi.astype(np.float64),
+             "sp": take(sp, ri), "ap": take(ap, ri), "row_index": ri.astype(np.float64),
+             "y": take(y, yi), "y_index": yi.astype(np.float64)}
+    assert sum(v.nbytes for v in files.values()) <= 64 * 10 ** 6
+    os.makedirs(path, exist_ok=True)
+    for name, v in files.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def compact(line):

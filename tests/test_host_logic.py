@@ -119,3 +119,39 @@ def test_driver_line_fits_the_drivers_tail():
         assert side["cpu_baseline"]["value"] == ref["cpu_baseline"]["value"] and side["parity"]
         assert line["summary"][name] == ref["value"]
     assert list(line)[-1] == "summary"                           # the numbers that matter are the line's last bytes
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float64 files of the last step's arrays, a fixed sample of the larger ones (the same
+    indices in every run), indices beside them, within 64 MB."""
+    import os
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    for n, k in ((10, 3), (272794, 4088), (21000000, 1 << 20), (5, 8)):
+        i = bench.output_sample(n, k, 3)
+        assert len(i) == min(n, k) and i[0] >= 0 and i[-1] < n and (np.diff(i) > 0).all()
+        np.testing.assert_array_equal(i, bench.output_sample(n, k, 3))
+    frames, bins, n_out = 300000, 1025, 1500000
+    t = torch.arange(frames, dtype=torch.float64) * 0.005
+    f0 = torch.linspace(0.0, 400.0, frames, dtype=torch.float64)
+    sp = torch.rand(frames, bins, dtype=torch.float64)
+    ap = torch.rand(frames, bins, dtype=torch.float64)
+    y = torch.randn(n_out, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), t, f0, sp, ap, y)
+    got = {n[:-4]: np.load(tmp_path / "d" / n) for n in os.listdir(tmp_path / "d")}
+    assert set(got) == {"t", "f0", "frame_index", "sp", "ap", "row_index", "y", "y_index"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "d" / (n + ".npy")) for n in got) <= 64 * 10 ** 6
+    np.testing.assert_array_equal(got["frame_index"], np.arange(frames))
+    np.testing.assert_array_equal(got["t"], t.numpy())
+    np.testing.assert_array_equal(got["f0"], f0.numpy())
+    rows = got["row_index"].astype(np.int64)
+    assert 1000 < len(rows) < frames and got["sp"].shape == (len(rows), bins)
+    np.testing.assert_array_equal(got["sp"], sp.numpy()[rows])
+    np.testing.assert_array_equal(got["ap"], ap.numpy()[rows])
+    yi = got["y_index"].astype(np.int64)
+    assert len(yi) == 1 << 20
+    np.testing.assert_array_equal(got["y"], y.numpy()[yi])

@@ -159,16 +159,14 @@ def test_cheaptrick_d4c_synthesis_options(oracle, reference, fs, index, dur):
 
 
 def test_reference_wavs(oracle, reference):
-    """The reference's own two inputs, read where they lie (this container only)."""
+    """The reference's own two inputs (wav_test/arctic_a0001.wav, test/vaiueo2d.wav): tests/golden/real_*.npz holds
+    their int16 samples and rates."""
     import os
-    import wave
-    W = "/root/reference/externs/WORLD_v2"
-    for path in (W + "/wav_test/arctic_a0001.wav", W + "/test/vaiueo2d.wav"):
-        if not os.path.exists(path):
-            pytest.skip("reference tree not present")
-        with wave.open(path, "rb") as w:
-            fs = w.getframerate()
-            x = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.float64) / 32768.0
+    from conftest import GOLDEN
+    for name in ("real_arctic_a0001", "real_vaiueo2d"):
+        g = np.load(os.path.join(GOLDEN, name + ".npz"))
+        x = g["x_i16"].astype(np.float64) / 32768.0
+        fs = int(g["fs"])
         tr, fr = reference.dio(x, fs)
         to, fo = oracle.dio(x, fs)
         assert ((fr > 0) == (fo > 0)).all()
