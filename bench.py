@@ -5,19 +5,25 @@ One "step" = one pass of the hot path over one batch of synthetic 16 kHz utteran
 already resident in HBM: Dio -> StoneMask -> CheapTrick -> D4C (analysis) then Synthesis from the
 features just produced, every utterance of the batch, fp64 as the reference computes.  Workload at
 N=1 is BASELINE.json configs[1]: 256 synthetic utterances of 2-8 s.  With --gpus N every rank owns
-its own 256 utterances (weak scaling, no data-path collective); at N > 1 the line also carries
+its own 256 utterances (weak scaling, no data-path collective); at N > 1 a --full line also carries
 `with_gather`: the same step followed by the RCCL gather-v of the float32 feature files to rank 0.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task description) with this extra object:
   roofline       -- dominant kernel (d4c_kernel): algorithmic bytes per launch / HIP-event duration
                     measured on the launch stream, against the 8 TB/s HBM peak; the FP64 figures that
                     actually bound the path are reported beside it.
+
+A plain run does only what that line needs: it sets up, pre-warms and warms up, times the steps, writes
+--dump-outputs and prints.  Everything else the benchmark measures or checks runs with --full:
   cpu_baseline   -- the reference WORLD (oracle/_ref, kind "reference") or this repo's C restatement
-                    (kind "port") timed single-threaded on a bounded sample of the same workload.
-  side_workloads -- (N = 1, default run) compact lines of the other BASELINE.json configurations, measured in the
-                    same process after the headline: configs[2] Harvest, configs[4] Synthesis only, configs[3]
-                    the corpus sweep; each with its own roofline / cpu_baseline / parity.  `--workload X` runs
-                    one of them alone and prints its full line.
+                    (kind "port") timed single-threaded on a bounded sample of the same workload, with the
+                    parity of that sample; -O2 and all-cores variants beside it.
+  host_inclusive -- the same step fed from and drained to pinned host memory (two legs).
+  side_workloads -- (N = 1) compact lines of the other BASELINE.json configurations, measured in the same
+                    process: configs[2] Harvest, configs[4] Synthesis only, configs[3] the corpus sweep; each
+                    with its own roofline / cpu_baseline / parity.  `--workload X` runs one of them alone and
+                    prints its full line.
+  with_gather    -- (N > 1) the step followed by the gather of the features to rank 0, and the `rccl` record.
 """
 from __future__ import annotations
 
@@ -183,16 +189,20 @@ def parse():
                     help="analysis_synthesis only: 16000 is BASELINE.json's metric; 48000 (fft 2048, D4C fft 4096) is the "
                          "setting the reference's author committed (config.status: SAMPFREQ=48000)")
     ap.add_argument("--gather", action="store_true", help="include the RCCL feature gather in the timed step itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baselines and parity, the host-inclusive legs, the side "
+                         "workloads (one GPU), the headline's gather legs and rccl record (N > 1), the detail file by default.  "
+                         "Without it a run sets up, warms up, times its steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and parity")
     ap.add_argument("--no-host-inclusive", action="store_true",
-                    help="skip the two PCIe-inclusive legs: every launch of the run is then one the line's launch_ms "
-                         "averages (what tools/profile_round.sh profiles)")
+                    help="with --full: skip the two PCIe-inclusive legs: every launch of the run is then one the line's "
+                         "launch_ms averages (what tools/profile_round.sh profiles)")
     ap.add_argument("--detail-file", default=None,
-                    help="where the FULL line goes (per-kernel tables, notes); default gpurun_out/bench_detail.json "
-                         "when that directory exists.  stdout carries the compact line (driver_line()).")
+                    help="where the FULL line goes (per-kernel tables, notes); without it only --full writes one, where "
+                         "write_detail() puts it by default.  stdout carries the compact line (driver_line()).")
     ap.add_argument("--full-line", action="store_true", help="print the full line on stdout instead of the compact one")
     ap.add_argument("--no-side", action="store_true",
-                    help="analysis_synthesis at one GPU: skip the side_workloads (configs[2], [4], [3]) after the headline")
+                    help="with --full, analysis_synthesis at one GPU: skip the side_workloads (configs[2], [4], [3])")
     ap.add_argument("--separate-calls", action="store_true",
                     help="WorldMi355Analyze then WorldMi355Synthesis instead of WorldMi355AnalyzeSynthesize")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
@@ -234,6 +244,9 @@ def parse():
     if args.utts <= 0:
         args.utts = {"sweep": 1000, "harvest": 64, "synthesis": 1024}.get(args.workload, 256)
     args.coded = not args.raw
+    if not args.full:
+        # a plain run: what the headline needs and nothing else
+        args.no_cpu_baseline = args.no_host_inclusive = args.no_side = True
     return args
 
 
@@ -416,7 +429,7 @@ def main():
     else:
         line = headline_bench(env, ctx, xs, fs, fp, cpu_all, side_data if side else None)
     if rank == 0 and line is not None:
-        detail = write_detail(args, line)
+        detail = write_detail(args, line) if args.full or args.detail_file else None
         print(json.dumps(line if args.full_line else driver_line(line, detail)), flush=True)
     if world > 1:
         dist.barrier()
@@ -500,7 +513,7 @@ def headline_bench(env, ctx, xs, fs, fp, cpu_all, side_data):
         dump_outputs(args.dump_outputs, *outs, y)
     elapsed_max, total_frames = env.reduce(elapsed, frames)
     with_gather = with_gather_raw = None
-    if world > 1 and not args.gather:
+    if world > 1 and not args.gather and args.full:
         # the same step followed by the one exchange the path has -- the gather-v of every rank's feature slabs to
         # rank 0 (RCCL grouped send/recv over xGMI) -- under the same timing contract: coded (what the recipe writes)
         # and raw
@@ -535,7 +548,7 @@ def headline_bench(env, ctx, xs, fs, fp, cpu_all, side_data):
                                     "the float64 -> float32 conversion of the slabs" if raw else "the coding kernels")}
         with_gather = gather_leg(False)
         with_gather_raw = gather_leg(True)
-    comm = env.comm_record()
+    comm = env.comm_record() if args.full else None
     hi = hic = None
     if not args.no_host_inclusive:
         hi = host_inclusive(env, ctx, xs, fs, fp, pipe=pipes.pop(None, None))

@@ -121,6 +121,25 @@ def test_driver_line_fits_the_drivers_tail():
     assert list(line)[-1] == "summary"                           # the numbers that matter are the line's last bytes
 
 
+def test_plain_bench_run_leaves_the_rest_to_full(monkeypatch):
+    """A plain bench.py run measures the headline only: the CPU baselines, the host-inclusive legs and the side
+    workloads run with --full, whose own --no-* switches still hold there."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_cpu_baseline and a.no_host_inclusive and a.no_side and a.prewarm == 10.0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_cpu_baseline or a.no_host_inclusive or a.no_side)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-side"])
+    a = bench.parse()
+    assert a.no_side and not (a.no_cpu_baseline or a.no_host_inclusive)
+
+
 def test_bench_dump_outputs(tmp_path):
     """bench.py --dump-outputs: float64 files of the last step's arrays, a fixed sample of the larger ones (the same
     indices in every run), indices beside them, within 64 MB."""

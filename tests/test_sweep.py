@@ -193,11 +193,11 @@ def test_sharded_sweep_writes_the_files_of_one_rank(tmp_path, ranks, coded):
 
 @pytest.mark.gpu
 def test_headline_line_at_two_ranks_carries_the_gather():
-    """`bench.py --gpus 2` on the headline workload (two gloo ranks sharing the box's GPU): one line from rank 0, weak
-    scaling over both ranks' frames, and `with_gather` / `with_gather_raw` -- the same step followed by the gather-v of
-    the coded / raw float32 slabs to rank 0 -- under the same timing contract."""
+    """`bench.py --gpus 2 --full` on the headline workload (two gloo ranks sharing the box's GPU): one line from rank 0,
+    weak scaling over both ranks' frames, and `with_gather` / `with_gather_raw` -- the same step followed by the gather-v
+    of the coded / raw float32 slabs to rank 0 -- under the same timing contract."""
     lines = _bench("--gpus", 2, "--backend", "gloo", "--utts", 6, "--dur", 0.5, 1.2, "--steps", 2, "--warmup", 1,
-                   "--prewarm", 0, "--no-cpu-baseline", "--no-side", "--workers", 1)
+                   "--prewarm", 0, "--full", "--no-cpu-baseline", "--no-side", "--workers", 1)
     assert len(lines) == 1
     ln = lines[0]
     assert ln["n_gpus"] == 2 and ln["scaling"] == "weak" and ln["config"]["utterances_per_gpu"] == 6
@@ -211,6 +211,24 @@ def test_headline_line_at_two_ranks_carries_the_gather():
     assert ln["summary"]["with_gather"] == ln["with_gather"]["value"]
     assert ln["rccl"]["world_size"] == 2 and len(ln["rccl"]["devices"]) == 2
     assert ln["roofline"]["kernel"] == "d4c_kernel" and ln["roofline"]["frac"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_headline_line_is_the_headline_alone():
+    """`bench.py` without --full on one GPU: the contract's keys and the roofline of the timed steps, no CPU baseline,
+    parity, host-inclusive legs or side workloads."""
+    lines = _bench("--gpus", 1, "--utts", 6, "--dur", 0.5, 1.2, "--steps", 2, "--warmup", 1, "--prewarm", 0,
+                   "--workers", 1)
+    assert len(lines) == 1
+    ln = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in ln, k
+    assert ln["n_gpus"] == 1 and ln["steps"] == 2 and ln["value"] > 0 and ln["ms_per_step"] > 0
+    assert ln["roofline"]["kernel"] == "d4c_kernel" and ln["roofline"]["frac"] > 0
+    assert ln["cpu_baseline"] is None
+    for k in ("parity", "host_inclusive", "host_inclusive_coded", "cpu_baseline_O2", "cpu_baseline_all_cores",
+              "side_workloads", "with_gather", "rccl"):
+        assert k not in ln, k
 
 
 @pytest.mark.gpu
