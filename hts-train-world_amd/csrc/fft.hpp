@@ -227,35 +227,12 @@ template <int R> struct TwDft {
   }
 };
 
-#ifndef WM_FFT_ILP
-#define WM_FFT_ILP 1
-#endif
-// Between the LDS exchanges of ONE wavefront's transform nothing needs to be waited for: a wave's DS instructions
-// execute in issue order, so a read that follows the writes of the same wave sees them, and writes that follow reads
-// do not overtake them.  What is needed is that the COMPILER keeps that order (lanes read what other lanes wrote:
-// to the compiler those are unrelated addresses).  WM_FFT_LIGHT_SYNC = 1: a compiler barrier only; 0: wave_sync(),
-// i.e. s_waitcnt lgkmcnt(0) at every exchange (all writes drained before the first read is issued).
-#ifndef WM_FFT_LIGHT_SYNC
-#define WM_FFT_LIGHT_SYNC 0
-#endif
-__device__ __forceinline__ void fft_sync() {
-#if WM_FFT_LIGHT_SYNC
-  asm volatile("" ::: "memory");
-#else
-  wave_sync();
-#endif
-}
-
+// Every LDS exchange of a wavefront's transform is fenced by wave_sync(), i.e. s_waitcnt lgkmcnt(0): lanes read what
+// other lanes wrote, and to the compiler those are unrelated addresses.  (A compiler barrier alone would do on the
+// device -- a wave's DS instructions execute in issue order -- and measured neutral: DESIGN.md section 3, item 30.)
 template <int N> struct FftCfg;
 template <> struct FftCfg<512>  { static constexpr int R1 = 8,  R2 = 8,  R3 = 8; };
-#ifndef WM_FFT_1024_SWAP
-#define WM_FFT_1024_SWAP 1
-#endif
-#if WM_FFT_1024_SWAP
 template <> struct FftCfg<1024> { static constexpr int R1 = 16, R2 = 16, R3 = 4; };   // second exchange by permlane swaps
-#else
-template <> struct FftCfg<1024> { static constexpr int R1 = 16, R2 = 8,  R3 = 8; };
-#endif
 template <> struct FftCfg<2048> { static constexpr int R1 = 16, R2 = 16, R3 = 8; };
 
 // LDS doubles2 needed by one transform of N points (padded image)
@@ -330,7 +307,7 @@ __device__ __forceinline__ void fft_pass1(const cpx (&v)[N / 64], cpx* lds, int 
   constexpr int R1 = FftCfg<N>::R1;
   constexpr int S1 = M / R1;
   static_assert(S1 >= 1, "radix plan does not fit 64 lanes");
-  fft_sync();
+  wave_sync();
   // ---- pass 1: radix R1, Ns = 1, no twiddles; store to out[j*R1 + r]
 #pragma unroll
   for (int b = 0; b < S1; ++b) {
@@ -347,9 +324,6 @@ __device__ __forceinline__ void fft_pass1(const cpx (&v)[N / 64], cpx* lds, int 
     const unsigned j = (unsigned)lane + 64u * b;
 #pragma unroll
     for (int r = 0; r < R1; ++r) lds[fft_pad<N>(j * R1 + r)] = a[r];
-#if !WM_FFT_ILP
-    __builtin_amdgcn_sched_barrier(0);      // one butterfly at a time: bounds the live registers
-#endif
   }
 }
 
@@ -383,11 +357,11 @@ template <int N>
 __device__ __forceinline__ void fft_finish_swap4(cpx (&v)[N / 64], cpx* lds, const FftTw<N>& tw, int lane) {
   constexpr int M = N / 64;
   static_assert(M == 16 && FftCfg<N>::R1 == 16 && FftCfg<N>::R2 == 16 && FftCfg<N>::R3 == 4, "16 x 16 x 4");
-  fft_sync();
+  wave_sync();
   cpx a[16];
 #pragma unroll
   for (int m = 0; m < M; ++m) a[m] = lds[fft_pad<N>((unsigned)lane + 64u * m)];
-  fft_sync();
+  wave_sync();
   {
     cpx pw[4];
     pw[0] = tw.w2;
@@ -432,14 +406,14 @@ __device__ __forceinline__ void fft_finish(cpx (&v)[N / 64], cpx* lds, const Fft
   constexpr int S2 = M / R2, S3 = M / R3;
   static_assert(S2 >= 1 && S3 >= 1, "radix plan does not fit 64 lanes");
   static_assert(R1 * R2 * R3 == N, "radix plan");
-  if constexpr (R3 == 4 && M == 16) {
+  if constexpr (N == 1024) {
     fft_finish_swap4<N>(v, lds, tw, lane);
     return;
   }
-  fft_sync();
+  wave_sync();
 #pragma unroll
   for (int m = 0; m < M; ++m) v[m] = lds[fft_pad<N>((unsigned)lane + 64u * m)];
-  fft_sync();
+  wave_sync();
   // ---- pass 2: radix R2, Ns = R1; twiddle W_{R1 R2}^{k r}, k = j % R1 = lane % R1
 #pragma unroll
   for (int b = 0; b < S2; ++b) {
@@ -458,11 +432,8 @@ __device__ __forceinline__ void fft_finish(cpx (&v)[N / 64], cpx* lds, const Fft
     const unsigned base = (j / R1) * (R1 * R2) + (j % R1);
 #pragma unroll
     for (int r = 0; r < R2; ++r) lds[fft_pad<N>(base + (unsigned)r * R1)] = a[r];
-#if !WM_FFT_ILP
-    __builtin_amdgcn_sched_barrier(0);
-#endif
   }
-  fft_sync();
+  wave_sync();
 #pragma unroll
   for (int m = 0; m < M; ++m) v[m] = lds[fft_pad<N>((unsigned)lane + 64u * m)];
   // ---- pass 3: radix R3, Ns = N / R3; twiddle W_N^{j r}; output lands in the register layout
@@ -481,9 +452,6 @@ __device__ __forceinline__ void fft_finish(cpx (&v)[N / 64], cpx* lds, const Fft
     }
 #pragma unroll
     for (int r = 0; r < R3; ++r) v[b + r * S3] = a[r];
-#if !WM_FFT_ILP
-    __builtin_amdgcn_sched_barrier(0);
-#endif
   }
 }
 

@@ -20,16 +20,6 @@
 #include "common.hpp"
 #include "window.hpp"
 
-// wave-uniform skips of register groups beyond the window (1) or straight-line predicated code (0)
-#ifndef WM_FRAME_SKIP
-#define WM_FRAME_SKIP 1
-#endif
-#if WM_FRAME_SKIP
-#define WM_FRAME_BRANCH(c) (c)
-#else
-#define WM_FRAME_BRANCH(c) true
-#endif
-
 namespace wm {
 
 struct FrameGeom {
@@ -92,7 +82,7 @@ __device__ __forceinline__ void frame_strided(const double* __restrict__ xu, int
       const int q = c * G + r;
       x[q] = 0.0;
       if (KEEP_W) w[q] = 0.0;
-      if (WM_FRAME_BRANCH(64 * q < L)) {
+      if (64 * q < L) {
         const bool in = 64 * q + lane < L;
         const double wv = window_value<TYPE>(g.c);
         const double val = xv[r] * wv + ((double)rv[r] / 268435456.0 - 6.0) * kSafe;
@@ -109,7 +99,7 @@ __device__ __forceinline__ void frame_strided(const double* __restrict__ xu, int
   g = g0;
 #pragma unroll
   for (int q = 0; q < QX; ++q) {
-    if (WM_FRAME_BRANCH(64 * q < L)) {
+    if (64 * q < L) {
       double wv;
       if (KEEP_W) {
         wv = w[q];
@@ -211,7 +201,7 @@ __device__ __forceinline__ void frame_packed(const double* __restrict__ xu, int 
     double e = 0.0;
 #pragma unroll
     for (int m = 0; m < M; ++m) {
-      if (WM_FRAME_BRANCH(128 * m < L)) {
+      if (128 * m < L) {
         const double w0 = 128 * m + 2 * lane < L ? window_value<TYPE>(he.c) : 0.0;
         const double w1 = 128 * m + 2 * lane + 1 < L ? window_value<TYPE>(ho.c) : 0.0;
         if (KEEP_W) {
@@ -259,7 +249,7 @@ __device__ __forceinline__ void frame_packed(const double* __restrict__ xu, int 
     for (int r = 0; r < G; ++r) {
       const int m = c * G + r;
       v[m] = make_double2(0.0, 0.0);
-      if (WM_FRAME_BRANCH(128 * m < L)) {
+      if (128 * m < L) {
         const bool in0 = 128 * m + 2 * lane < L, in1 = 128 * m + 2 * lane + 1 < L;
         double w0, w1;
         if (HAVE_W) {                                  // zero beyond the window already
@@ -289,7 +279,7 @@ __device__ __forceinline__ void frame_packed(const double* __restrict__ xu, int 
   go = go0;
 #pragma unroll
   for (int m = 0; m < M; ++m) {
-    if (WM_FRAME_BRANCH(128 * m < L)) {
+    if (128 * m < L) {
       if (KEEP_W) {
         v[m].x -= kw0[KEEP_W ? m : 0] * coef;
         v[m].y -= kw1[KEEP_W ? m : 0] * coef;

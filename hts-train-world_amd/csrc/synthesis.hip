@@ -50,10 +50,7 @@ __device__ __forceinline__ double coarse_vuv(const double* __restrict__ f0, int 
 // The f0-only kernels are latency chains of a few waves that run BESIDE the frame kernels of the analysis (CheapTrick,
 // D4C) or of an earlier part's render stage, whose waves fill every SIMD: at equal priority a chain wave gets the
 // issue slots the older waves leave.  Raised priority hands a chain its slot whenever it is ready -- it needs few.
-#ifndef WM_CHAIN_PRIO_LEVEL
-#define WM_CHAIN_PRIO_LEVEL 3
-#endif
-#define WM_CHAIN_PRIO __builtin_amdgcn_s_setprio(WM_CHAIN_PRIO_LEVEL);
+#define WM_CHAIN_PRIO __builtin_amdgcn_s_setprio(3);
 // (All f0-only kernels take their utterances through a list: Synthesis prepares the batch in two parts, the
 // shortest utterances first -- synthesis_prepare_part.)
 __global__ __launch_bounds__(256) void synth_inc_kernel(
@@ -1062,15 +1059,15 @@ static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more
   if (part.total_p == 0) return WM_OK;
   // The responses of a piece of the pulse list wait in scratch memory for the overlap-add.  The scratch holds two
   // pieces: while one is added into y on the second stream the pulse kernel fills the other (synthesis_render).
-  // A piece is half of the list when that fits, else what half of the scratch cap holds.  Measured (tools/syn_sweep.sh,
-  // ms per pass, configs[1] | configs[4]): 1 piece 14.64 | 20.86, 2 pieces 14.64 | 20.73, 4 pieces 14.81 | 20.75,
-  // 8 pieces 15.76 | 20.62 -- every launch of the pulse kernel has a tail, so a short list wants few pieces.
+  // A piece is half of the list when that fits, else what half of the scratch cap holds.  Measured (DESIGN.md section 3,
+  // item 25, and profiles/README.md, r03_c; ms per pass, configs[1] | configs[4]): 1 piece 14.64 | 20.86, 2 pieces
+  // 14.64 | 20.73, 4 pieces 14.81 | 20.75, 8 pieces 15.76 | 20.62 -- every launch of the pulse kernel has a tail, so a
+  // short list wants few pieces.
   int64_t cap_mb = 4096;
   if (const char* e = getenv("WORLD_MI355_SCRATCH_MB")) cap_mb = atoll(e) > 0 ? atoll(e) : cap_mb;
   int64_t chunk = (cap_mb * 1024 * 1024 / 8) / F / 2;
   if (chunk < 1) chunk = 1;
-  int pieces = 2;
-  if (const char* e = getenv("WORLD_MI355_SYN_PIECES")) pieces = atoi(e) > 0 ? atoi(e) : pieces;
+  constexpr int pieces = 2;
   const int64_t list = part.total_p > expect_more ? part.total_p : expect_more;     // the longest list still to come
   const int64_t share = (list + pieces - 1) / pieces;
   if (share >= 16384 && chunk > share) chunk = share;       // short lists: one piece, nothing to overlap
@@ -1157,32 +1154,16 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
   } break;
     {
       TimedScope ts_(b.ctx, "synth_pulse_kernel");
-      // fft 2048 (two waves per SIMD): spectra by pairs in registers (synth_pulse_bp.hpp); WORLD_MI355_PULSE_BP=0: the
-      // strided form
-      const char* bp_env = getenv("WORLD_MI355_PULSE_BP");          // read per launch: a test switches it within a process
-      const bool bp = !(bp_env && atoi(bp_env) == 0);
+      // fft 2048 (two waves per SIMD): spectra by pairs in registers (synth_pulse_bp.hpp)
       switch (F) {
         WM_SY_CASE(512, synth_pulse_kernel)
         WM_SY_CASE(1024, synth_pulse_kernel)
-        case 2048:
-          if (bp) {
-            const int per_ = persistent_grid(c, synth_pulse_bp_kernel<2048>, 64, (int64_t)1 << 40);
-            hipLaunchKernelGGL(synth_pulse_bp_kernel<2048>, dim3(imin(grid, per_)), dim3(64), 0, st, d_sp, d_ap,
-                               (const PulseRec*)b.d_pulse_rec, b.d_dc_remover, c.d_rng, fs, fp, p0, p1,
-                               (const int*)b.d_pulse_perm + p0, resp);
-          } else {
-            const int per_ = persistent_grid(c, synth_pulse_kernel<2048>, 64, (int64_t)1 << 40);
-            hipLaunchKernelGGL(synth_pulse_kernel<2048>, dim3(imin(grid, per_)), dim3(64), 0, st, d_sp, d_ap,
-                               (const PulseRec*)b.d_pulse_rec, b.d_dc_remover, c.d_rng, fs, fp, p0, p1,
-                               (const int*)b.d_pulse_perm + p0, resp);
-          }
-          break;
+        WM_SY_CASE(2048, synth_pulse_bp_kernel)
         WM_SY_CASE(4096, synth_pulse_kernel)
       }
     }
 #undef WM_SY_CASE
-    static const bool overlap = !(getenv("WORLD_MI355_SYN_OVERLAP") && atoi(getenv("WORLD_MI355_SYN_OVERLAP")) == 0);
-    hipStream_t so = overlap ? c.side : st;
+    hipStream_t so = c.side;
     rc = wm_check(hipEventRecord(c.ev_pulse[h], st));
     rc = rc ? rc : wm_check(hipStreamWaitEvent(so, c.ev_pulse[h], 0));
     if (rc) break;
@@ -1249,9 +1230,8 @@ int synthesis_render(Batch& b, const double* d_sp, const double* d_ap, double* d
 // ---- Synthesis alone: the batch in two parts (see the top of this section) ----
 int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y) {
   Context& c = *b.ctx;
-  static const int split_env = getenv("WORLD_MI355_SYN_SPLIT") ? atoi(getenv("WORLD_MI355_SYN_SPLIT")) : 3;
   // worth it from a few hundred thousand output samples per part on: below, the parts do not fill the machine
-  if (!split_env || b.n_utt < 16 || b.total_y < (int64_t)4 << 20) {
+  if (b.n_utt < 16 || b.total_y < (int64_t)4 << 20) {
     int rc = synthesis_prepare(b, d_f0, d_y);
     return rc ? rc : synthesis_render(b, d_sp, d_ap, d_y);
   }
@@ -1271,11 +1251,10 @@ int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const dou
   }
   if (rc) return rc;
   hipStream_t st = c.stream;
-  // part A: the shortest utterances up to a sixth of the output samples
+  // part A: the shortest utterances up to a third of the output samples (profiles/r04_syn_split_sweep.txt)
   int n_a = 0;
   int64_t acc = 0;
-  const int denom = split_env >= 2 ? split_env : 3;
-  while (n_a < b.n_utt - 1 && acc < b.total_y / denom) acc += b.y_len[(size_t)b.syn_sorted[(size_t)n_a++]];
+  while (n_a < b.n_utt - 1 && acc < b.total_y / 3) acc += b.y_len[(size_t)b.syn_sorted[(size_t)n_a++]];
   const int* sorted = b.d_syn_order + b.n_utt;
   SynPart pa{sorted, n_a, b.y_len[(size_t)b.syn_sorted[(size_t)n_a - 1]], 0};
   SynPart pb{sorted + n_a, b.n_utt - n_a, b.max_y_len, 0};

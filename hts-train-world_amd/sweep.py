@@ -48,7 +48,7 @@ def tapered_batches(order, frames, rounds, limit, ratio=0.65):
     within `limit`.  A pass is a pipeline -- round k + 1 is analysed while round k travels to the host and round k - 1
     is written -- so what no compute hides is the LAST round's transfer and file writes: the smaller that round, the
     shorter the tail (equal rounds: a quarter of the pass's copy + write time exposed at four rounds; tapered: a
-    tenth).  Too small a round does not fill the GPU, hence the gentle ratio."""
+    tenth).  Too small a round does not fill the GPU, hence the gentle ratio (profiles/r04_sweep_taper.txt)."""
     total = sum(frames[i] for i in order)
     w = [ratio ** k for k in range(rounds)]
     cum, acc = [], 0.0
@@ -94,8 +94,7 @@ class ShardedSweep:
         # several rounds the rounds taper off (tapered_batches)
         by_len = lambda s: sorted(s, key=lambda i: (-self.frames[i], i))
         if rounds > 1:
-            ratio = float(os.environ.get("WORLD_MI355_SWEEP_TAPER", "0.65"))
-            self.plan = [tapered_batches(by_len(s), self.frames, rounds, max_batch_frames, ratio) for s in self.shards]
+            self.plan = [tapered_batches(by_len(s), self.frames, rounds, max_batch_frames) for s in self.shards]
         else:
             self.plan = [list(batches(by_len(s), self.frames, max_batch_frames)) for s in self.shards]
         self.rounds = max((len(p) for p in self.plan), default=0)
