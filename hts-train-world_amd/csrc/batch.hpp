@@ -3,13 +3,14 @@
 // Context : one per (process, device): HIP stream, the universal randn table
 //           (matlabfunctions.cpp:247-277 as data), launch geometry.
 // Batch   : one per set of utterances: lengths/offsets on host and device, the
-//           frame->utterance map and every scratch buffer the kernels need, all
-//           allocated at creation so the analysis path never calls hipMalloc.
+//           frame->utterance map and the per-frame arrays several stages share,
+//           and each stage's own workspace, built on its first use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <map>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -30,6 +31,41 @@ hipError_t dev_alloc_bytes(void** p, size_t bytes);
 void dev_free(void* p);
 void dev_cache_trim(size_t keep_bytes);       // hipFree cached blocks until at most keep_bytes stay cached
 template <class T> inline hipError_t dev_alloc(T** p, size_t bytes) { return dev_alloc_bytes((void**)p, bytes); }
+
+// Device blocks freed together with their owner: alloc() records what it hands out.  Every stage keeps the state it
+// builds on first use in one such struct, private to its .hip file and owned by the batch (Batch::dio ... vibrato);
+// a set-up builds it in a local and moves it into the batch only once every allocation, copy, launch and
+// synchronisation has succeeded, so a failure leaves nothing half-built behind.
+struct StageWs {
+  std::vector<void*> owned;
+  template <class T> hipError_t alloc(T** p, size_t bytes) {
+    const hipError_t e = dev_alloc(p, bytes);
+    if (e == hipSuccess) owned.push_back(*p);
+    return e;
+  }
+  StageWs() = default;
+  StageWs(const StageWs&) = delete;
+  StageWs& operator=(const StageWs&) = delete;
+  virtual ~StageWs() {
+    for (void* p : owned) dev_free(p);
+  }
+};
+
+// A per-context table: its kind and that kind's parameters (compared exactly; unused ones 0), and its device blocks.
+enum TableKind { kDioFilters, kD4cWindow, kDcRemover, kSmTwiddles };
+struct TableKey {
+  TableKind kind;
+  double v[5];
+  bool operator==(const TableKey& o) const {
+    for (int i = 0; i < 5; ++i)
+      if (!(v[i] == o.v[i])) return false;
+    return kind == o.kind;
+  }
+};
+struct Table : StageWs {
+  TableKey key;
+  void* d[3] = {nullptr, nullptr, nullptr};
+};
 
 struct Context {
   int device = 0;
@@ -61,27 +97,32 @@ struct Context {
   hipEvent_t ev_f0 = nullptr, ev_prep = nullptr, ev_d4c = nullptr, ev_rare = nullptr;
   hipEvent_t ev_pulse[2] = {nullptr, nullptr}, ev_ola[2] = {nullptr, nullptr};   // synthesis_render's two response halves
   int ensure_side();                 // the second stream and its events, created on first use
-  // Dio's filters -- low-cut taps, Nuttall windows and their block spectra (fftconv.hpp) -- depend on the options and
-  // the sampling rate only, not on the utterances: built once per context and configuration and shared by every batch
-  // (the drop-in API makes a batch per utterance length: rebuilding them per batch was 0.1 ms of every Dio call)
-  struct DioFilters {
-    int fs, speed;
-    double f0_floor, f0_ceil, channels;
-    double* d_lowcut;
-    double* d_win;
-    void* d_H;
-  };
-  std::vector<DioFilters> dio_filters;
-  // likewise: D4C's Nuttall window by length (a function of the sampling rate) and StoneMask's DFT twiddle table
-  std::vector<std::pair<int, double*>> nuttall_windows;
-  std::vector<std::pair<int, double*>> dc_removers;   // Synthesis' GetDCRemover table by fft_size (a one-thread kernel:
-                                                      // 0.29 ms in front of every Synthesis() of a new utterance length)
-  void* d_sm_twid = nullptr;
+  // Tables that depend on a few parameters, not on the utterances (Dio's filters, D4C's Nuttall window, Synthesis' DC
+  // remover, StoneMask's twiddles): built once per context and key and shared by every batch of the context (the
+  // drop-in API makes a batch per utterance length: rebuilding them per batch was 0.1 - 0.3 ms of every call)
+  std::vector<std::unique_ptr<Table>> tables;
+  template <class Build> int table(const TableKey& key, const Table*& out, Build build);
   // optional per-kernel HIP-event timing on `stream` (bench.py's roofline leg)
   bool timing = false;
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> timed;
   void timing_clear();
 };
+
+// The table of `key`, built by build(Table&) -> WM_OK on first use.  An entry that fails to build is freed, not kept.
+template <class Build> int Context::table(const TableKey& key, const Table*& out, Build build) {
+  for (const auto& t : tables)
+    if (t->key == key) {
+      out = t.get();
+      return WM_OK;
+    }
+  std::unique_ptr<Table> t(new Table);
+  t->key = key;
+  const int rc = build(*t);
+  if (rc) return rc;
+  out = t.get();
+  tables.push_back(std::move(t));
+  return WM_OK;
+}
 
 // Grid of a grid-stride per-frame kernel: a small multiple (Context::oversub) of the workgroups that are resident
 // at once.  Exactly the resident number gives every wave slot the same share when the kernel has the machine to
@@ -160,7 +201,6 @@ struct Batch {
   double* d_ap0 = nullptr;           // [total_f] D4C LoveTrain result
   double* d_f0_tmp = nullptr;        // [total_f] raw DIO f0 before StoneMask
   int* d_perm = nullptr;             // [total_f] costly frames first (partition.hpp)
-  int* d_perm2 = nullptr;            // [total_f] D4C: frames that need the wide-margin kernel first
   int* d_part_cnt = nullptr;         // [total_f / 1024 + 2]
   int* d_part_n = nullptr;           // [4] number of listed frames
   // D4C's own offsets and lists: its preparation may run beside CheapTrick (d4c_prepare, d4c.hip)
@@ -168,69 +208,14 @@ struct Batch {
   int* d_perm_d4c = nullptr;         // [total_f]
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
-  void* d_sm_twid = nullptr;         // StoneMask's DFT twiddle table (stonemask.hip): the context's, not owned
-  // D4C tables
-  double* d_d4c_window = nullptr;    // Nuttall window of GetCoarseAperiodicity: the context's, not owned (non-null = D4C's tables are ready)
-  int* d_utt_total = nullptr;        // [n_utt] LoveTrain randn totals
-  double* d_d4c_big = nullptr;       // fft_size_d4c 4096: centroid quarters, centroid, group delay, coarse values per frame
-  // DIO workspace
-  bool dio_ready = false;
-  void* dio_host = nullptr;          // DioHost (dio.hip)
-  double* d_dio_lowcut = nullptr;    // low-cut FIR taps by lag
-  double* d_dio_win = nullptr;       // Nuttall low-pass windows, all bands
-  void* d_dio_desc = nullptr;        // ONE block holding the per-utterance tables below (fft, ylen, offsets): one upload
-  int* d_dio_fft = nullptr;          // [n_utt] the reference's fft_size (circular indexing)
-  double* d_dio_ws = nullptr;        // [3][total_f] contour work arrays
-  void* d_dio_H = nullptr;           // filter spectra of the FFT-convolution path (fftconv.hpp)
-  int* d_dio_edges = nullptr;        // [n_utt][2][edge_cap] edge lists of the contour fix when they outgrow LDS
-  int* d_dio_ylen = nullptr;         // [n_utt] y_length = 1 + N / speed
-  double* d_dio_y = nullptr;         // decimated signals (speed > 1)
-  double* d_dio_tmp = nullptr;       // decimation pass-1 output
-  int64_t* d_dio_yoff = nullptr;
-  int64_t* d_dio_toff = nullptr;
-  int64_t dio_tot_y = 0;
-  int dio_bands = 0;
-  double* d_dio_mean = nullptr;      // [n_utt]
-  double* d_dio_mean_part = nullptr; // [n_utt][32] partial sums
-  double* d_dio_z = nullptr;         // low-cut output, per utterance y_len + 2*pad
-  int64_t* d_dio_z_off = nullptr;
-  std::vector<int64_t> dio_z_off;
-  int dio_pad = 0;
-  double* d_dio_events = nullptr;    // fine edges, [utt][band][4][cap]
-  int64_t* d_dio_ev_off = nullptr;   // per utterance base into events (in doubles)
-  std::vector<int64_t> dio_ev_off;
-  int* d_dio_ev_cnt = nullptr;       // [utt][band][4]
-  int* d_dio_tile_cnt = nullptr;     // [utt][band][tile + 1][4] per-tile event counts, then offsets
-  double* d_dio_slots = nullptr;     // staged events, [utt][band][4][tiles(utt)][kZcSlot]
-  int64_t* d_dio_slot_off = nullptr; // per utterance base into d_dio_slots
-  double* d_dio_cand = nullptr;      // [band][total_f]
-  double* d_dio_score = nullptr;     // [band][total_f]
-  void* harvest_ws = nullptr;        // HarvestWs (harvest.hip)
-  void* codec_tables = nullptr;      // CodecTables (codec.hip)
-  void* vibrato_ws = nullptr;        // VibWs (vibrato.hip)
-  // Synthesis workspace: sections of one allocation (d_syn_arena), laid out by synthesis_prepare
-  void* d_syn_arena = nullptr;
-  int* d_pulse_idx = nullptr;        // [total_y]
-  double* d_pulse_shift = nullptr;   // [total_y]
-  double* d_vuv = nullptr;           // [total_y] interpolated vuv
-  double* d_phase = nullptr;         // [total_y] scratch (increments / wrapped phase)
-  int* d_pulse_cnt = nullptr;        // [n_utt]
-  int* d_pulse_tile_cnt = nullptr;   // [n_utt][tiles] pulses per search tile
-  int64_t* d_pulse_off = nullptr;    // [n_utt+1]
-  int* d_pulse_first = nullptr;      // first pulse at or after every 128th sample of an utterance (the overlap-add's table)
-  int* d_syn_order = nullptr;        // [2 n_utt] the identity, then the utterances by output length (shortest first)
-  std::vector<int> syn_sorted;       // host copy of the second half
-  std::vector<int> syn_order_host;   // what d_syn_order was uploaded from: kept alive, so the upload needs no wait
-  void* d_pulse_rec = nullptr;       // [pulse_rec_cap] PulseRec (synthesis.hip), grown on demand
-  int64_t pulse_rec_cap = 0;
-  int* d_pulse_perm = nullptr;       // [cap] voiced-first pulse order of a chunk, then n, then block counts
-  double* d_dc_remover = nullptr;    // [fft_size]: the context's, not owned
-  int64_t syn_total_p = 0, syn_chunk = 0;   // pulses of the prepared synthesis, pulses per piece (half of the response scratch)
+  // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato;
   bool syn_warm = false;                    // launch_analyze_synthesize has run once on this batch
 
   int64_t rng_bound_cheaptrick() const;
   int64_t rng_bound_d4c() const;
   int64_t rng_bound_synthesis() const;
+  ~Batch() { dev_free(d_arena); }
 };
 
 // kernel launchers (one translation unit each)

@@ -30,7 +30,6 @@ namespace wm {
 const char* last_error();
 void set_error(const char* msg);
 int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0);
-void free_batch_buffers(Batch& b);
 #ifdef WM_PHASE
 int phase_read_d4c(unsigned long long* out32);
 int phase_read_cheaptrick(unsigned long long* out32);
@@ -121,19 +120,7 @@ void WorldMi355DestroyContext(WorldMi355Context* h) {
   c.timing_clear();
   if (c.d_rng) wm::dev_free(c.d_rng);
   if (c.d_scratch) wm::dev_free(c.d_scratch);
-  for (auto& f : c.dio_filters) {
-    if (f.d_lowcut) wm::dev_free(f.d_lowcut);
-    if (f.d_win) wm::dev_free(f.d_win);
-    if (f.d_H) wm::dev_free(f.d_H);
-  }
-  c.dio_filters.clear();
-  for (auto& w : c.nuttall_windows)
-    if (w.second) wm::dev_free(w.second);
-  c.nuttall_windows.clear();
-  for (auto& w : c.dc_removers)
-    if (w.second) wm::dev_free(w.second);
-  c.dc_removers.clear();
-  if (c.d_sm_twid) wm::dev_free(c.d_sm_twid);
+  c.tables.clear();
   if (c.h_pulse_info) hipHostFree(c.h_pulse_info);
   if (c.own_stream) hipStreamDestroy(c.stream);
   if (c.side) { hipStreamSynchronize(c.side); hipStreamDestroy(c.side); }
@@ -240,13 +227,12 @@ int WorldMi355CreateBatch(WorldMi355Context* h, const WorldMi355Params* params, 
   }
   unsigned char* base = nullptr;
   int rc = wm_check(wm::dev_alloc(&base, at));
+  if (!rc) b.d_arena = base;                     // freed with the batch
   if (!rc) rc = wm_check(hipMemcpy(base, img.data(), init_bytes, hipMemcpyHostToDevice));
   if (rc) {
-    if (base) wm::dev_free(base);
     delete hb;
     return rc;
   }
-  b.d_arena = base;
   b.d_x_off = (int64_t*)(base + o_xoff); b.d_f_off = (int64_t*)(base + o_foff); b.d_y_off = (int64_t*)(base + o_yoff);
   b.d_x_len = (int*)(base + o_xlen); b.d_f0_len = (int*)(base + o_flen); b.d_y_len = (int*)(base + o_ylen);
   b.d_frame_utt = (int*)(base + o_futt);
@@ -264,7 +250,6 @@ void WorldMi355DestroyBatch(WorldMi355Batch* hb) {
   Batch& b = hb->b;
   OnDevice dev_(*b.ctx);
   hipStreamSynchronize(b.ctx->stream);
-  wm::free_batch_buffers(b);
   delete hb;
 }
 

@@ -297,21 +297,21 @@ static void interp_table(const std::vector<double>& x, const std::vector<double>
   }
 }
 
-struct CodecTables {
+struct CodecTables : StageWs {     // the batch's codec tables (Batch::codec)
   int* d_code_k = nullptr; double* d_code_s = nullptr; cpx* d_code_w = nullptr;
   int* d_dec_k = nullptr; double* d_dec_s = nullptr; cpx* d_dec_w = nullptr;
 };
 
 static int codec_setup(Batch& b) {
-  if (b.codec_tables) return WM_OK;
+  if (b.codec) return WM_OK;
   const int fs = b.p.fs, F = b.p.fft_size, md = F / 2, bins = F / 2 + 1;
   const double ceilf = fs / 2.0 < kCodecCeilFreq ? fs / 2.0 : kCodecCeilFreq;
   const double floor_mel = to_mel(kCodecFloorFreq), ceil_mel = to_mel(ceilf);
-  CodecTables* T = new CodecTables();
+  std::unique_ptr<CodecTables> T(new CodecTables());
   int rc = WM_OK;
   auto up = [&](void** dst, const void* src, size_t bytes) {
     if (rc) return;
-    rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
+    rc = wm_check(T->alloc(dst, bytes ? bytes : 8));
     if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
   };
   {   // coding: frequency axis in mel (knots) -> uniform mel axis (queries), GetParametersForCoding :161-180
@@ -344,17 +344,9 @@ static int codec_setup(Batch& b) {
     up((void**)&T->d_dec_s, s.data(), sizeof(double) * s.size());
     up((void**)&T->d_dec_w, w.data(), sizeof(cpx) * w.size());
   }
-  b.codec_tables = T;
-  return rc;
-}
-
-void codec_free(void* p) {
-  CodecTables* T = (CodecTables*)p;
-  if (!T) return;
-  void* ptrs[] = {T->d_code_k, T->d_code_s, T->d_code_w, T->d_dec_k, T->d_dec_s, T->d_dec_w};
-  for (void* q : ptrs)
-    if (q) dev_free(q);
-  delete T;
+  if (rc) return rc;
+  b.codec = std::move(T);
+  return WM_OK;
 }
 
 int codec_num_aperiodicities(int fs) {                              // codec.cpp:212-215
@@ -369,7 +361,7 @@ static int code_sp(Batch& b, const double* d_in, int ndim, CodeOpts o, OUT* d_ou
   if (ndim < 1 || ndim > F / 4 + 1) return WM_ERR_BAD_ARG;      // the reference reads spectrum[i], i <= fft_size/4
   int rc = codec_setup(b);
   if (rc) return rc;
-  const CodecTables& T = *(CodecTables*)b.codec_tables;
+  const CodecTables& T = static_cast<const CodecTables&>(*b.codec);
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
   hipStream_t st = b.ctx->stream;
@@ -402,7 +394,7 @@ static int decode_sp(Batch& b, const IN* d_coded, int ndim, DecodeOpts o, double
   if (ndim < 1 || ndim > F / 2) return WM_ERR_BAD_ARG;
   int rc = codec_setup(b);
   if (rc) return rc;
-  const CodecTables& T = *(CodecTables*)b.codec_tables;
+  const CodecTables& T = static_cast<const CodecTables&>(*b.codec);
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
   hipStream_t st = b.ctx->stream;

@@ -268,7 +268,7 @@ int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, doubl
   int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
   rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
   if (rc) return rc;
-  if (!b.d_d4c_window) {
+  if (!b.d4c) {
     rc = launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
     return rc ? rc : launch_d4c(b, d_x, d_t, d_f0, d_ap);
   }
@@ -347,29 +347,4 @@ int64_t Batch::rng_bound_d4c() const {
 }
 int64_t Batch::rng_bound_synthesis() const { return (int64_t)max_y_len + 64; }
 
-}  // namespace wm
-
-namespace wm {
-void dio_free_host(void* h);
-void harvest_free(void* p);
-void codec_free(void* p);
-void vibrato_free(void* p);
-
-void free_batch_buffers(Batch& b) {
-  void* ptrs[] = {b.d_arena, b.d_perm2, b.d_utt_total, b.d_d4c_big,
-                  // (Dio's filters are the context's, its per-utterance tables live in d_dio_desc)
-                  b.d_dio_desc, b.d_dio_ws, b.d_dio_edges, b.d_dio_y, b.d_dio_tmp, b.d_dio_mean, b.d_dio_mean_part, b.d_dio_z,
-                  b.d_dio_events, b.d_dio_ev_cnt, b.d_dio_tile_cnt, b.d_dio_slots, b.d_dio_cand,
-                  b.d_dio_score, b.d_syn_arena, b.d_pulse_rec, b.d_pulse_perm};
-  for (void* p : ptrs)
-    if (p) dev_free(p);
-  if (b.dio_host) dio_free_host(b.dio_host);
-  b.dio_host = nullptr;
-  if (b.harvest_ws) harvest_free(b.harvest_ws);
-  b.harvest_ws = nullptr;
-  if (b.codec_tables) codec_free(b.codec_tables);
-  b.codec_tables = nullptr;
-  if (b.vibrato_ws) vibrato_free(b.vibrato_ws);
-  b.vibrato_ws = nullptr;
-}
 }  // namespace wm

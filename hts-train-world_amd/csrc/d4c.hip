@@ -565,6 +565,16 @@ __global__ __launch_bounds__(64, WAVES) void d4c_kernel(
 #include "d4c_wide.hpp"
 namespace wm {
 
+// The batch's D4C state (Batch::d4c), made by d4c_prepare().
+struct D4cWs : StageWs {
+  const double* d_window = nullptr;  // Nuttall window of GetCoarseAperiodicity (the context's)
+  int* d_utt_total = nullptr;        // [n_utt] LoveTrain randn totals
+  int* d_perm2 = nullptr;            // [total_f] frames that need the wide-margin kernel first
+  double* d_big = nullptr;           // fft_size_d4c 4096 / 8192: centroid quarters, centroid, group delay, coarse values
+                                     // per frame (launch_d4c_big, on its first use)
+};
+static D4cWs& d4c_ws(Batch& b) { return static_cast<D4cWs&>(*b.d4c); }
+
 // fft_size_d4c = 4096 / 8192: the four-kernel form of d4c_big.hpp for the usual frames
 // Grid of the RARE launch: one round of resident workgroups, not `oversub` rounds -- its list is empty at the default
 // f0 range, and 6 144 workgroups of 33 KB LDS took 64 us to come and go (1 024: 12 us).
@@ -588,13 +598,14 @@ static int launch_d4c_big(Batch& b, const double* d_x, const double* d_t, const 
   constexpr int64_t kD4cBigChunk = 128 * 1024;
   const int64_t chunk = tf < kD4cBigChunk ? (tf > 0 ? tf : 1) : kD4cBigChunk;
   const size_t ws_rows = (size_t)g1;                               // scratch rows per workgroup of the centroid kernel
-  if (!b.d_d4c_big) {
+  D4cWs& W = d4c_ws(b);
+  if (!W.d_big) {
     const size_t per = (size_t)4 * G::kQ + (size_t)G::kRow;
-    int rc = wm_check(dev_alloc(&b.d_d4c_big, sizeof(double) * (per * (size_t)chunk + 8 * (size_t)(tf > 0 ? tf : 1) +
-                                                                        ws_rows * D4cBigWs<FD>::kDoubles)));
+    int rc = wm_check(W.alloc(&W.d_big, sizeof(double) * (per * (size_t)chunk + 8 * (size_t)(tf > 0 ? tf : 1) +
+                                                          ws_rows * D4cBigWs<FD>::kDoubles)));
     if (rc) return rc;
   }
-  double* C = b.d_d4c_big;
+  double* C = W.d_big;
   double* GD = C + (size_t)chunk * 4 * G::kQ;
   double* COARSE = GD + (size_t)chunk * G::kRow;
   double* WS = COARSE + (size_t)tf * 8;
@@ -631,7 +642,7 @@ static int launch_d4c_big(Batch& b, const double* d_x, const double* d_t, const 
 static int d4c_tables(Batch& b, D4CTables& tab) {
   const int fs = b.p.fs;
   const int FD = d4c_fft_size(fs);
-  tab.nuttall = b.d_d4c_window;
+  tab.nuttall = d4c_ws(b).d_window;
   tab.window_length = (int)(kFreqInterval * FD / fs) * 2 + 1;
   double lim = fs / 2.0 - kFreqInterval;
   tab.nap = (int)((kUpperLimit < lim ? kUpperLimit : lim) / kFreqInterval);
@@ -652,32 +663,32 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
   if (b.p.d4c_threshold > 0.0 && FL != 1024 && FL != 2048 && FL != 4096 && FL != 8192) return WM_ERR_UNSUPPORTED_FFT;
   int rc = c.ensure_rng(b.rng_bound_d4c());
   if (rc) return rc;
-  // Nuttall window table for GetCoarseAperiodicity (d4c.cpp:356-359, common.cpp:113-121)
-  const int wl = (int)(kFreqInterval * FD / fs) * 2 + 1;
-  if (!b.d_d4c_window) {
-    double* dw = nullptr;
-    for (const auto& e : c.nuttall_windows)
-      if (e.first == wl) dw = e.second;
-    if (!dw) {                                           // once per context and sampling rate
+  if (!b.d4c) {
+    // Nuttall window table for GetCoarseAperiodicity (d4c.cpp:356-359, common.cpp:113-121): once per context and
+    // window length (a function of the sampling rate)
+    const int wl = (int)(kFreqInterval * FD / fs) * 2 + 1;
+    const Table* win = nullptr;
+    rc = c.table({kD4cWindow, {(double)wl}}, win, [&](Table& t) {
       std::vector<double> w((size_t)wl);
       for (int i = 0; i < wl; ++i) {
         double tmp = i / (wl - 1.0);
         w[(size_t)i] = 0.355768 - 0.487396 * cos(2.0 * kPi * tmp) + 0.144232 * cos(4.0 * kPi * tmp) -
                        0.012604 * cos(6.0 * kPi * tmp);
       }
-      rc = wm_check(dev_alloc(&dw, sizeof(double) * (size_t)wl));
-      if (rc) return rc;
-      rc = wm_check(hipMemcpyAsync(dw, w.data(), sizeof(double) * (size_t)wl, hipMemcpyHostToDevice, st));
-      if (!rc) rc = wm_check(hipStreamSynchronize(st));   // w is a stack-lifetime buffer
-      if (rc) { dev_free(dw); return rc; }
-      c.nuttall_windows.push_back(std::make_pair(wl, dw));
-    }
-    if (!b.d_utt_total) rc = wm_check(dev_alloc(&b.d_utt_total, sizeof(int) * (size_t)b.n_utt));
-    if (!rc && !b.d_perm2)                               // StoneMask may have taken it already
-      rc = wm_check(dev_alloc(&b.d_perm2, sizeof(int) * (size_t)(b.total_f > 0 ? b.total_f : 1)));
+      int r = wm_check(t.alloc(&t.d[0], sizeof(double) * (size_t)wl));
+      if (!r) r = wm_check(hipMemcpyAsync(t.d[0], w.data(), sizeof(double) * (size_t)wl, hipMemcpyHostToDevice, st));
+      if (!r) r = wm_check(hipStreamSynchronize(st));   // w is a stack-lifetime buffer
+      return r;
+    });
     if (rc) return rc;
-    b.d_d4c_window = dw;
+    std::unique_ptr<D4cWs> W(new D4cWs());
+    W->d_window = (const double*)win->d[0];
+    rc = wm_check(W->alloc(&W->d_utt_total, sizeof(int) * (size_t)b.n_utt));
+    if (!rc) rc = wm_check(W->alloc(&W->d_perm2, sizeof(int) * (size_t)(b.total_f > 0 ? b.total_f : 1)));
+    if (rc) return rc;
+    b.d4c = std::move(W);
   }
+  D4cWs& W = d4c_ws(b);
   D4CTables tab;
   rc = d4c_tables(b, tab);
   if (rc) return rc;
@@ -685,7 +696,7 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
   const int64_t tf = b.total_f;
   const int grid = (int)(tf < (int64_t)c.frame_grid ? tf : (int64_t)c.frame_grid);
   hipLaunchKernelGGL(d4c_offsets_kernel<0>, dim3(b.n_utt), dim3(256), 0, st, d_f0, (const double*)nullptr,
-                     b.d_f_off, fs, b.p.d4c_threshold, b.d_utt_total, b.d_rng_off2);
+                     b.d_f_off, fs, b.p.d4c_threshold, W.d_utt_total, b.d_rng_off2);
   launch_partition(st, VoicedPred{d_f0}, (int)tf, b.d_part_cnt_d4c, b.d_perm_d4c, b.d_part_n_d4c);
 #define WM_LT_CASE(FF)                                                                                     \
   case FF: {                                                                                               \
@@ -716,12 +727,12 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
   }
 #undef WM_LT_CASE
   hipLaunchKernelGGL(d4c_offsets_kernel<1>, dim3(b.n_utt), dim3(256), 0, st, d_f0, (const double*)b.d_ap0,
-                     b.d_f_off, fs, b.p.d4c_threshold, b.d_utt_total, b.d_rng_off_d4c);
+                     b.d_f_off, fs, b.p.d4c_threshold, W.d_utt_total, b.d_rng_off_d4c);
   launch_partition(st, D4cRunUsualPred{d_f0, b.d_ap0, b.p.d4c_threshold, FD, fs}, (int)tf, b.d_part_cnt_d4c, b.d_perm_d4c,
                    b.d_part_n_d4c);
   // the rare frames (f0 >= fs / 16, or a window longer than FD / 2 samples) are listed separately for the
   // wide-margin, long-frame instantiation; an empty list costs that launch a few microseconds
-  launch_partition(st, D4cRunRarePred{d_f0, b.d_ap0, b.p.d4c_threshold, FD, fs}, (int)tf, b.d_part_cnt_d4c, b.d_perm2,
+  launch_partition(st, D4cRunRarePred{d_f0, b.d_ap0, b.p.d4c_threshold, FD, fs}, (int)tf, b.d_part_cnt_d4c, W.d_perm2,
                    b.d_part_n_d4c + 1);
   return wm_check(hipGetLastError());
 }
@@ -734,6 +745,7 @@ int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0,
   D4CTables tab;
   int rc = d4c_tables(b, tab);
   if (rc) return rc;
+  const int* perm2 = d4c_ws(b).d_perm2;
   const int64_t tf = b.total_f;
   const int grid = (int)(tf < (int64_t)c.frame_grid ? tf : (int64_t)c.frame_grid);
   // The RARE launch on its own: its rows are its own (the other kernels leave them alone), so it needs nothing of
@@ -748,7 +760,7 @@ int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0,
     hipLaunchKernelGGL((d4c_kernel<FF, 1, true>), dim3(imin(grid, rare_grid(c, per2_))), dim3(64), 0, st, d_x, \
                        b.d_x_off, b.d_x_len, b.d_frame_utt, d_t, d_f0, (const double*)b.d_ap0,            \
                        b.d_rng_off_d4c, c.d_rng, fs, b.p.d4c_threshold, tab, b.p.fft_size, tf,            \
-                       (const int*)b.d_perm2, (const int*)(b.d_part_n_d4c + 1), d_ap);                    \
+                       perm2, (const int*)(b.d_part_n_d4c + 1), d_ap);                                    \
   } break;
   switch (FD) {
     WM_D4C_RARE(1024)
@@ -759,7 +771,7 @@ int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0,
       allow_dynamic_lds(c, d4c_wide_kernel<8192>, lds);
       hipLaunchKernelGGL(d4c_wide_kernel<8192>, dim3(imin(grid, c.num_cu)), dim3(kWideThreads), lds, st, d_x, b.d_x_off,
                          b.d_x_len, b.d_frame_utt, d_t, d_f0, b.d_rng_off_d4c, c.d_rng, fs, tab, b.p.fft_size,
-                         (const int*)b.d_perm2, (const int*)(b.d_part_n_d4c + 1), d_ap);
+                         perm2, (const int*)(b.d_part_n_d4c + 1), d_ap);
     } break;
   }
 #undef WM_D4C_RARE

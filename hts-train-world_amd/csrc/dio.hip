@@ -468,34 +468,91 @@ static int suitable_fft_size(int sample) {   // common.cpp:51-54
   return (int)pow(2.0, (int)(log((double)sample) / kLog2) + 1.0);
 }
 
-struct DioHost {
+// The batch's Dio state (Batch::dio).  The filters are the context's table, the rest the batch's own.
+struct DioWs : StageWs {
   DioMeta meta;
-  std::vector<double> lowcut, win;
+  const double* d_lowcut = nullptr;  // low-cut FIR taps by lag (the context's)
+  const double* d_win = nullptr;     // Nuttall low-pass windows, all bands (the context's)
+  const cpx* d_H = nullptr;          // filter spectra of the FFT-convolution path, fftconv.hpp (the context's)
+  int* d_fft = nullptr;              // [n_utt] the reference's fft_size (circular indexing); d_fft .. d_slot_off are
+                                     // sections of ONE block of per-utterance tables: one upload
+  int* d_ylen = nullptr;             // [n_utt] y_length = 1 + N / speed
+  int64_t* d_yoff = nullptr;
+  int64_t* d_toff = nullptr;
+  int64_t* d_z_off = nullptr;
+  int64_t* d_ev_off = nullptr;       // per utterance base into events (in doubles)
+  int64_t* d_slot_off = nullptr;     // per utterance base into d_slots
+  double* d_ws = nullptr;            // [3][total_f] contour work arrays
+  int* d_edges = nullptr;            // [n_utt][2][edge_cap] edge lists of the contour fix when they outgrow LDS
+  double* d_y = nullptr;             // decimated signals (speed > 1)
+  double* d_tmp = nullptr;           // decimation pass-1 output
+  int64_t tot_y = 0;
+  double* d_mean = nullptr;          // [n_utt]
+  double* d_mean_part = nullptr;     // [n_utt][32] partial sums
+  double* d_z = nullptr;             // low-cut output, per utterance y_len + 2*pad
+  double* d_events = nullptr;        // fine edges, [utt][band][4][cap]
+  int* d_ev_cnt = nullptr;           // [utt][band][4]
+  int* d_tile_cnt = nullptr;         // [utt][band][tile + 1][4] per-tile event counts, then offsets
+  double* d_slots = nullptr;         // staged events, [utt][band][4][tiles(utt)][kZcSlot]
+  double* d_cand = nullptr;          // [band][total_f]
+  double* d_score = nullptr;         // [band][total_f]
 };
 
-// frees every device buffer dio_setup() allocates and clears the pointers (the filters belong to the context)
-static void dio_release(Batch& b) {
-  void** ptrs[] = {(void**)&b.d_dio_desc, (void**)&b.d_dio_mean, (void**)&b.d_dio_mean_part, (void**)&b.d_dio_y,
-                   (void**)&b.d_dio_tmp, (void**)&b.d_dio_z, (void**)&b.d_dio_events, (void**)&b.d_dio_ev_cnt,
-                   (void**)&b.d_dio_tile_cnt, (void**)&b.d_dio_slots, (void**)&b.d_dio_cand, (void**)&b.d_dio_score,
-                   (void**)&b.d_dio_ws};
-  for (void** p : ptrs) {
-    if (*p) dev_free(*p);
-    *p = nullptr;
+// Taps and windows as the reference designs them, and the filter spectra of the FFT-convolution path: [0] low-cut
+// (block lc_conv), [1 .. nb] bands (block band_conv).  t.d = {low-cut taps, windows, spectra or null}.
+static int dio_filters(Context& c, const DioMeta& m, const std::vector<double>& lowcut, const std::vector<double>& win,
+                       Table& t) {
+  int rc = WM_OK;
+  auto up = [&](StageWs& o, void** dst, const void* src, size_t bytes) {
+    if (rc) return;
+    rc = wm_check(o.alloc(dst, bytes ? bytes : 8));
+    if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  };
+  up(t, &t.d[0], lowcut.data(), sizeof(double) * lowcut.size());
+  up(t, &t.d[1], win.data(), sizeof(double) * win.size());
+  if (rc || !(m.band_conv || m.lc_conv)) return rc;
+  const size_t n_lc = m.lc_conv ? (size_t)m.lc_conv / 2 + 1 : 0, n_bd = m.band_conv ? (size_t)m.band_conv / 2 + 1 : 0;
+  rc = wm_check(t.alloc(&t.d[2], sizeof(cpx) * (n_lc + (size_t)m.nb * n_bd)));
+  std::vector<int> desc(3 * ((size_t)m.nb + 1));
+  const int n1 = m.nb + 1;
+  desc[0] = 0; desc[(size_t)n1] = 2 * m.cut + 1; desc[2 * (size_t)n1] = 0;
+  for (int i = 0; i < m.nb; ++i) {
+    desc[(size_t)i + 1] = m.win_off[i];
+    desc[(size_t)n1 + i + 1] = 4 * m.hal[i];
+    desc[2 * (size_t)n1 + i + 1] = 2 * (m.hal[0] - m.hal[i]);
   }
-  b.d_dio_lowcut = b.d_dio_win = nullptr;
-  b.d_dio_H = nullptr;
-  b.d_dio_fft = b.d_dio_ylen = nullptr;
-  b.d_dio_yoff = b.d_dio_toff = b.d_dio_z_off = b.d_dio_ev_off = b.d_dio_slot_off = nullptr;
+  StageWs tmp;                                           // the descriptors: freed once the spectra are made
+  int* d_desc = nullptr;
+  up(tmp, (void**)&d_desc, desc.data(), sizeof(int) * desc.size());
+  if (rc) return rc;
+  const double* d_lowcut = (const double*)t.d[0];
+  const double* d_win = (const double*)t.d[1];
+  cpx* Hs = (cpx*)t.d[2];
+  hipStream_t st = c.stream;
+  if (m.lc_conv == 2048)
+    hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(1), dim3(64), 0, st, d_lowcut, d_desc, d_desc + n1,
+                       d_desc + 2 * n1, Hs);
+  else if (m.lc_conv == 4096)
+    hipLaunchKernelGGL(conv_spectrum_kernel<4096>, dim3(1), dim3(64), 0, st, d_lowcut, d_desc, d_desc + n1,
+                       d_desc + 2 * n1, Hs);
+  if (m.band_conv == 4096)
+    hipLaunchKernelGGL(conv_spectrum_kernel<4096>, dim3(m.nb), dim3(64), 0, st, d_win, d_desc + 1,
+                       d_desc + n1 + 1, d_desc + 2 * n1 + 1, Hs + n_lc);
+  else if (m.band_conv)
+    hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(m.nb), dim3(64), 0, st, d_win, d_desc + 1,
+                       d_desc + n1 + 1, d_desc + 2 * n1 + 1, Hs + n_lc);
+  rc = wm_check(hipGetLastError());
+  if (!rc) rc = wm_check(hipStreamSynchronize(st));
+  return rc;
 }
 
 static int dio_setup(Batch& b) {
-  if (b.dio_ready) return WM_OK;
+  if (b.dio) return WM_OK;
   const WorldMi355Params& p = b.p;
-  DioHost* H = new DioHost();
-  DioMeta& m = H->meta;
+  std::unique_ptr<DioWs> W(new DioWs());
+  DioMeta& m = W->meta;
   m.nb = 1 + (int)(log(p.f0_ceil / p.f0_floor) / kLog2 * p.channels_in_octave);      // dio.cpp:582-583
-  if (m.nb < 1 || m.nb > kMaxBands) { delete H; return WM_ERR_UNSUPPORTED; }
+  if (m.nb < 1 || m.nb > kMaxBands) return WM_ERR_UNSUPPORTED;
   m.ratio = imax(imin(p.speed, 12), 1);                                                // :589
   m.afs = (double)p.fs / m.ratio;
   int woff = 0;
@@ -514,13 +571,13 @@ static int dio_setup(Batch& b) {
   m.lc_conv = 2 * m.cut + 1 <= 1024 ? 2048 : (2 * m.cut + 1 <= 4000 ? 4096 : 0);
   m.step = m.band_conv ? imin(m.band_conv - 4 * m.hal[0] + 1 - 2, 64 * kDioConvC) : kZcStep;
   // Nuttall low-pass windows (dio.cpp:301, common.cpp:113-121)
-  H->win.resize((size_t)woff);
+  std::vector<double> win((size_t)woff), lowcut((size_t)(2 * m.cut + 1));
   for (int i = 0; i < m.nb; ++i) {
     const int n = 4 * m.hal[i];
     for (int j = 0; j < n; ++j) {
       double tmp = j / (n - 1.0);
-      H->win[(size_t)(m.win_off[i] + j)] = 0.355768 - 0.487396 * cos(2.0 * kPi * tmp) +
-                                           0.144232 * cos(4.0 * kPi * tmp) - 0.012604 * cos(6.0 * kPi * tmp);
+      win[(size_t)(m.win_off[i] + j)] = 0.355768 - 0.487396 * cos(2.0 * kPi * tmp) +
+                                        0.144232 * cos(4.0 * kPi * tmp) - 0.012604 * cos(6.0 * kPi * tmp);
     }
   }
   // low-cut filter as a function of lag in [-cut, cut] (DesignLowCutFilter, dio.cpp:40-53)
@@ -532,30 +589,28 @@ static int dio_setup(Batch& b) {
       lc[(size_t)(i - 1)] = 0.5 - 0.5 * cos(i * 2.0 * kPi / (N + 1));
       sum += lc[(size_t)(i - 1)];
     }
-    H->lowcut.resize((size_t)N);
-    for (int i = 0; i < N; ++i) H->lowcut[(size_t)i] = -lc[(size_t)i] / sum;   // lag = i - cut
-    H->lowcut[(size_t)m.cut] += 1.0;
+    for (int i = 0; i < N; ++i) lowcut[(size_t)i] = -lc[(size_t)i] / sum;   // lag = i - cut
+    lowcut[(size_t)m.cut] += 1.0;
   }
   // per-utterance FFT size of the reference's circular convolution (dio.cpp:590-593)
   std::vector<int> fftn((size_t)b.n_utt), ylens((size_t)b.n_utt);
   std::vector<int64_t> yoff((size_t)b.n_utt + 1, 0), toff((size_t)b.n_utt + 1, 0);
-  b.dio_z_off.assign((size_t)b.n_utt + 1, 0);
-  b.dio_ev_off.assign((size_t)b.n_utt + 1, 0);
+  std::vector<int64_t> z_off((size_t)b.n_utt + 1, 0), ev_off((size_t)b.n_utt + 1, 0);
   for (int u = 0; u < b.n_utt; ++u) {
     const int ylen = 1 + b.x_len[u] / m.ratio;                                          // dio.cpp:590
     ylens[(size_t)u] = ylen;
     yoff[(size_t)u + 1] = yoff[(size_t)u] + ylen;
     toff[(size_t)u + 1] = toff[(size_t)u] + b.x_len[u] + 18;
     fftn[(size_t)u] = suitable_fft_size(ylen + 4 * (int)(1.0 + m.afs / m.boundary[0] / 2.0));
-    b.dio_z_off[(size_t)u + 1] = b.dio_z_off[(size_t)u] + ylen + 2 * m.pad;
-    b.dio_ev_off[(size_t)u + 1] = b.dio_ev_off[(size_t)u] + (int64_t)m.nb * 4 * (ylen / 2 + 2);
+    z_off[(size_t)u + 1] = z_off[(size_t)u] + ylen + 2 * m.pad;
+    ev_off[(size_t)u + 1] = ev_off[(size_t)u] + (int64_t)m.nb * 4 * (ylen / 2 + 2);
   }
   int rc = WM_OK;
   // slot offsets of the staged events (needed below, part of the same upload)
   std::vector<int64_t> soff((size_t)b.n_utt + 1, 0);
   for (int u = 0; u < b.n_utt; ++u)
     soff[(size_t)u + 1] = soff[(size_t)u] + (int64_t)m.nb * 4 * dio_tiles(ylens[(size_t)u], m.step) * kZcSlot;
-  if (m.ratio > 1) b.dio_tot_y = yoff[(size_t)b.n_utt];
+  if (m.ratio > 1) W->tot_y = yoff[(size_t)b.n_utt];
   // The per-utterance tables in ONE block and one upload (a batch per utterance length is what the drop-in API makes:
   // eight synchronous copies of a few bytes each were 0.1 ms of every Dio call).  Sections are 8-byte aligned.
   {
@@ -567,128 +622,63 @@ static int dio_setup(Batch& b) {
     int64_t* bl = blob.data() + ints / 2;
     memcpy(bl + 0 * n1, yoff.data(), 8 * n1);
     memcpy(bl + 1 * n1, toff.data(), 8 * n1);
-    memcpy(bl + 2 * n1, b.dio_z_off.data(), 8 * n1);
-    memcpy(bl + 3 * n1, b.dio_ev_off.data(), 8 * n1);
+    memcpy(bl + 2 * n1, z_off.data(), 8 * n1);
+    memcpy(bl + 3 * n1, ev_off.data(), 8 * n1);
     memcpy(bl + 4 * n1, soff.data(), 8 * n1);
-    rc = wm_check(dev_alloc(&b.d_dio_desc, 8 * blob.size()));
-    if (!rc) rc = wm_check(hipMemcpy(b.d_dio_desc, blob.data(), 8 * blob.size(), hipMemcpyHostToDevice));
+    void* d_desc = nullptr;
+    rc = wm_check(W->alloc(&d_desc, 8 * blob.size()));
+    if (!rc) rc = wm_check(hipMemcpy(d_desc, blob.data(), 8 * blob.size(), hipMemcpyHostToDevice));
     if (!rc) {
-      int* di = (int*)b.d_dio_desc;
-      int64_t* dl = (int64_t*)b.d_dio_desc + ints / 2;
-      b.d_dio_fft = di;
-      b.d_dio_ylen = di + n;
-      b.d_dio_yoff = m.ratio > 1 ? dl + 0 * n1 : nullptr;
-      b.d_dio_toff = m.ratio > 1 ? dl + 1 * n1 : nullptr;
-      b.d_dio_z_off = dl + 2 * n1;
-      b.d_dio_ev_off = dl + 3 * n1;
-      b.d_dio_slot_off = dl + 4 * n1;
+      int* di = (int*)d_desc;
+      int64_t* dl = (int64_t*)d_desc + ints / 2;
+      W->d_fft = di;
+      W->d_ylen = di + n;
+      W->d_yoff = m.ratio > 1 ? dl + 0 * n1 : nullptr;
+      W->d_toff = m.ratio > 1 ? dl + 1 * n1 : nullptr;
+      W->d_z_off = dl + 2 * n1;
+      W->d_ev_off = dl + 3 * n1;
+      W->d_slot_off = dl + 4 * n1;
     }
   }
   auto al = [&](void** dst, size_t bytes) {
     if (rc) return;
-    rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
+    rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
   };
-  al((void**)&b.d_dio_mean, sizeof(double) * (size_t)b.n_utt);
-  al((void**)&b.d_dio_mean_part, sizeof(double) * (size_t)b.n_utt * kMeanTiles);
+  al((void**)&W->d_mean, sizeof(double) * (size_t)b.n_utt);
+  al((void**)&W->d_mean_part, sizeof(double) * (size_t)b.n_utt * kMeanTiles);
   if (m.ratio > 1) {
-    al((void**)&b.d_dio_y, sizeof(double) * (size_t)yoff[(size_t)b.n_utt]);
-    al((void**)&b.d_dio_tmp, sizeof(double) * (size_t)toff[(size_t)b.n_utt]);
+    al((void**)&W->d_y, sizeof(double) * (size_t)yoff[(size_t)b.n_utt]);
+    al((void**)&W->d_tmp, sizeof(double) * (size_t)toff[(size_t)b.n_utt]);
   }
-  al((void**)&b.d_dio_z, sizeof(double) * (size_t)b.dio_z_off[(size_t)b.n_utt]);
-  al((void**)&b.d_dio_events, sizeof(double) * (size_t)b.dio_ev_off[(size_t)b.n_utt]);
-  al((void**)&b.d_dio_ev_cnt, sizeof(int) * (size_t)b.n_utt * m.nb * 4);
-  al((void**)&b.d_dio_tile_cnt,
+  al((void**)&W->d_z, sizeof(double) * (size_t)z_off[(size_t)b.n_utt]);
+  al((void**)&W->d_events, sizeof(double) * (size_t)ev_off[(size_t)b.n_utt]);
+  al((void**)&W->d_ev_cnt, sizeof(int) * (size_t)b.n_utt * m.nb * 4);
+  al((void**)&W->d_tile_cnt,
      sizeof(int) * (size_t)b.n_utt * m.nb * 4 * ((size_t)dio_tiles(b.max_x_len / m.ratio + 1, m.step) + 1));
-  al((void**)&b.d_dio_slots, sizeof(double) * (size_t)soff[(size_t)b.n_utt]);
-  al((void**)&b.d_dio_cand, sizeof(double) * (size_t)m.nb * (size_t)b.total_f);
-  al((void**)&b.d_dio_score, sizeof(double) * (size_t)m.nb * (size_t)b.total_f);
-  al((void**)&b.d_dio_ws, sizeof(double) * 3 * (size_t)b.total_f);
-  // The filters: the context's, by configuration.  Taps and windows as the reference designs them (above); the filter
-  // spectra of the FFT-convolution path: [0] low-cut (block lc_conv), [1 .. nb] bands (block band_conv).
-  if (!rc) {
-    Context& c = *b.ctx;
-    const Context::DioFilters* hit = nullptr;
-    for (const auto& f : c.dio_filters)
-      if (f.fs == p.fs && f.speed == m.ratio && f.f0_floor == p.f0_floor && f.f0_ceil == p.f0_ceil &&
-          f.channels == p.channels_in_octave)
-        hit = &f;
-    if (!hit) {
-      Context::DioFilters f{p.fs, m.ratio, p.f0_floor, p.f0_ceil, p.channels_in_octave, nullptr, nullptr, nullptr};
-      auto up = [&](void** dst, const void* src, size_t bytes) {
-        if (rc) return;
-        rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
-        if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-      };
-      up((void**)&f.d_lowcut, H->lowcut.data(), sizeof(double) * H->lowcut.size());
-      up((void**)&f.d_win, H->win.data(), sizeof(double) * H->win.size());
-      if (!rc && (m.band_conv || m.lc_conv)) {
-        const size_t n_lc = m.lc_conv ? (size_t)m.lc_conv / 2 + 1 : 0, n_bd = m.band_conv ? (size_t)m.band_conv / 2 + 1 : 0;
-        rc = wm_check(dev_alloc(&f.d_H, sizeof(cpx) * (n_lc + (size_t)m.nb * n_bd)));
-        std::vector<int> desc(3 * ((size_t)m.nb + 1));
-        const int n1 = m.nb + 1;
-        desc[0] = 0; desc[(size_t)n1] = 2 * m.cut + 1; desc[2 * (size_t)n1] = 0;
-        for (int i = 0; i < m.nb; ++i) {
-          desc[(size_t)i + 1] = m.win_off[i];
-          desc[(size_t)n1 + i + 1] = 4 * m.hal[i];
-          desc[2 * (size_t)n1 + i + 1] = 2 * (m.hal[0] - m.hal[i]);
-        }
-        int* d_desc = nullptr;
-        up((void**)&d_desc, desc.data(), sizeof(int) * desc.size());
-        if (!rc) {
-          cpx* Hs = (cpx*)f.d_H;
-          hipStream_t st = c.stream;
-          if (m.lc_conv == 2048)
-            hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(1), dim3(64), 0, st, f.d_lowcut, d_desc, d_desc + n1,
-                               d_desc + 2 * n1, Hs);
-          else if (m.lc_conv == 4096)
-            hipLaunchKernelGGL(conv_spectrum_kernel<4096>, dim3(1), dim3(64), 0, st, f.d_lowcut, d_desc, d_desc + n1,
-                               d_desc + 2 * n1, Hs);
-          if (m.band_conv == 4096)
-            hipLaunchKernelGGL(conv_spectrum_kernel<4096>, dim3(m.nb), dim3(64), 0, st, f.d_win, d_desc + 1,
-                               d_desc + n1 + 1, d_desc + 2 * n1 + 1, Hs + n_lc);
-          else if (m.band_conv)
-            hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(m.nb), dim3(64), 0, st, f.d_win, d_desc + 1,
-                               d_desc + n1 + 1, d_desc + 2 * n1 + 1, Hs + n_lc);
-          rc = wm_check(hipGetLastError());
-          if (!rc) rc = wm_check(hipStreamSynchronize(st));
-        }
-        if (d_desc) dev_free(d_desc);
-      }
-      if (rc) {
-        if (f.d_lowcut) dev_free(f.d_lowcut);
-        if (f.d_win) dev_free(f.d_win);
-        if (f.d_H) dev_free(f.d_H);
-      } else {
-        // kept for the life of the context (about 150 KB per configuration; batches hold the pointers)
-        c.dio_filters.push_back(f);
-        hit = &c.dio_filters.back();
-      }
-    }
-    if (!rc) {
-      b.d_dio_lowcut = hit->d_lowcut;
-      b.d_dio_win = hit->d_win;
-      b.d_dio_H = hit->d_H;
-    }
-  }
-  if (rc) {
-    // nothing half-built stays behind: a retry starts from scratch instead of leaking H and the buffers above
-    dio_release(b);
-    delete H;
-    return rc;
-  }
-  b.dio_host = H;
-  b.dio_ready = true;
+  al((void**)&W->d_slots, sizeof(double) * (size_t)soff[(size_t)b.n_utt]);
+  al((void**)&W->d_cand, sizeof(double) * (size_t)m.nb * (size_t)b.total_f);
+  al((void**)&W->d_score, sizeof(double) * (size_t)m.nb * (size_t)b.total_f);
+  al((void**)&W->d_ws, sizeof(double) * 3 * (size_t)b.total_f);
+  // the filters: the context's, by configuration (about 150 KB each, kept for the life of the context)
+  const Table* f = nullptr;
+  if (!rc)
+    rc = b.ctx->table({kDioFilters, {(double)p.fs, (double)m.ratio, p.f0_floor, p.f0_ceil, p.channels_in_octave}}, f,
+                      [&](Table& t) { return dio_filters(*b.ctx, m, lowcut, win, t); });
+  if (rc) return rc;
+  W->d_lowcut = (const double*)f->d[0];
+  W->d_win = (const double*)f->d[1];
+  W->d_H = (const cpx*)f->d[2];
+  b.dio = std::move(W);
   return WM_OK;
 }
-
-void dio_free_host(void* h) { delete (DioHost*)h; }
 
 int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   int rc = dio_setup(b);
   if (rc) return rc;
   Context& c = *b.ctx;
   hipStream_t st = c.stream;
-  const DioMeta& m = ((DioHost*)b.dio_host)->meta;
+  DioWs& W = static_cast<DioWs&>(*b.dio);
+  const DioMeta& m = W.meta;
   // speed > 1: decimate first (dio.cpp:68-70); the rest of the chain then reads the decimated signal
   const double* src = d_x;
   const int64_t* src_off = b.d_x_off;
@@ -697,17 +687,17 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
     const DecMeta dm = make_dec_meta(m.ratio, 0);
     const int len_max = b.max_x_len + 18;
     const int blocks = (len_max + 64 * kDecChunk - 1) / (64 * kDecChunk);
-    (void)hipMemsetAsync(b.d_dio_y, 0, sizeof(double) * (size_t)b.dio_tot_y, st);
+    (void)hipMemsetAsync(W.d_y, 0, sizeof(double) * (size_t)W.tot_y, st);
     hipLaunchKernelGGL(decim_fwd_kernel, dim3(blocks, b.n_utt), dim3(64), 0, st, d_x, b.d_x_off, b.d_x_len, dm,
-                       b.d_dio_toff, b.d_dio_tmp);
-    hipLaunchKernelGGL(decim_bwd_kernel, dim3(blocks, b.n_utt), dim3(64), 0, st, b.d_x_len, dm, b.d_dio_toff,
-                       b.d_dio_tmp, b.d_dio_yoff, b.d_dio_ylen, b.d_dio_y);
-    src = b.d_dio_y; src_off = b.d_dio_yoff; src_len = b.d_dio_ylen;
+                       W.d_toff, W.d_tmp);
+    hipLaunchKernelGGL(decim_bwd_kernel, dim3(blocks, b.n_utt), dim3(64), 0, st, b.d_x_len, dm, W.d_toff,
+                       W.d_tmp, W.d_yoff, W.d_ylen, W.d_y);
+    src = W.d_y; src_off = W.d_yoff; src_len = W.d_ylen;
   }
   hipLaunchKernelGGL(dio_mean_partial_kernel, dim3(kMeanTiles, b.n_utt), dim3(256), 0, st, src, src_off, src_len,
-                     b.d_dio_mean_part);
-  hipLaunchKernelGGL(dio_mean_kernel, dim3((b.n_utt + 255) / 256), dim3(256), 0, st, b.d_dio_mean_part, b.d_dio_ylen,
-                     b.n_utt, b.d_dio_mean);
+                     W.d_mean_part);
+  hipLaunchKernelGGL(dio_mean_kernel, dim3((b.n_utt + 255) / 256), dim3(256), 0, st, W.d_mean_part, W.d_ylen,
+                     b.n_utt, W.d_mean);
   {
     const int total_max = b.max_x_len / m.ratio + 1 + 2 * m.pad;
     const int tiles = (total_max + kBandTile - 1) / kBandTile;
@@ -720,19 +710,19 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
       const int V = m.lc_conv - ntap + 1;
       const dim3 grid((total_max + V - 1) / V, b.n_utt);
       if (m.lc_conv == 2048)
-        hipLaunchKernelGGL(dio_lowcut_fft_kernel<2048>, grid, dim3(64), 0, st, src, src_off, src_len, b.d_dio_ylen,
-                           b.d_dio_mean, b.d_dio_fft, (const cpx*)b.d_dio_H, m, b.d_dio_z_off, b.d_dio_z);
+        hipLaunchKernelGGL(dio_lowcut_fft_kernel<2048>, grid, dim3(64), 0, st, src, src_off, src_len, W.d_ylen,
+                           W.d_mean, W.d_fft, W.d_H, m, W.d_z_off, W.d_z);
       else
-        hipLaunchKernelGGL(dio_lowcut_fft_kernel<4096>, grid, dim3(64), 0, st, src, src_off, src_len, b.d_dio_ylen,
-                           b.d_dio_mean, b.d_dio_fft, (const cpx*)b.d_dio_H, m, b.d_dio_z_off, b.d_dio_z);
+        hipLaunchKernelGGL(dio_lowcut_fft_kernel<4096>, grid, dim3(64), 0, st, src, src_off, src_len, W.d_ylen,
+                           W.d_mean, W.d_fft, W.d_H, m, W.d_z_off, W.d_z);
     } else if (small)
       hipLaunchKernelGGL(dio_lowcut_kernel<kZcStrideHarvest>, dim3(tiles, b.n_utt), dim3(256), lds, st, src, src_off,
-                         src_len, b.d_dio_ylen, b.d_dio_mean, b.d_dio_fft, b.d_dio_lowcut, m, b.d_dio_z_off,
-                         b.d_dio_z);
+                         src_len, W.d_ylen, W.d_mean, W.d_fft, W.d_lowcut, m, W.d_z_off,
+                         W.d_z);
     else
       hipLaunchKernelGGL(dio_lowcut_kernel<kZcStrideLong>, dim3(tiles, b.n_utt), dim3(256), lds, st, src, src_off,
-                         src_len, b.d_dio_ylen, b.d_dio_mean, b.d_dio_fft, b.d_dio_lowcut, m, b.d_dio_z_off,
-                         b.d_dio_z);
+                         src_len, W.d_ylen, W.d_mean, W.d_fft, W.d_lowcut, m, W.d_z_off,
+                         W.d_z);
   }
   {
     // row stride of the LDS tile by the longest filter: 16 kHz fits the small one, 48 kHz needs the large
@@ -744,55 +734,55 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
     const int tiles_max = dio_tiles(b.max_x_len / m.ratio + 1, m.step);
     TimedScope ts_(b.ctx, "dio_band_kernel");
     if (m.band_conv) {
-      const cpx* Hb = (const cpx*)b.d_dio_H + (m.lc_conv ? m.lc_conv / 2 + 1 : 0);
+      const cpx* Hb = W.d_H + (m.lc_conv ? m.lc_conv / 2 + 1 : 0);
       if (m.band_conv == 4096) {
         allow_dynamic_lds(*b.ctx, dio_band_fft_kernel<4096>, (int)(ConvEvCfg<4096, kDioConvC>::kLdsBytes));
         hipLaunchKernelGGL(dio_band_fft_kernel<4096>, dim3(tiles_max, b.n_utt), dim3(64), (ConvEvCfg<4096, kDioConvC>::kLdsBytes), st,
-                           b.d_dio_ylen, b.d_dio_z_off, b.d_dio_z, Hb, m, tiles_max, b.d_dio_tile_cnt, b.d_dio_slot_off,
-                           b.d_dio_slots);
+                           W.d_ylen, W.d_z_off, W.d_z, Hb, m, tiles_max, W.d_tile_cnt, W.d_slot_off,
+                           W.d_slots);
       } else {
         allow_dynamic_lds(*b.ctx, dio_band_fft_kernel<2048>, (int)(ConvEvCfg<2048, kDioConvC>::kLdsBytes));
         hipLaunchKernelGGL(dio_band_fft_kernel<2048>, dim3(tiles_max, b.n_utt), dim3(64), (ConvEvCfg<2048, kDioConvC>::kLdsBytes), st,
-                           b.d_dio_ylen, b.d_dio_z_off, b.d_dio_z, Hb, m, tiles_max, b.d_dio_tile_cnt, b.d_dio_slot_off,
-                           b.d_dio_slots);
+                           W.d_ylen, W.d_z_off, W.d_z, Hb, m, tiles_max, W.d_tile_cnt, W.d_slot_off,
+                           W.d_slots);
       }
     } else if (small)
       hipLaunchKernelGGL((dio_band_kernel<kZcStrideDio>), dim3(tiles_max, m.nb, b.n_utt), dim3(256), lds, st,
-                         b.d_dio_ylen, b.d_dio_z_off, b.d_dio_z, b.d_dio_win, m, tiles_max, b.d_dio_tile_cnt,
-                         b.d_dio_slot_off, b.d_dio_slots);
+                         W.d_ylen, W.d_z_off, W.d_z, W.d_win, m, tiles_max, W.d_tile_cnt,
+                         W.d_slot_off, W.d_slots);
     else
       hipLaunchKernelGGL((dio_band_kernel<kZcStrideHarvest>), dim3(tiles_max, m.nb, b.n_utt), dim3(256), lds, st,
-                         b.d_dio_ylen, b.d_dio_z_off, b.d_dio_z, b.d_dio_win, m, tiles_max, b.d_dio_tile_cnt,
-                         b.d_dio_slot_off, b.d_dio_slots);
-    hipLaunchKernelGGL(dio_band_scan_kernel, dim3(m.nb, b.n_utt), dim3(64), 0, st, b.d_dio_ylen, m, tiles_max,
-                       b.d_dio_tile_cnt, b.d_dio_ev_cnt);
-    hipLaunchKernelGGL(dio_band_compact_kernel, dim3(m.nb, b.n_utt), dim3(256), 0, st, b.d_dio_ylen, m,
-                       tiles_max, b.d_dio_tile_cnt, b.d_dio_slot_off, b.d_dio_slots, b.d_dio_ev_off,
-                       b.d_dio_events);
+                         W.d_ylen, W.d_z_off, W.d_z, W.d_win, m, tiles_max, W.d_tile_cnt,
+                         W.d_slot_off, W.d_slots);
+    hipLaunchKernelGGL(dio_band_scan_kernel, dim3(m.nb, b.n_utt), dim3(64), 0, st, W.d_ylen, m, tiles_max,
+                       W.d_tile_cnt, W.d_ev_cnt);
+    hipLaunchKernelGGL(dio_band_compact_kernel, dim3(m.nb, b.n_utt), dim3(256), 0, st, W.d_ylen, m,
+                       tiles_max, W.d_tile_cnt, W.d_slot_off, W.d_slots, W.d_ev_off,
+                       W.d_events);
   }
   {
     const int gx = (int)((b.total_f + 255) / 256);
     TimedScope ts_(b.ctx, "dio_candidate_kernel");
-    hipLaunchKernelGGL(dio_candidate_kernel, dim3(gx, m.nb), dim3(256), 0, st, b.d_dio_ylen, b.d_f_off,
-                       b.d_frame_utt, b.p.frame_period, m, b.p.f0_floor, b.p.f0_ceil, b.d_dio_ev_off, b.d_dio_events,
-                       b.d_dio_ev_cnt, b.total_f, b.d_dio_cand, b.d_dio_score);
+    hipLaunchKernelGGL(dio_candidate_kernel, dim3(gx, m.nb), dim3(256), 0, st, W.d_ylen, b.d_f_off,
+                       b.d_frame_utt, b.p.frame_period, m, b.p.f0_floor, b.p.f0_ceil, W.d_ev_off, W.d_events,
+                       W.d_ev_cnt, b.total_f, W.d_cand, W.d_score);
   }
   {
   TimedScope ts_(b.ctx, "dio_fix_kernel");
   const int edge_cap = b.max_f0_len / 2 + 2;
   const size_t lds = sizeof(int) * 2 * (size_t)edge_cap;
   if (lds <= 48 * 1024) {
-    hipLaunchKernelGGL(dio_fix_kernel<true>, dim3(b.n_utt), dim3(256), lds, st, b.d_f_off, b.d_dio_cand, b.d_dio_score,
-                       m.nb, b.p.frame_period, b.p.f0_floor, b.p.allowed_range, b.total_f, edge_cap, b.d_dio_ws,
+    hipLaunchKernelGGL(dio_fix_kernel<true>, dim3(b.n_utt), dim3(256), lds, st, b.d_f_off, W.d_cand, W.d_score,
+                       m.nb, b.p.frame_period, b.p.f0_floor, b.p.allowed_range, b.total_f, edge_cap, W.d_ws,
                        (int*)nullptr, d_t, d_f0);
   } else {
-    if (!b.d_dio_edges) {
-      rc = wm_check(dev_alloc(&b.d_dio_edges, sizeof(int) * 2 * (size_t)edge_cap * (size_t)b.n_utt));
+    if (!W.d_edges) {
+      rc = wm_check(W.alloc(&W.d_edges, sizeof(int) * 2 * (size_t)edge_cap * (size_t)b.n_utt));
       if (rc) return rc;
     }
-    hipLaunchKernelGGL(dio_fix_kernel<false>, dim3(b.n_utt), dim3(256), 0, st, b.d_f_off, b.d_dio_cand, b.d_dio_score,
-                       m.nb, b.p.frame_period, b.p.f0_floor, b.p.allowed_range, b.total_f, edge_cap, b.d_dio_ws,
-                       b.d_dio_edges, d_t, d_f0);
+    hipLaunchKernelGGL(dio_fix_kernel<false>, dim3(b.n_utt), dim3(256), 0, st, b.d_f_off, W.d_cand, W.d_score,
+                       m.nb, b.p.frame_period, b.p.f0_floor, b.p.allowed_range, b.total_f, edge_cap, W.d_ws,
+                       W.d_edges, d_t, d_f0);
   }
   }
   return wm_check(hipGetLastError());

@@ -53,7 +53,7 @@ __host__ __device__ inline int hv_tiles(int ylen, int step) { return (ylen + ste
 constexpr int kHvConvC = 28;        // samples per lane of a block's event passes
 constexpr int kHvChGroup = 19;      // channels per wavefront of the FFT filter bank (152 = 8 x 19)
 
-struct HarvestWs {
+struct HarvestWs : StageWs {                 // the batch's Harvest state (Batch::harvest)
   HvMeta m;
   std::vector<int> ylen, nb1;
   std::vector<int64_t> yoff, toff, evoff, boff, mdoff, smoff;
@@ -79,7 +79,6 @@ struct HarvestWs {
   int* d_sec = nullptr;                        // [3][tot_b/4 ...] section descriptors (lo, hi, off)
   double* d_sm = nullptr;                      // smoothing scratch
   cpx* d_twid = nullptr;                       // [kHvTwid] exp(-2 pi i k / kHvTwid), the refinement's twiddles
-  std::vector<void*> owned;
 };
 
 __global__ __launch_bounds__(256) void hv_copy_kernel(const double* __restrict__ x,
@@ -1335,13 +1334,10 @@ __global__ __launch_bounds__(kCtThreads) void hv_contour_kernel(
 }
 
 // ---- host side ------------------------------------------------------------------------------
-void harvest_free(void* p);
 
 static int hv_setup(Batch& b) {
-  if (b.harvest_ws) return WM_OK;
-  // the workspace is published on the batch only once every allocation and upload has succeeded: a half-built
-  // one would make the next call skip the set-up and launch with null device pointers
-  HarvestWs* W = new HarvestWs();
+  if (b.harvest) return WM_OK;
+  std::unique_ptr<HarvestWs> W(new HarvestWs());
   HvMeta& m = W->m;
   const WorldMi355Params& p = b.p;
   const double adj_floor = p.f0_floor * 0.9, adj_ceil = p.f0_ceil * 1.1;
@@ -1351,7 +1347,7 @@ static int hv_setup(Batch& b) {
   m.lag = m.r == 1 ? 0 : (int)(ceil(140.0 / m.r) * m.r);
   m.cpf = matlab_round(m.nch / 10.0);
   m.maxc = m.cpf * kHvOverlap;
-  if (m.maxc > 64 * kSelPer) { delete W; return WM_ERR_UNSUPPORTED; }   // hv_select_wave: candidates over lanes
+  if (m.maxc > 64 * kSelPer) return WM_ERR_UNSUPPORTED;   // hv_select_wave: candidates over lanes
   std::vector<double> bf((size_t)m.nch), taps;
   std::vector<int> half((size_t)m.nch), tapoff((size_t)m.nch);
   m.ntap_max = 0;
@@ -1397,14 +1393,12 @@ static int hv_setup(Batch& b) {
   int rc = WM_OK;
   auto up = [&](void** dst, const void* src, size_t bytes) {
     if (rc) return;
-    rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
-    if (!rc) W->owned.push_back(*dst);
+    rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
     if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
   };
   auto al = [&](void** dst, size_t bytes) {
     if (rc) return;
-    rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
-    if (!rc) W->owned.push_back(*dst);
+    rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
   };
   up((void**)&W->d_ylen, W->ylen.data(), sizeof(int) * (size_t)n_utt);
   up((void**)&W->d_nb1, W->nb1.data(), sizeof(int) * (size_t)n_utt);
@@ -1482,26 +1476,16 @@ static int hv_setup(Batch& b) {
       if (!rc) rc = wm_check(hipStreamSynchronize(b.ctx->stream));
     }
   }
-  if (rc) {
-    harvest_free(W);
-    return rc;
-  }
-  b.harvest_ws = W;
+  if (rc) return rc;
+  b.harvest = std::move(W);
   return WM_OK;
-}
-
-void harvest_free(void* p) {
-  HarvestWs* W = (HarvestWs*)p;
-  if (!W) return;
-  for (void* q : W->owned) dev_free(q);
-  delete W;
 }
 
 int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   if (b.total_x <= 0) return WM_ERR_BAD_ARG;
   int rc = hv_setup(b);
   if (rc) return rc;
-  HarvestWs& W = *(HarvestWs*)b.harvest_ws;
+  HarvestWs& W = static_cast<HarvestWs&>(*b.harvest);
   const HvMeta& m = W.m;
   Context& c = *b.ctx;
   hipStream_t st = c.stream;

@@ -253,21 +253,22 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
   const int fs = b.p.fs;
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
-  if (!c.d_sm_twid) {                       // once per context (the table depends on nothing)
-    int rc = wm_check(dev_alloc(&c.d_sm_twid, sizeof(cpx) * (size_t)kSmTwid));
-    if (rc) return rc;
-    hipLaunchKernelGGL(sm_twiddle_kernel, dim3(kSmTwid / 256), dim3(256), 0, c.stream, (cpx*)c.d_sm_twid);
-    rc = wm_check(hipStreamSynchronize(c.stream));          // later calls may come on other streams
-    if (rc) return rc;
-  }
-  b.d_sm_twid = c.d_sm_twid;
+  const Table* twid = nullptr;              // once per context (the table depends on nothing)
+  int rc = c.table({kSmTwiddles, {}}, twid, [&](Table& t) {
+    int r = wm_check(t.alloc(&t.d[0], sizeof(cpx) * (size_t)kSmTwid));
+    if (r) return r;
+    hipLaunchKernelGGL(sm_twiddle_kernel, dim3(kSmTwid / 256), dim3(256), 0, c.stream, (cpx*)t.d[0]);
+    r = wm_check(hipGetLastError());
+    return r ? r : wm_check(hipStreamSynchronize(c.stream));   // later calls may come on other streams
+  });
+  if (rc) return rc;
   // The output is cleared before the list is made from d_f0: the two must not be the same array (the reference's
   // StoneMask takes them as separate arrays too, stonemask.h:27-29); refused rather than answered with zeros.
   if (d_out == d_f0) {
     set_error("StoneMask: refined_f0 must not alias f0");
     return WM_ERR_BAD_ARG;
   }
-  int rc = wm_check(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)tf, c.stream));    // stonemask.cpp:186-187
+  rc = wm_check(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)tf, c.stream));    // stonemask.cpp:186-187
   if (rc) return rc;
   TimedScope ts_(b.ctx, "stonemask_kernel");
   launch_partition(c.stream, StoneMaskPred{d_f0, fs / 12.0}, (int)tf, b.d_part_cnt, b.d_perm, b.d_part_n);
@@ -275,7 +276,7 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
   const int64_t cap = (int64_t)c.num_cu * 64;
   hipLaunchKernelGGL(stonemask_kernel, dim3((unsigned)(chunks < cap ? chunks : cap)), dim3(256), 0, c.stream, d_x, b.d_x_off,
                      b.d_x_len, b.d_frame_utt, d_t, d_f0, fs, (const int*)b.d_perm, (const int*)b.d_part_n,
-                     (const cpx*)b.d_sm_twid, d_out);
+                     (const cpx*)twid->d[0], d_out);
   return wm_check(hipGetLastError());
 }
 

@@ -941,7 +941,7 @@ __global__ __launch_bounds__(64 * kOlaWaves) void synth_ola_kernel(const int* __
 // base, the pulse list and its per-pulse records; it ends with the one host round trip of the path (the pulse count
 // sizes the response scratch).  The RENDER stage turns sp / ap into responses and overlap-adds them.
 //
-// Both work on a PART of the batch: a list of utterances (Batch::d_syn_order holds the batch's utterances sorted by
+// Both work on a PART of the batch: a list of utterances (SynWs::d_order holds the batch's utterances sorted by
 // output length; the identity order when the batch is prepared as one part).  launch_analyze_synthesize()
 // (context.cpp) prepares the whole batch as one part on a side stream while CheapTrick and D4C occupy the main one.
 // launch_synthesis() -- Synthesis alone, BASELINE.json configs[4] -- has nothing to hide the prepare stage behind
@@ -958,10 +958,36 @@ struct SynPart {
   int max_np = 0;
 };
 
+// The batch's Synthesis state (Batch::syn): the work arrays are sections of one allocation, laid out by
+// synthesis_arena(); the pulse records and their order grow on demand (synthesis_prepare_finish).
+struct SynWs : StageWs {
+  int* d_pulse_idx = nullptr;        // [total_y]
+  double* d_pulse_shift = nullptr;   // [total_y]
+  double* d_vuv = nullptr;           // [total_y] interpolated vuv
+  double* d_phase = nullptr;         // [total_y] scratch (increments / wrapped phase)
+  int* d_pulse_cnt = nullptr;        // [n_utt]
+  int* d_pulse_tile_cnt = nullptr;   // [n_utt][tiles] pulses per search tile
+  int64_t* d_pulse_off = nullptr;    // [n_utt+1]
+  int* d_pulse_first = nullptr;      // first pulse at or after every 128th sample of an utterance (the overlap-add's table)
+  int* d_order = nullptr;            // [2 n_utt] the identity, then the utterances by output length (shortest first)
+  std::vector<int> sorted;           // host copy of the second half
+  std::vector<int> order_host;       // what d_order was uploaded from: kept alive, so the upload needs no wait
+  const double* d_dc_remover = nullptr;   // [fft_size] (the context's)
+  PulseRec* d_pulse_rec = nullptr;   // [pulse_rec_cap]
+  int64_t pulse_rec_cap = 0;
+  int* d_pulse_perm = nullptr;       // [cap] voiced-first pulse order of a chunk, then n, then block counts
+  int64_t total_p = 0, chunk = 0;    // pulses of the prepared synthesis, pulses per piece (half of the response scratch)
+  ~SynWs() override {
+    dev_free(d_pulse_rec);
+    dev_free(d_pulse_perm);
+  }
+};
+static SynWs& syn_ws(Batch& b) { return static_cast<SynWs&>(*b.syn); }
+
 static int synthesis_arena(Batch& b) {
   Context& c = *b.ctx;
   const int F = b.p.fft_size;
-  if (b.d_pulse_idx) return WM_OK;
+  if (b.syn) return WM_OK;
   // one allocation for the work arrays of this batch (sections aligned to 256 bytes)
   const size_t ny = (size_t)b.total_y, nu = (size_t)b.n_utt;
   const size_t tiles = (size_t)((b.max_y_len + kSearchTile - 1) / kSearchTile + 1);
@@ -972,47 +998,47 @@ static int synthesis_arena(Batch& b) {
   const size_t o_first = take(4 * (ny / kOlaStep + 2 * nu + 4));
   const size_t o_order = take(4 * 2 * nu);
   // the DC remover (GetDCRemover, synthesis.cpp:322-334) depends on fft_size only: once per context
-  double* dcr = nullptr;
-  for (const auto& e : c.dc_removers)
-    if (e.first == F) dcr = e.second;
-  if (!dcr) {
-    int rc0 = wm_check(dev_alloc(&dcr, sizeof(double) * (size_t)F));
-    if (rc0) return rc0;
-    hipLaunchKernelGGL(synth_dc_remover_kernel, dim3(1), dim3(64), 0, c.stream, F, dcr);
-    rc0 = wm_check(hipStreamSynchronize(c.stream));                // later calls may come on other streams
-    if (rc0) { dev_free(dcr); return rc0; }
-    c.dc_removers.push_back(std::make_pair(F, dcr));
-  }
+  const Table* dcr = nullptr;
+  int rc = c.table({kDcRemover, {(double)F}}, dcr, [&](Table& t) {
+    int r = wm_check(t.alloc(&t.d[0], sizeof(double) * (size_t)F));
+    if (r) return r;
+    hipLaunchKernelGGL(synth_dc_remover_kernel, dim3(1), dim3(64), 0, c.stream, F, (double*)t.d[0]);
+    return wm_check(hipStreamSynchronize(c.stream));              // later calls may come on other streams
+  });
+  if (rc) return rc;
+  std::unique_ptr<SynWs> W(new SynWs());
   unsigned char* base = nullptr;
-  int rc = wm_check(dev_alloc(&base, at));
+  rc = wm_check(W->alloc(&base, at));
   if (rc) return rc;
   if (!c.h_pulse_info) {            // per context: two pinned, device-visible integers
     rc = wm_check(hipHostMalloc((void**)&c.h_pulse_info, sizeof(int64_t) * 2, hipHostMallocMapped));
     if (!rc) rc = wm_check(hipHostGetDevicePointer((void**)&c.d_pulse_info, c.h_pulse_info, 0));
-    if (rc) { dev_free(base); return rc; }
+    if (rc) return rc;
   }
-  b.d_syn_arena = base;
-  b.d_pulse_idx = (int*)(base + o_idx); b.d_pulse_shift = (double*)(base + o_shift);
-  b.d_vuv = (double*)(base + o_vuv); b.d_phase = (double*)(base + o_phase);
-  b.d_pulse_cnt = (int*)(base + o_cnt); b.d_pulse_tile_cnt = (int*)(base + o_tile);
-  b.d_pulse_off = (int64_t*)(base + o_off); b.d_dc_remover = dcr;
-  b.d_pulse_first = (int*)(base + o_first);
-  b.d_syn_order = (int*)(base + o_order);
+  W->d_pulse_idx = (int*)(base + o_idx); W->d_pulse_shift = (double*)(base + o_shift);
+  W->d_vuv = (double*)(base + o_vuv); W->d_phase = (double*)(base + o_phase);
+  W->d_pulse_cnt = (int*)(base + o_cnt); W->d_pulse_tile_cnt = (int*)(base + o_tile);
+  W->d_pulse_off = (int64_t*)(base + o_off); W->d_dc_remover = (const double*)dcr->d[0];
+  W->d_pulse_first = (int*)(base + o_first);
+  W->d_order = (int*)(base + o_order);
   // [0, n): the identity; [n, 2 n): the utterances by output length, shortest first (stable)
-  std::vector<int>& order = b.syn_order_host;                    // the batch's: alive until the copy has been made
+  std::vector<int>& order = W->order_host;                       // the batch's: alive until the copy has been made
   order.resize(2 * nu);
   for (size_t u = 0; u < nu; ++u) order[u] = order[nu + u] = (int)u;
   std::stable_sort(order.begin() + (long)nu, order.end(), [&](int x, int y) { return b.y_len[(size_t)x] < b.y_len[(size_t)y]; });
-  b.syn_sorted.assign(order.begin() + (long)nu, order.end());
+  W->sorted.assign(order.begin() + (long)nu, order.end());
   // (a copy from pageable memory returns once the source has been read or staged: no wait here -- it was 20 us of
   // every Synthesis() of a new utterance length)
-  rc = wm_check(hipMemcpyAsync(b.d_syn_order, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, c.stream));
-  return rc;
+  rc = wm_check(hipMemcpyAsync(W->d_order, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, c.stream));
+  if (rc) return rc;
+  b.syn = std::move(W);
+  return WM_OK;
 }
 
 // The f0-only kernels of a part, up to its pulse numbers: asynchronous on the context's stream.
 static int synthesis_prepare_launch(Batch& b, const SynPart& part, const double* d_f0) {
   Context& c = *b.ctx;
+  SynWs& W = syn_ws(b);
   hipStream_t st = c.stream;
   const int F = b.p.fft_size, fs = b.p.fs;
   const double fp = b.p.frame_period / 1000.0;
@@ -1022,29 +1048,29 @@ static int synthesis_prepare_launch(Batch& b, const SynPart& part, const double*
     {
       TimedScope ts_(b.ctx, "synth_inc_kernel");
       hipLaunchKernelGGL(synth_inc_kernel, dim3(tiles, part.n), dim3(256), 0, st, part.d_list, d_f0, b.d_f_off,
-                         b.d_y_off, fs, fp, lowest_f0, b.d_vuv, b.d_phase);
+                         b.d_y_off, fs, fp, lowest_f0, W.d_vuv, W.d_phase);
     }
     TimedScope ts_(b.ctx, "synth_timebase_kernel");
-    hipLaunchKernelGGL(synth_timebase_kernel, dim3(part.n), dim3(64), 0, st, part.d_list, b.d_y_off, b.d_phase);
+    hipLaunchKernelGGL(synth_timebase_kernel, dim3(part.n), dim3(64), 0, st, part.d_list, b.d_y_off, W.d_phase);
   }
   {
     TimedScope ts_(b.ctx, "synth_search_kernel");
     const int tiles_max = (b.max_y_len + kSearchTile - 1) / kSearchTile + 1;        // the row length of the tile counts
     const int tiles_part = (part.max_y_len + kSearchTile - 1) / kSearchTile + 1;
     hipLaunchKernelGGL(synth_pulse_search_kernel<false>, dim3(tiles_part, part.n), dim3(256), 0, st, part.d_list,
-                       b.d_y_off, b.d_phase, fs, tiles_max, b.d_pulse_tile_cnt, b.d_pulse_idx, b.d_pulse_shift,
-                       b.d_pulse_cnt);
+                       b.d_y_off, W.d_phase, fs, tiles_max, W.d_pulse_tile_cnt, W.d_pulse_idx, W.d_pulse_shift,
+                       W.d_pulse_cnt);
     hipLaunchKernelGGL(synth_pulse_search_kernel<true>, dim3(tiles_part, part.n), dim3(256), 0, st, part.d_list,
-                       b.d_y_off, b.d_phase, fs, tiles_max, b.d_pulse_tile_cnt, b.d_pulse_idx, b.d_pulse_shift,
-                       b.d_pulse_cnt);
+                       b.d_y_off, W.d_phase, fs, tiles_max, W.d_pulse_tile_cnt, W.d_pulse_idx, W.d_pulse_shift,
+                       W.d_pulse_cnt);
   }
   // Pulse numbers stay on the device; the host needs two numbers only -- the part's total, which sizes the response
   // scratch, and the largest count, which sizes a grid -- and reads them from pinned memory the kernel writes
   // directly.  No hipMemcpy in either direction: a small copy queues on the same DMA engine as whatever bulk
   // transfer another stream has in flight (a 1 GB feature download held this synchronisation, and with it the
   // whole step, for 20 ms).
-  hipLaunchKernelGGL(synth_pulse_off_kernel, dim3(1), dim3(256), 0, st, part.d_list, (const int*)b.d_pulse_cnt, part.n,
-                     part.p_base, b.d_pulse_off, c.d_pulse_info);
+  hipLaunchKernelGGL(synth_pulse_off_kernel, dim3(1), dim3(256), 0, st, part.d_list, (const int*)W.d_pulse_cnt, part.n,
+                     part.p_base, W.d_pulse_off, c.d_pulse_info);
   return wm_check(hipGetLastError());
 }
 
@@ -1052,6 +1078,7 @@ static int synthesis_prepare_launch(Batch& b, const SynPart& part, const double*
 // pulse records and the response scratch, which therefore must not move.
 static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more, bool in_flight) {
   Context& c = *b.ctx;
+  SynWs& W = syn_ws(b);
   hipStream_t st = c.stream;
   const int F = b.p.fft_size;
   part.total_p = c.h_pulse_info[0];
@@ -1076,47 +1103,47 @@ static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more
   if (rc) return rc;
   if (in_flight) {
     // what is there stays: this part is cut into pieces of the size the scratch was laid out for
-    chunk = b.syn_chunk > 0 ? b.syn_chunk : chunk;
+    chunk = W.chunk > 0 ? W.chunk : chunk;
   } else {
     // one half only when this part is the whole call AND fits one piece: a later part (expect_more > 0) starts at
     // whatever piece parity the earlier one ended on, so the split path always lays out both halves
     rc = c.ensure_scratch((chunk < list || expect_more > 0 ? 2 : 1) * chunk * F);
     if (rc) return rc;
-    b.syn_chunk = chunk;
+    W.chunk = chunk;
   }
   const int64_t need = part.p_base + part.total_p + (in_flight ? 0 : expect_more);
-  if (need > b.pulse_rec_cap) {
+  if (need > W.pulse_rec_cap) {
     if (in_flight) {
       // the earlier part's kernels read the records: let them finish (they no longer need theirs afterwards)
       rc = wm_check(hipDeviceSynchronize());
       if (rc) return rc;
     }
-    if (b.d_pulse_rec) dev_free(b.d_pulse_rec);
-    b.d_pulse_rec = nullptr;
-    b.pulse_rec_cap = 0;
-    if (b.d_pulse_perm) dev_free(b.d_pulse_perm);
-    b.d_pulse_perm = nullptr;
+    if (W.d_pulse_rec) dev_free(W.d_pulse_rec);
+    W.d_pulse_rec = nullptr;
+    W.pulse_rec_cap = 0;
+    if (W.d_pulse_perm) dev_free(W.d_pulse_perm);
+    W.d_pulse_perm = nullptr;
     const int64_t cap = need + need / 8 + 64;
-    rc = wm_check(dev_alloc(&b.d_pulse_rec, sizeof(PulseRec) * (size_t)cap));
+    rc = wm_check(dev_alloc(&W.d_pulse_rec, sizeof(PulseRec) * (size_t)cap));
     if (rc) return rc;
     // perm[cap], then two sets of partition scratch (n_true + block counts), one per part of a split call
-    rc = wm_check(dev_alloc(&b.d_pulse_perm, sizeof(int) * (size_t)(cap + 2 * (cap / kPartBlock + 8))));
+    rc = wm_check(dev_alloc(&W.d_pulse_perm, sizeof(int) * (size_t)(cap + 2 * (cap / kPartBlock + 8))));
     if (rc) return rc;
-    b.pulse_rec_cap = cap;
+    W.pulse_rec_cap = cap;
   }
   hipLaunchKernelGGL(synth_pulse_rec_kernel, dim3(imin(64, (part.max_np + 255) / 256), part.n), dim3(256), 0, st,
-                     part.d_list, b.d_f_off, b.d_y_off, b.d_pulse_off, (const int*)b.d_pulse_cnt, b.d_pulse_idx,
-                     b.d_pulse_shift, b.d_vuv, (PulseRec*)b.d_pulse_rec, b.d_pulse_first);
+                     part.d_list, b.d_f_off, b.d_y_off, W.d_pulse_off, (const int*)W.d_pulse_cnt, W.d_pulse_idx,
+                     W.d_pulse_shift, W.d_vuv, W.d_pulse_rec, W.d_pulse_first);
   // The voiced-first order of every piece of the list, here rather than in front of each pulse kernel: two short
   // dependent launches per piece that sat between D4C and the first pulse kernel and between the pieces.  A piece's
   // order lives at its own place of the array (perm + p0); the block counts are scratch of one launch pair.
   // The second part of a split call partitions on another stream than the first: its count scratch is its own.
-  const int64_t piece = b.syn_chunk, p_end = part.p_base + part.total_p;
-  int* part_scratch = b.d_pulse_perm + b.pulse_rec_cap + (in_flight ? b.pulse_rec_cap / kPartBlock + 8 : 0);
+  const int64_t piece = W.chunk, p_end = part.p_base + part.total_p;
+  int* part_scratch = W.d_pulse_perm + W.pulse_rec_cap + (in_flight ? W.pulse_rec_cap / kPartBlock + 8 : 0);
   for (int64_t p0 = part.p_base; p0 < p_end; p0 += piece) {
     const int64_t np = p_end - p0 < piece ? p_end - p0 : piece;
-    launch_partition(st, PulseVoicedPred{(const PulseRec*)b.d_pulse_rec + p0}, (int)np, part_scratch + 4,
-                     b.d_pulse_perm + p0, part_scratch);
+    launch_partition(st, PulseVoicedPred{W.d_pulse_rec + p0}, (int)np, part_scratch + 4,
+                     W.d_pulse_perm + p0, part_scratch);
   }
   return wm_check(hipGetLastError());
 }
@@ -1127,10 +1154,11 @@ static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more
 static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_sp, const double* d_ap, double* d_y,
                                  int& piece) {
   Context& c = *b.ctx;
+  SynWs& W = syn_ws(b);
   hipStream_t st = c.stream;
   const int F = b.p.fft_size, fs = b.p.fs;
   const double fp = b.p.frame_period / 1000.0;
-  const int64_t chunk = b.syn_chunk;
+  const int64_t chunk = W.chunk;
   const int ola_tiles = (part.max_y_len + kOlaSeg * kOlaWaves - 1) / (kOlaSeg * kOlaWaves);
   // Piece k: pulse kernel on the caller's stream into half k & 1 of the scratch, overlap-add on the second stream.
   // The overlap-adds run in list order on one stream, so every sample is summed in the order of one piece per launch
@@ -1149,8 +1177,8 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
   case FF: {                                                                                                    \
     const int per_ = persistent_grid(c, KERNEL<FF>, 64, (int64_t)1 << 40);                               \
     hipLaunchKernelGGL(KERNEL<FF>, dim3(imin(grid, per_)), dim3(64), 0, st, d_sp, d_ap,                         \
-                       (const PulseRec*)b.d_pulse_rec, b.d_dc_remover, c.d_rng, fs, fp, p0, p1,                 \
-                       (const int*)b.d_pulse_perm + p0, resp);                                                  \
+                       W.d_pulse_rec, W.d_dc_remover, c.d_rng, fs, fp, p0, p1,                 \
+                       (const int*)W.d_pulse_perm + p0, resp);                                                  \
   } break;
     {
       TimedScope ts_(b.ctx, "synth_pulse_kernel");
@@ -1171,7 +1199,7 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
       c.stream = so;                                       // the timing bracket records on the context's stream
       TimedScope ts2_(b.ctx, "synth_ola_kernel");
       hipLaunchKernelGGL(synth_ola_kernel, dim3(ola_tiles, part.n), dim3(64 * kOlaWaves), 0, so, part.d_list, b.d_y_off,
-                         b.d_pulse_off, (const int*)b.d_pulse_cnt, b.d_pulse_idx, (const int*)b.d_pulse_first, F, p0,
+                         W.d_pulse_off, (const int*)W.d_pulse_cnt, W.d_pulse_idx, (const int*)W.d_pulse_first, F, p0,
                          p1, resp, d_y);
     }
     c.stream = st;
@@ -1201,16 +1229,17 @@ int synthesis_begin(Batch& b, const double* d_f0, double* d_y) {
   rc = rc ? rc : synthesis_arena(b);
   rc = rc ? rc : wm_check(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)b.total_y, c.stream));
   if (rc) return rc;
-  SynPart part{b.d_syn_order, b.n_utt, b.max_y_len, 0};
+  SynPart part{syn_ws(b).d_order, b.n_utt, b.max_y_len, 0};
   return synthesis_prepare_launch(b, part, d_f0);
 }
 int synthesis_prepare_wait(Batch& b) {
   Context& c = *b.ctx;
-  SynPart part{b.d_syn_order, b.n_utt, b.max_y_len, 0};
+  SynWs& W = syn_ws(b);
+  SynPart part{W.d_order, b.n_utt, b.max_y_len, 0};
   int rc = wm_check(hipStreamSynchronize(c.stream));            // the one host round trip of the path
-  b.syn_chunk = 0;
+  W.chunk = 0;
   rc = rc ? rc : synthesis_prepare_finish(b, part, 0, false);
-  b.syn_total_p = part.total_p;
+  W.total_p = part.total_p;
   return rc;
 }
 int synthesis_prepare(Batch& b, const double* d_f0, double* d_y) {
@@ -1219,9 +1248,10 @@ int synthesis_prepare(Batch& b, const double* d_f0, double* d_y) {
 }
 
 int synthesis_render(Batch& b, const double* d_sp, const double* d_ap, double* d_y) {
-  if (b.syn_total_p == 0) return WM_OK;
-  SynPart part{b.d_syn_order, b.n_utt, b.max_y_len, 0};
-  part.total_p = b.syn_total_p;
+  const SynWs& W = syn_ws(b);
+  if (W.total_p == 0) return WM_OK;
+  SynPart part{W.d_order, b.n_utt, b.max_y_len, 0};
+  part.total_p = W.total_p;
   int piece = 0;
   int rc = synthesis_render_part(b, part, d_sp, d_ap, d_y, piece);
   return rc ? rc : synthesis_join(b, piece);
@@ -1250,20 +1280,21 @@ int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const dou
     rc = rc ? rc : wm_check(hipEventCreateWithFlags(&c.ev_prep_b, hipEventDisableTiming));
   }
   if (rc) return rc;
+  SynWs& W = syn_ws(b);
   hipStream_t st = c.stream;
   // part A: the shortest utterances up to a third of the output samples (profiles/r04_syn_split_sweep.txt)
   int n_a = 0;
   int64_t acc = 0;
-  while (n_a < b.n_utt - 1 && acc < b.total_y / 3) acc += b.y_len[(size_t)b.syn_sorted[(size_t)n_a++]];
-  const int* sorted = b.d_syn_order + b.n_utt;
-  SynPart pa{sorted, n_a, b.y_len[(size_t)b.syn_sorted[(size_t)n_a - 1]], 0};
+  while (n_a < b.n_utt - 1 && acc < b.total_y / 3) acc += b.y_len[(size_t)W.sorted[(size_t)n_a++]];
+  const int* sorted = W.d_order + b.n_utt;
+  SynPart pa{sorted, n_a, b.y_len[(size_t)W.sorted[(size_t)n_a - 1]], 0};
   SynPart pb{sorted + n_a, b.n_utt - n_a, b.max_y_len, 0};
   rc = wm_check(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)b.total_y, st));
   rc = rc ? rc : wm_check(hipEventRecord(c.ev_call, st));          // the caller's f0 is ready from here on
   rc = rc ? rc : synthesis_prepare_launch(b, pa, d_f0);
   rc = rc ? rc : wm_check(hipStreamSynchronize(st));               // host round trip of part A
   if (rc) return rc;
-  b.syn_chunk = 0;
+  W.chunk = 0;
   const int64_t guess_b = (int64_t)((double)c.h_pulse_info[0] * (double)(b.total_y - acc) / (double)(acc > 0 ? acc : 1) * 1.25) + 1024;
   rc = synthesis_prepare_finish(b, pa, guess_b, false);
   if (rc) return rc;
@@ -1283,7 +1314,7 @@ int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const dou
   c.stream = st;
   rc = rc ? rc : wm_check(hipStreamWaitEvent(st, c.ev_prep_b, 0));
   if (!rc && pb.total_p > 0) rc = synthesis_render_part(b, pb, d_sp, d_ap, d_y, piece);
-  b.syn_total_p = pa.total_p + pb.total_p;
+  W.total_p = pa.total_p + pb.total_p;
   return rc ? rc : synthesis_join(b, piece);
 }
 

@@ -256,8 +256,7 @@ __global__ __launch_bounds__(64) void vib_resolve_kernel(const int64_t* __restri
   }
 }
 
-struct VibWs {
-  std::vector<void*> owned;
+struct VibWs : StageWs {           // the batch's Vibrato state (Batch::vibrato)
   int64_t* d_slot_off = nullptr;
   int* d_slot_utt = nullptr;
   VibRun* d_runs = nullptr;
@@ -267,20 +266,13 @@ struct VibWs {
   int64_t total_slots = 0;
 };
 
-void vibrato_free(void* p) {
-  VibWs* W = (VibWs*)p;
-  if (!W) return;
-  for (void* q : W->owned) dev_free(q);
-  delete W;
-}
-
 int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const int* seg_start, const int* seg_end,
                    const double* seg_pitch, float* d_vib, float* d_lf0_out, int* n_too_long) {
   if (!d_lf0 || !seg_utt_off || !d_vib || !d_lf0_out) return WM_ERR_BAD_ARG;
   hipStream_t st = b.ctx->stream;
   int rc = WM_OK;
-  if (!b.vibrato_ws) {
-    VibWs* W = new VibWs();
+  if (!b.vibrato) {
+    std::unique_ptr<VibWs> W(new VibWs());
     std::vector<int64_t> soff((size_t)b.n_utt + 1, 0);
     for (int u = 0; u < b.n_utt; ++u) soff[(size_t)u + 1] = soff[(size_t)u] + b.f0_len[(size_t)u] / 21 + 1;
     W->total_slots = soff[(size_t)b.n_utt];
@@ -289,8 +281,7 @@ int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const i
       for (int64_t s = soff[(size_t)u]; s < soff[(size_t)u + 1]; ++s) sutt[(size_t)s] = u;
     auto al = [&](void** dst, size_t bytes) {
       if (rc) return;
-      rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
-      if (!rc) W->owned.push_back(*dst);
+      rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
     };
     const size_t tf = (size_t)b.total_f;
     al((void**)&W->d_slot_off, sizeof(int64_t) * soff.size());
@@ -307,17 +298,18 @@ int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const i
     if (!rc) rc = wm_check(hipMemcpy(W->d_slot_utt, sutt.data(), sizeof(int) * sutt.size(), hipMemcpyHostToDevice));
     if (!rc) rc = wm_check(hipFuncSetAttribute((const void*)vib_lowess_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)(sizeof(double) * (3 * kVibMaxRun + kVibSortMax))));
-    if (rc) { vibrato_free(W); return rc; }
-    b.vibrato_ws = W;
+    if (rc) return rc;
+    b.vibrato = std::move(W);
   }
-  VibWs& W = *(VibWs*)b.vibrato_ws;
-  // the label segments of this call (host arrays: they come from text files)
+  VibWs& W = static_cast<VibWs&>(*b.vibrato);
+  // the label segments of this call (host arrays: they come from text files), freed on return
   const int nseg = seg_utt_off[b.n_utt];
+  StageWs seg;
   int *d_soff = nullptr, *d_ss = nullptr, *d_se = nullptr;
   double* d_sp = nullptr;
   auto up = [&](void** dst, const void* src, size_t bytes) {
     if (rc) return;
-    rc = wm_check(dev_alloc(dst, bytes ? bytes : 8));
+    rc = wm_check(seg.alloc(dst, bytes ? bytes : 8));
     if (!rc && bytes) rc = wm_check(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
   };
   up((void**)&d_soff, seg_utt_off, sizeof(int) * ((size_t)b.n_utt + 1));
@@ -340,8 +332,6 @@ int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const i
   int too_long = 0;
   if (!rc) rc = wm_check(hipMemcpyAsync(&too_long, W.d_too_long, sizeof(int), hipMemcpyDeviceToHost, st));
   if (!rc) rc = wm_check(hipStreamSynchronize(st));       // the segment arrays are call-local
-  for (void* p : {(void*)d_soff, (void*)d_ss, (void*)d_se, (void*)d_sp})
-    if (p) dev_free(p);
   if (n_too_long) *n_too_long = too_long;
   return rc;
 }

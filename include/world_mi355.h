@@ -76,6 +76,7 @@ void WorldMi355SetErrorHandler(WorldMi355ErrorHandler handler, void* user);
 
 /* device < 0: current device.  stream == NULL: the legacy default stream (stream 0). */
 int WorldMi355CreateContext(int device, void* hip_stream, WorldMi355Context** out);
+/* Every batch of a context must be destroyed before the context: a batch uses the context's stream and tables. */
 void WorldMi355DestroyContext(WorldMi355Context* ctx);
 int WorldMi355SetStream(WorldMi355Context* ctx, void* hip_stream);
 int WorldMi355Synchronize(WorldMi355Context* ctx);
