@@ -1,6 +1,6 @@
 // batch.hpp -- host-side state shared by the kernel launchers and the C ABI.
 //
-// Context : one per (process, device): HIP stream, the universal randn table
+// Context : one per (process, device): the caller's HIP stream, the universal randn table
 //           (matlabfunctions.cpp:247-277 as data), launch geometry.
 // Batch   : one per set of utterances: lengths/offsets on host and device, the
 //           frame->utterance map and the per-frame arrays several stages share,
@@ -32,20 +32,23 @@ void dev_free(void* p);
 void dev_cache_trim(size_t keep_bytes);       // hipFree cached blocks until at most keep_bytes stay cached
 template <class T> inline hipError_t dev_alloc(T** p, size_t bytes) { return dev_alloc_bytes((void**)p, bytes); }
 
+struct NoCopy {                               // base of what frees or restores something in its destructor
+  NoCopy() = default;
+  NoCopy(const NoCopy&) = delete;
+  NoCopy& operator=(const NoCopy&) = delete;
+};
+
 // Device blocks freed together with their owner: alloc() records what it hands out.  Every stage keeps the state it
 // builds on first use in one such struct, private to its .hip file and owned by the batch (Batch::dio ... vibrato);
 // a set-up builds it in a local and moves it into the batch only once every allocation, copy, launch and
 // synchronisation has succeeded, so a failure leaves nothing half-built behind.
-struct StageWs {
+struct StageWs : NoCopy {
   std::vector<void*> owned;
   template <class T> hipError_t alloc(T** p, size_t bytes) {
     const hipError_t e = dev_alloc(p, bytes);
     if (e == hipSuccess) owned.push_back(*p);
     return e;
   }
-  StageWs() = default;
-  StageWs(const StageWs&) = delete;
-  StageWs& operator=(const StageWs&) = delete;
   virtual ~StageWs() {
     for (void* p : owned) dev_free(p);
   }
@@ -67,10 +70,46 @@ struct Table : StageWs {
   void* d[3] = {nullptr, nullptr, nullptr};
 };
 
+// Streams and events that are created together and destroyed with their owner, in StageWs' idiom: a set-up creates them
+// in a local and moves that into the context only when every creation has succeeded, so nothing half-made is ever seen.
+struct Handles : NoCopy {
+  std::vector<hipStream_t> streams;
+  std::vector<hipEvent_t> events;
+  hipError_t stream(hipStream_t* s) { return keep(hipStreamCreateWithFlags(s, hipStreamNonBlocking), streams, *s); }
+  hipError_t stream(hipStream_t* s, int prio) { return keep(hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio), streams, *s); }
+  hipError_t event(hipEvent_t* e) { return keep(hipEventCreateWithFlags(e, hipEventDisableTiming), events, *e); }
+  ~Handles() {
+    for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  }
+ private:
+  template <class T> static hipError_t keep(hipError_t e, std::vector<T>& v, T made) {
+    if (e == hipSuccess) v.push_back(made);
+    return e;
+  }
+};
+// the one-call forms and Synthesis' render stage (Context::ensure_side)
+struct SideStreams : Handles {
+  hipStream_t side = nullptr;        // D4C's and Synthesis' preparation beside CheapTrick; the overlap-adds
+  hipStream_t aux = nullptr;         // D4C's RARE launch (d4c_rare)
+  hipEvent_t ev_f0 = nullptr, ev_prep = nullptr, ev_d4c = nullptr, ev_rare = nullptr;
+  hipEvent_t ev_pulse[2] = {nullptr, nullptr}, ev_ola[2] = {nullptr, nullptr};   // synthesis_render's two response halves
+};
+// the split form of launch_synthesis, made when it first runs
+struct SplitStreams : Handles {
+  hipStream_t prep = nullptr;        // the f0-only kernels of the batch's second part
+  hipEvent_t ev_call = nullptr, ev_prep_b = nullptr;
+};
+// {total pulses, largest per-utterance count} of the last Synthesis: two pinned, mapped integers the device writes
+struct PulseInfo : NoCopy {
+  int64_t* h = nullptr;
+  int64_t* d = nullptr;              // the same memory as the device sees it
+  ~PulseInfo() { (void)hipHostFree(h); }   // (of NULL: no-op)
+};
+// Driven by one thread at a time (with its batches): table, scratch, events and pulse counters are shared by all its calls.
 struct Context {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hipStream_t stream = nullptr;      // the CALLER's (CreateContext / SetStream); what work runs on is an argument, `st`
   int num_cu = 256;
   int frame_grid = 256 * 8;          // upper bound on the workgroups of a grid-stride per-frame kernel
   int oversub = 6;                   // workgroups per resident slot of those kernels (persistent_grid): measured on
@@ -85,24 +124,19 @@ struct Context {
   uint32_t rng_state[4] = {123456789u, 362436069u, 521288629u, 88675123u};   // matlabfunctions.cpp:247-250
   double* d_scratch = nullptr;       // growable scratch (synthesis responses)
   int64_t scratch_cap = 0;           // in doubles
-  int ensure_rng(int64_t count);     // grow + (re)generate, returns error code
-  int ensure_scratch(int64_t doubles);
-  int64_t* h_pulse_info = nullptr;   // pinned, mapped: {total pulses, largest per-utterance count} of the last Synthesis
-  int64_t* d_pulse_info = nullptr;   // the same memory as the device sees it
-  // second stream + events of launch_analyze_synthesize (created on first use)
-  hipStream_t side = nullptr;
-  hipStream_t aux = nullptr;         // D4C's RARE launch (d4c_rare)
-  hipStream_t prep = nullptr;        // launch_synthesis: the f0-only kernels of the batch's second part
-  hipEvent_t ev_call = nullptr, ev_prep_b = nullptr;
-  hipEvent_t ev_f0 = nullptr, ev_prep = nullptr, ev_d4c = nullptr, ev_rare = nullptr;
-  hipEvent_t ev_pulse[2] = {nullptr, nullptr}, ev_ola[2] = {nullptr, nullptr};   // synthesis_render's two response halves
-  int ensure_side();                 // the second stream and its events, created on first use
+  // grow (+ generate); `user` is the stream whose kernels may still read the old block: waited for before it is freed
+  int ensure_rng(int64_t count, hipStream_t user);
+  int ensure_scratch(int64_t doubles, hipStream_t user);
+  std::unique_ptr<PulseInfo> pulse;      // made by Synthesis' first set-up on the context
+  std::unique_ptr<SideStreams> fork;
+  std::unique_ptr<SplitStreams> split;
+  int ensure_side(), ensure_split(); // `fork` / `split`, created on first use
   // Tables that depend on a few parameters, not on the utterances (Dio's filters, D4C's Nuttall window, Synthesis' DC
   // remover, StoneMask's twiddles): built once per context and key and shared by every batch of the context (the
   // drop-in API makes a batch per utterance length: rebuilding them per batch was 0.1 - 0.3 ms of every call)
   std::vector<std::unique_ptr<Table>> tables;
   template <class Build> int table(const TableKey& key, const Table*& out, Build build);
-  // optional per-kernel HIP-event timing on `stream` (bench.py's roofline leg)
+  // optional per-kernel HIP-event timing (bench.py's roofline leg): see TimedScope
   bool timing = false;
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> timed;
   void timing_clear();
@@ -155,7 +189,7 @@ template <class K> inline void allow_dynamic_lds(const Context& c, K kernel, int
 
 // Every entry point that takes a batch or a context runs on the context's device, whatever device is current on
 // the calling thread, and leaves the caller's current device as it found it.
-struct OnDevice {
+struct OnDevice : NoCopy {
   int prev = -1;
   explicit OnDevice(const Context& c) {
     int cur = -1;
@@ -164,22 +198,20 @@ struct OnDevice {
   ~OnDevice() {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
-  OnDevice(const OnDevice&) = delete;
-  OnDevice& operator=(const OnDevice&) = delete;
 };
 
-// RAII bracket: records a start/stop event pair around the launches in its scope.
+// RAII bracket: records a start/stop event pair on `st`, the stream of the launches in its scope.
 struct TimedScope {
-  Context* c;
+  hipStream_t st;
   hipEvent_t a = nullptr, b = nullptr;
-  TimedScope(Context* ctx, const char* name) : c(ctx) {
+  TimedScope(Context* c, hipStream_t stream, const char* name) : st(stream) {
     if (!c->timing) return;
     if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
-    (void)hipEventRecord(a, c->stream);
+    (void)hipEventRecord(a, st);
     c->timed[name].push_back(std::make_pair(a, b));
   }
   ~TimedScope() {
-    if (b) (void)hipEventRecord(b, c->stream);
+    if (b) (void)hipEventRecord(b, st);
   }
 };
 
@@ -210,7 +242,7 @@ struct Batch {
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
   std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato;
-  bool syn_warm = false;                    // launch_analyze_synthesize has run once on this batch
+  bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
   int64_t rng_bound_d4c() const;
@@ -225,14 +257,15 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
 int launch_cheaptrick(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_sp);
 int launch_d4c(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
 int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap);
-int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_f0);
-int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
-int d4c_run(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
 int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y);
-int synthesis_prepare(Batch& b, const double* d_f0, double* d_y);
-int synthesis_begin(Batch& b, const double* d_f0, double* d_y);      // the f0-only kernels, queued
-int synthesis_prepare_wait(Batch& b);                                 // their host round trip
-int synthesis_render(Batch& b, const double* d_sp, const double* d_ap, double* d_y);
+// the stages behind launch_d4c / launch_synthesis on the stream `st` they are given (context.cpp, the drop-in Synthesis())
+int d4c_prepare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0);
+int d4c_rare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
+int d4c_run(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
+int synthesis_prepare(Batch& b, hipStream_t st, const double* d_f0, double* d_y);
+int synthesis_begin(Batch& b, hipStream_t st, const double* d_f0, double* d_y);      // the f0-only kernels, queued
+int synthesis_prepare_wait(Batch& b, hipStream_t st);                                 // their host round trip
+int synthesis_render(Batch& b, hipStream_t st, const double* d_sp, const double* d_ap, double* d_y);
 int launch_analyze_synthesize(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap,
                               double* d_y);
 int launch_utterance_status(Batch& b, const double* d_x, const double* d_f0, const double* d_sp, const double* d_ap,

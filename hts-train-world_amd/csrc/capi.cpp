@@ -105,7 +105,6 @@ int WorldMi355CreateContext(int device, void* hip_stream, WorldMi355Context** ou
   // NULL selects the legacy default stream (stream 0): it orders with every blocking stream, which
   // is what callers that allocate and copy with plain hipMemcpy / torch's default stream expect.
   c.stream = (hipStream_t)hip_stream;
-  c.own_stream = false;
   *out = h;
   // every entry point switches to its context's device itself (OnDevice): the caller's current device stays
   if (before >= 0 && before != c.device) (void)hipSetDevice(before);
@@ -117,26 +116,12 @@ void WorldMi355DestroyContext(WorldMi355Context* h) {
   Context& c = h->c;
   OnDevice dev_(c);
   hipStreamSynchronize(c.stream);
+  if (c.fork) { hipStreamSynchronize(c.fork->side); hipStreamSynchronize(c.fork->aux); }
+  if (c.split) hipStreamSynchronize(c.split->prep);
   c.timing_clear();
-  if (c.d_rng) wm::dev_free(c.d_rng);
-  if (c.d_scratch) wm::dev_free(c.d_scratch);
-  c.tables.clear();
-  if (c.h_pulse_info) hipHostFree(c.h_pulse_info);
-  if (c.own_stream) hipStreamDestroy(c.stream);
-  if (c.side) { hipStreamSynchronize(c.side); hipStreamDestroy(c.side); }
-  if (c.ev_f0) hipEventDestroy(c.ev_f0);
-  if (c.ev_prep) hipEventDestroy(c.ev_prep);
-  if (c.ev_d4c) hipEventDestroy(c.ev_d4c);
-  if (c.ev_rare) hipEventDestroy(c.ev_rare);
-  if (c.aux) { hipStreamSynchronize(c.aux); hipStreamDestroy(c.aux); }
-  if (c.prep) { hipStreamSynchronize(c.prep); hipStreamDestroy(c.prep); }
-  if (c.ev_call) hipEventDestroy(c.ev_call);
-  if (c.ev_prep_b) hipEventDestroy(c.ev_prep_b);
-  for (int h = 0; h < 2; ++h) {
-    if (c.ev_pulse[h]) hipEventDestroy(c.ev_pulse[h]);
-    if (c.ev_ola[h]) hipEventDestroy(c.ev_ola[h]);
-  }
-  delete h;
+  wm::dev_free(c.d_rng);
+  wm::dev_free(c.d_scratch);
+  delete h;                            // the tables, the streams and events, the pinned counters: with their owners
 }
 
 int WorldMi355SetStream(WorldMi355Context* h, void* hip_stream) {
@@ -144,8 +129,6 @@ int WorldMi355SetStream(WorldMi355Context* h, void* hip_stream) {
   Context& c = h->c;
   int rc = wm_check(hipStreamSynchronize(c.stream));
   if (rc) return rc;
-  if (c.own_stream) hipStreamDestroy(c.stream);
-  c.own_stream = false;
   c.stream = (hipStream_t)hip_stream;
   return WM_OK;
 }
@@ -543,15 +526,18 @@ void drop_in_failed(const DropInError& e) {
 hipStream_t ws_stream() { return default_context()->c.stream; }
 
 // the upload stream of Synthesis(): its sp / ap rows travel beside the f0-only kernels, not behind them
-hipStream_t g_up_stream = nullptr;
-hipEvent_t g_up_done = nullptr;
-hipStream_t up_stream() {
-  if (!g_up_stream) {
-    if (hipStreamCreateWithFlags(&g_up_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&g_up_done, hipEventDisableTiming) != hipSuccess)
-      die("upload stream", WM_ERR_HIP);
+struct Upload : Handles {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+};
+const Upload* g_up = nullptr;            // made on first use and never destroyed, like g_ctx
+const Upload& upload_stream() {
+  if (!g_up) {
+    std::unique_ptr<Upload> u(new Upload());
+    if (u->Handles::stream(&u->stream) != hipSuccess || u->event(&u->done) != hipSuccess) die("upload stream", WM_ERR_HIP);
+    g_up = u.release();
   }
-  return g_up_stream;
+  return *g_up;
 }
 
 void h2d(double* dst, const double* staged, size_t n, hipStream_t st = nullptr) {
@@ -897,7 +883,7 @@ void Synthesis(const double* f0, int f0_length, const double* const* spectrogram
     double* dy = g_ws.device(kY, (size_t)y_length);
     {
       OnDevice dev_(b->b.ctx[0]);
-      run_or_die("Synthesis", synthesis_begin(b->b, df, dy));
+      run_or_die("Synthesis", synthesis_begin(b->b, ws_stream(), df, dy));
     }
     tr.mark("begin");
     // (the device and pinned buffers are sized before anything of this call is in flight on the upload stream: growing
@@ -907,17 +893,17 @@ void Synthesis(const double* f0, int f0_length, const double* const* spectrogram
     (void)g_ws.device(kAp, cells);
     (void)g_ws.stage(2 * cells + 16);
     g_ws.stage_at -= (2 * cells + 16 + 7) & ~(size_t)7;               // reserved, not taken
-    hipStream_t up = up_stream();
-    double* ds = put_rows(kSp, spectrogram, f0_length, w, up);
-    double* da = put_rows(kAp, aperiodicity, f0_length, w, up);
-    if (hipEventRecord(g_up_done, up) != hipSuccess) die("upload", WM_ERR_HIP);
+    const Upload& up = upload_stream();
+    double* ds = put_rows(kSp, spectrogram, f0_length, w, up.stream);
+    double* da = put_rows(kAp, aperiodicity, f0_length, w, up.stream);
+    if (hipEventRecord(up.done, up.stream) != hipSuccess) die("upload", WM_ERR_HIP);
     tr.mark("stage");
     {
       OnDevice dev_(b->b.ctx[0]);
-      run_or_die("Synthesis", synthesis_prepare_wait(b->b));
+      run_or_die("Synthesis", synthesis_prepare_wait(b->b, ws_stream()));
       tr.mark("wait");
-      if (hipStreamWaitEvent(ws_stream(), g_up_done, 0) != hipSuccess) die("upload", WM_ERR_HIP);
-      run_or_die("Synthesis", synthesis_render(b->b, ds, da, dy));
+      if (hipStreamWaitEvent(ws_stream(), up.done, 0) != hipSuccess) die("upload", WM_ERR_HIP);
+      run_or_die("Synthesis", synthesis_render(b->b, ws_stream(), ds, da, dy));
     }
     tr.mark("launch");
     tr.mark("kernels", true);

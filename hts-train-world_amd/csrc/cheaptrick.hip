@@ -207,7 +207,7 @@ __global__ __launch_bounds__(64, F >= 4096 ? 1 : (F >= 2048 ? 2 : 3)) void cheap
 int launch_cheaptrick(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_sp) {
   hipStream_t st = b.ctx->stream;
   const int F = b.p.fft_size;
-  int rc = b.ctx->ensure_rng(b.rng_bound_cheaptrick());
+  int rc = b.ctx->ensure_rng(b.rng_bound_cheaptrick(), st);
   if (rc) return rc;
   hipLaunchKernelGGL(cheaptrick_offsets_kernel, dim3(b.n_utt), dim3(256), 0, st, d_f0, b.d_f_off, b.p.fs, F,
                      b.d_rng_off);
@@ -226,7 +226,7 @@ int launch_cheaptrick(Batch& b, const double* d_x, const double* d_t, const doub
                        b.p.fs, b.p.q1, tf, (const int*)b.d_perm, (const int*)b.d_part_n, d_sp);          \
   } break;
   {
-  TimedScope ts_(b.ctx, "cheaptrick_kernel");
+  TimedScope ts_(b.ctx, st, "cheaptrick_kernel");
   launch_partition(st, CtUsualPred{d_f0, b.p.fs, F}, (int)tf, b.d_part_cnt, b.d_perm, b.d_part_n);
   switch (F) {
     WM_CT_CASE(512)       // fs <= 12.8 kHz (GetFFTSizeForCheapTrick, cheaptrick.cpp:191-194)

@@ -365,7 +365,7 @@ static int code_sp(Batch& b, const double* d_in, int ndim, CodeOpts o, OUT* d_ou
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
   hipStream_t st = b.ctx->stream;
-  TimedScope ts_(b.ctx, name);
+  TimedScope ts_(b.ctx, st, name);
 #define WM_CODE_CASE(FF)                                                                                     \
   case FF: {                                                                                                 \
     const int per_ = persistent_grid(*b.ctx, codec_code_sp_kernel<FF, OUT>, 64, (int64_t)1 << 40);    \
@@ -398,7 +398,7 @@ static int decode_sp(Batch& b, const IN* d_coded, int ndim, DecodeOpts o, double
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
   hipStream_t st = b.ctx->stream;
-  TimedScope ts_(b.ctx, "codec_decode_sp_kernel");
+  TimedScope ts_(b.ctx, st, "codec_decode_sp_kernel");
 #define WM_DEC_CASE(FF)                                                                                      \
   case FF: {                                                                                                 \
     const int per_ = persistent_grid(*b.ctx, codec_decode_sp_kernel<FF, IN>, 64, (int64_t)1 << 40);   \
@@ -423,7 +423,7 @@ int launch_code_aperiodicity(Batch& b, const double* d_ap, double* d_coded) {
   const int nap = codec_num_aperiodicities(b.p.fs);
   const int64_t n = b.total_f * nap;
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, "codec_code_ap_kernel");
+  TimedScope ts_(b.ctx, b.ctx->stream, "codec_code_ap_kernel");
   hipLaunchKernelGGL(codec_code_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, d_ap,
                      b.p.fft_size / 2 + 1, b.p.fs, b.p.fft_size, nap, b.total_f, d_coded);
   return wm_check(hipGetLastError());
@@ -434,7 +434,7 @@ int launch_decode_aperiodicity(Batch& b, const double* d_coded, double* d_ap) {
   if (nap < 1) return WM_ERR_UNSUPPORTED;
   const int64_t n = b.total_f * (b.p.fft_size / 2 + 1);
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, "codec_decode_ap_kernel");
+  TimedScope ts_(b.ctx, b.ctx->stream, "codec_decode_ap_kernel");
   hipLaunchKernelGGL(codec_decode_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, d_coded,
                      nap, b.p.fs, b.p.fft_size, b.total_f, d_ap);
   return wm_check(hipGetLastError());
@@ -585,7 +585,7 @@ int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const
   if (tf <= 0) return WM_OK;
   hipStream_t st = b.ctx->stream;
   {
-    TimedScope ts_(b.ctx, "codec_bap_decode_kernel");
+    TimedScope ts_(b.ctx, st, "codec_bap_decode_kernel");
     const int64_t cap = (int64_t)b.ctx->num_cu * 16;
     const int64_t units = order < 32 ? (tf + 1) / 2 : tf;
     const dim3 grid((unsigned)(units < cap ? units : cap));
@@ -691,7 +691,7 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
   m.total_cols = col;
   const int64_t n = b.total_f * col;
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, "cmp_compose_kernel");
+  TimedScope ts_(b.ctx, b.ctx->stream, "cmp_compose_kernel");
   hipLaunchKernelGGL(cmp_compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, m,
                      b.d_frame_utt, b.d_f_off, b.total_f, d_out);
   return wm_check(hipGetLastError());

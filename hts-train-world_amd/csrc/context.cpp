@@ -3,11 +3,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
-
 #include <mutex>
 #include <unordered_map>
-#include <iterator>
 
 #include "batch.hpp"
 #include "common.hpp"
@@ -179,7 +178,7 @@ static void fill_randn_u32(uint32_t* out, int64_t count, uint32_t (&st)[4]) {
 
 // The table only ever grows: entries [0, rng_cap) stay, the tail continues the xorshift stream from
 // the saved state (a longer utterance after a shorter one costs its extra entries, not a new table).
-int Context::ensure_rng(int64_t count) {
+int Context::ensure_rng(int64_t count, hipStream_t user) {
   // consumers index the table with 32-bit per-utterance offsets (d_rng_off, randn_at): an utterance whose draws
   // could pass 2^31 (about 135 k frames at 48 kHz) is refused instead of wrapping silently
   if (count > (int64_t)INT32_MAX) {
@@ -192,8 +191,9 @@ int Context::ensure_rng(int64_t count) {
   const int64_t add = cap - rng_cap;
   std::vector<uint32_t> host((size_t)add);
   fill_randn_u32(host.data(), add, rng_state);
-  // the old table may still be read by kernels in flight on the stream
-  int rc = wm_check(hipStreamSynchronize(stream));
+  // The old table may still be read by kernels in flight.  `user` is enough: every call ends with its other streams
+  // joined into the caller's, and the one-call forms settle the size before they fork (no growth under two streams).
+  int rc = wm_check(hipStreamSynchronize(user));
   if (rc) return rc;
   uint32_t* grown = nullptr;
   rc = wm_check(dev_alloc(&grown, sizeof(uint32_t) * (size_t)cap));
@@ -209,9 +209,11 @@ int Context::ensure_rng(int64_t count) {
   return WM_OK;
 }
 
-int Context::ensure_scratch(int64_t doubles) {
+int Context::ensure_scratch(int64_t doubles, hipStream_t user) {
   if (doubles <= scratch_cap) return WM_OK;
-  int rc = wm_check(hipStreamSynchronize(stream));
+  // `user` is enough: the scratch's last users, the overlap-adds on the side stream, were joined into the stream of the
+  // call that queued them (synthesis_join), and a later call's preparation is ordered behind that
+  int rc = wm_check(hipStreamSynchronize(user));
   if (rc) return rc;
   if (d_scratch) dev_free(d_scratch);
   d_scratch = nullptr;
@@ -223,17 +225,30 @@ int Context::ensure_scratch(int64_t doubles) {
 }
 
 int Context::ensure_side() {
-  if (side) return WM_OK;
-  int rc = wm_check(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-  rc = rc ? rc : wm_check(hipEventCreateWithFlags(&ev_f0, hipEventDisableTiming));
-  rc = rc ? rc : wm_check(hipEventCreateWithFlags(&ev_prep, hipEventDisableTiming));
-  rc = rc ? rc : wm_check(hipEventCreateWithFlags(&ev_d4c, hipEventDisableTiming));
-  rc = rc ? rc : wm_check(hipEventCreateWithFlags(&ev_rare, hipEventDisableTiming));
-  rc = rc ? rc : wm_check(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-  for (int h = 0; h < 2 && !rc; ++h) {
-    rc = wm_check(hipEventCreateWithFlags(&ev_pulse[h], hipEventDisableTiming));
-    rc = rc ? rc : wm_check(hipEventCreateWithFlags(&ev_ola[h], hipEventDisableTiming));
+  if (fork) return WM_OK;
+  std::unique_ptr<SideStreams> s(new SideStreams());
+  int rc = wm_check(s->stream(&s->side));
+  for (hipEvent_t* e : {&s->ev_f0, &s->ev_prep, &s->ev_d4c, &s->ev_rare}) rc = rc ? rc : wm_check(s->event(e));
+  rc = rc ? rc : wm_check(s->stream(&s->aux));
+  for (int h = 0; h < 2; ++h) {
+    rc = rc ? rc : wm_check(s->event(&s->ev_pulse[h]));
+    rc = rc ? rc : wm_check(s->event(&s->ev_ola[h]));
   }
+  if (!rc) fork = std::move(s);
+  return rc;
+}
+
+int Context::ensure_split() {
+  if (split) return WM_OK;
+  // the highest priority there is: its workgroups are few and latency-bound, and they only get the slots the
+  // pulse kernel's workgroups leave as they retire
+  int prio_lo = 0, prio_hi = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  std::unique_ptr<SplitStreams> s(new SplitStreams());
+  int rc = wm_check(s->stream(&s->prep, prio_hi));
+  rc = rc ? rc : wm_check(s->event(&s->ev_call));
+  rc = rc ? rc : wm_check(s->event(&s->ev_prep_b));
+  if (!rc) split = std::move(s);
   return rc;
 }
 
@@ -242,46 +257,46 @@ int Context::ensure_side() {
 // SIMDs, i.e. for CheapTrick to drain, and would hold up whatever came behind them on a shared stream); d4c_after()
 // queues the usual kernel behind the preparation and makes the caller's stream wait for the RARE launch.
 static int d4c_beside(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
-  Context& c = *b.ctx;
-  hipStream_t main_stream = c.stream;
-  c.stream = c.side;
-  int rc = d4c_prepare(b, d_x, d_t, d_f0);
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_d4c, c.side));
-  rc = rc ? rc : wm_check(hipStreamWaitEvent(c.aux, c.ev_d4c, 0));
-  c.stream = c.aux;
-  rc = rc ? rc : d4c_rare(b, d_x, d_t, d_f0, d_ap);
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_rare, c.aux));
-  c.stream = main_stream;
-  return rc;
+  const SideStreams& s = *b.ctx->fork;
+  int rc = d4c_prepare(b, s.side, d_x, d_t, d_f0);
+  rc = rc ? rc : wm_check(hipEventRecord(s.ev_d4c, s.side));
+  rc = rc ? rc : wm_check(hipStreamWaitEvent(s.aux, s.ev_d4c, 0));
+  rc = rc ? rc : d4c_rare(b, s.aux, d_x, d_t, d_f0, d_ap);
+  return rc ? rc : wm_check(hipEventRecord(s.ev_rare, s.aux));
 }
 static int d4c_after(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
   Context& c = *b.ctx;
-  int rc = wm_check(hipStreamWaitEvent(c.stream, c.ev_d4c, 0));
-  rc = rc ? rc : d4c_run(b, d_x, d_t, d_f0, d_ap);
-  return rc ? rc : wm_check(hipStreamWaitEvent(c.stream, c.ev_rare, 0));
+  int rc = wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_d4c, 0));
+  rc = rc ? rc : d4c_run(b, c.stream, d_x, d_t, d_f0, d_ap);
+  return rc ? rc : wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_rare, 0));
+}
+
+// Dio -> StoneMask -> CheapTrick -> D4C, one behind the other on the caller's stream
+static int analyze_in_order(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
+  int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
+  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
+  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
+  return rc ? rc : launch_d4c(b, d_x, d_t, d_f0, d_ap);
+}
+// The same with D4C's preparation on the second stream beside CheapTrick, from f0 (ev_f0) on.
+static int analyze_forked(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
+  Context& c = *b.ctx;
+  int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
+  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
+  rc = rc ? rc : c.ensure_side();
+  // the randn table must not move under two streams (it may be reallocated when it grows): settle its size first
+  rc = rc ? rc : c.ensure_rng(std::max(b.rng_bound_cheaptrick(), b.rng_bound_d4c()), c.stream);
+  rc = rc ? rc : wm_check(hipEventRecord(c.fork->ev_f0, c.stream));
+  rc = rc ? rc : wm_check(hipStreamWaitEvent(c.fork->side, c.fork->ev_f0, 0));
+  rc = rc ? rc : d4c_beside(b, d_x, d_t, d_f0, d_ap);
+  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
+  return rc ? rc : d4c_after(b, d_x, d_t, d_f0, d_ap);
 }
 
 // Dio -> StoneMask -> CheapTrick -> D4C as one call: D4C's preparation runs on the second stream beside CheapTrick
 // once the batch has its D4C tables (the first use allocates them, in the plain order).
 int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
-  Context& c = *b.ctx;
-  int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
-  if (rc) return rc;
-  if (!b.d4c) {
-    rc = launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-    return rc ? rc : launch_d4c(b, d_x, d_t, d_f0, d_ap);
-  }
-  int64_t need = b.rng_bound_cheaptrick();                 // the randn table must not move under two streams
-  if (b.rng_bound_d4c() > need) need = b.rng_bound_d4c();
-  rc = c.ensure_side();
-  rc = rc ? rc : c.ensure_rng(need);
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_f0, c.stream));
-  rc = rc ? rc : wm_check(hipStreamWaitEvent(c.side, c.ev_f0, 0));
-  if (rc) return rc;
-  rc = d4c_beside(b, d_x, d_t, d_f0, d_ap);
-  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-  return rc ? rc : d4c_after(b, d_x, d_t, d_f0, d_ap);
+  return b.d4c ? analyze_forked(b, d_x, d_t, d_f0, d_sp, d_ap) : analyze_in_order(b, d_x, d_t, d_f0, d_sp, d_ap);
 }
 
 // Analysis followed by Synthesis of the same features (BASELINE.json's metric), as one call.  Identical
@@ -293,40 +308,23 @@ int launch_analyze_synthesize(Batch& b, const double* d_x, double* d_t, double* 
                               double* d_y) {
   Context& c = *b.ctx;
   int rc = c.ensure_side();
+  // Synthesis reads the randn table too: the size is settled here for all three stages, in one growth
+  rc = rc ? rc : c.ensure_rng(std::max({b.rng_bound_cheaptrick(), b.rng_bound_d4c(), b.rng_bound_synthesis()}), c.stream);
   if (rc) return rc;
-  // the randn table may be reallocated when it grows: settle its size before two streams read it
-  int64_t need = b.rng_bound_cheaptrick();
-  if (b.rng_bound_d4c() > need) need = b.rng_bound_d4c();
-  if (b.rng_bound_synthesis() > need) need = b.rng_bound_synthesis();
-  rc = c.ensure_rng(need);
-  if (!rc && !b.syn_warm) {
+  if (!b.syn_warm) {
     // first use of this batch: Synthesis allocates its work arrays and sizes the response scratch, and a
     // hipMalloc of gigabytes stalls kernels running beside it -- take the plain order once
-    b.syn_warm = true;
-    rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
-    rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
-    rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-    rc = rc ? rc : launch_d4c(b, d_x, d_t, d_f0, d_ap);
-    return rc ? rc : launch_synthesis(b, d_f0, d_sp, d_ap, d_y);
+    rc = analyze_in_order(b, d_x, d_t, d_f0, d_sp, d_ap);
+    rc = rc ? rc : launch_synthesis(b, d_f0, d_sp, d_ap, d_y);
+    b.syn_warm = !rc;                                          // a failed first use is made again in this order
+    return rc;
   }
-  rc = rc ? rc : launch_dio(b, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_f0, c.stream));
-  if (rc) return rc;
-  hipStream_t main_stream = c.stream;
   // second stream, from f0 on: D4C's preparation (offsets, LoveTrain, frame lists), then Synthesis's
-  rc = wm_check(hipStreamWaitEvent(c.side, c.ev_f0, 0));
-  rc = rc ? rc : d4c_beside(b, d_x, d_t, d_f0, d_ap);
-  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-  rc = rc ? rc : d4c_after(b, d_x, d_t, d_f0, d_ap);
-  if (!rc) {
-    c.stream = c.side;
-    rc = synthesis_prepare(b, d_f0, d_y);
-    if (!rc) rc = wm_check(hipEventRecord(c.ev_prep, c.side));
-    c.stream = main_stream;
-  }
-  rc = rc ? rc : wm_check(hipStreamWaitEvent(main_stream, c.ev_prep, 0));
-  return rc ? rc : synthesis_render(b, d_sp, d_ap, d_y);
+  rc = analyze_forked(b, d_x, d_t, d_f0, d_sp, d_ap);
+  rc = rc ? rc : synthesis_prepare(b, c.fork->side, d_f0, d_y);
+  rc = rc ? rc : wm_check(hipEventRecord(c.fork->ev_prep, c.fork->side));
+  rc = rc ? rc : wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_prep, 0));
+  return rc ? rc : synthesis_render(b, c.stream, d_sp, d_ap, d_y);
 }
 
 void Context::timing_clear() {

@@ -581,11 +581,10 @@ static D4cWs& d4c_ws(Batch& b) { return static_cast<D4cWs&>(*b.d4c); }
 static inline int rare_grid(const Context& c, int persistent) { return imax(1, persistent / imax(1, c.oversub)); }
 
 template <int FD>
-static int launch_d4c_big(Batch& b, const double* d_x, const double* d_t, const double* d_f0, D4CTables tab,
-                          double* d_ap) {
+static int launch_d4c_big(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0,
+                          D4CTables tab, double* d_ap) {
   typedef D4cBig<FD> G;
   Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   const int64_t tf = b.total_f;
   if (tab.window_length >= FD / 4) return WM_ERR_UNSUPPORTED;    // d4cb_band_kernel: taps fill half the packed operand at most
   const int g1 = persistent_grid(c, d4cb_centroid_kernel<FD>, 64, (int64_t)1 << 40);
@@ -635,7 +634,7 @@ static int launch_d4c_big(Batch& b, const double* d_x, const double* d_t, const 
 }
 
 // D4C in three steps.  d4c_prepare(): everything that needs f0 (and the waveform, for the LoveTrain ratio) but no
-// result of CheapTrick -- the randn offsets, the LoveTrain stage and the three frame lists -- on the context's stream.
+// result of CheapTrick -- the randn offsets, the LoveTrain stage and the three frame lists.
 // d4c_rare(): the RARE instantiation over its list (normally empty).  d4c_run(): the transforms of the usual frames.  launch_analyze_synthesize() puts the first on its second stream beside CheapTrick (ten
 // short dependent launches, 0.1 ms of an otherwise idle machine between CheapTrick and the D4C kernel); the lists and
 // offsets are D4C's own arrays (`*_d4c`), so nothing of CheapTrick's is touched.
@@ -651,9 +650,8 @@ static int d4c_tables(Batch& b, D4CTables& tab) {
   return WM_OK;
 }
 
-int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_f0) {
+int d4c_prepare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0) {
   Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   const int fs = b.p.fs;
   const int FD = d4c_fft_size(fs), FL = lovetrain_fft_size(fs);
   // D4C's own transform and LoveTrain's are sized independently (d4c.cpp:344-346, :261-263): they differ for fs in
@@ -661,7 +659,7 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
   // only run for a threshold above zero.
   if (FD != 1024 && FD != 2048 && FD != 4096 && FD != 8192) return WM_ERR_UNSUPPORTED_FFT;
   if (b.p.d4c_threshold > 0.0 && FL != 1024 && FL != 2048 && FL != 4096 && FL != 8192) return WM_ERR_UNSUPPORTED_FFT;
-  int rc = c.ensure_rng(b.rng_bound_d4c());
+  int rc = c.ensure_rng(b.rng_bound_d4c(), st);
   if (rc) return rc;
   if (!b.d4c) {
     // Nuttall window table for GetCoarseAperiodicity (d4c.cpp:356-359, common.cpp:113-121): once per context and
@@ -706,7 +704,7 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
                        (const int*)b.d_perm_d4c, (const int*)b.d_part_n_d4c, b.d_ap0);                             \
   } break;
   {
-    TimedScope ts_(b.ctx, "d4c_lovetrain_kernel");
+    TimedScope ts_(b.ctx, st, "d4c_lovetrain_kernel");
     if (b.p.d4c_threshold <= 0.0) {
       // every voiced frame passes whatever the ratio is: see d4c_lovetrain_all_pass_kernel
       hipLaunchKernelGGL(d4c_lovetrain_all_pass_kernel, dim3((unsigned)((tf + 255) / 256)), dim3(256), 0, st, d_f0, tf,
@@ -737,9 +735,8 @@ int d4c_prepare(Batch& b, const double* d_x, const double* d_t, const double* d_
   return wm_check(hipGetLastError());
 }
 
-int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
+int d4c_rare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
   Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   const int fs = b.p.fs;
   const int FD = d4c_fft_size(fs);
   D4CTables tab;
@@ -778,9 +775,8 @@ int d4c_rare(Batch& b, const double* d_x, const double* d_t, const double* d_f0,
   return wm_check(hipGetLastError());
 }
 
-int d4c_run(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
+int d4c_run(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
   Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   const int fs = b.p.fs;
   const int FD = d4c_fft_size(fs);
   D4CTables tab;
@@ -797,16 +793,16 @@ int d4c_run(Batch& b, const double* d_x, const double* d_t, const double* d_f0, 
                        (const int*)b.d_perm_d4c, (const int*)b.d_part_n_d4c, d_ap);                               \
   } break;
   {
-    TimedScope ts_(b.ctx, "d4c_kernel");
+    TimedScope ts_(b.ctx, st, "d4c_kernel");
     switch (FD) {
       WM_D4C_CASE(1024, 2)
       WM_D4C_CASE(2048, 2)
       case 4096: {              // four kernels on the 1024-point transform (d4c_big.hpp)
-        rc = launch_d4c_big<4096>(b, d_x, d_t, d_f0, tab, d_ap);
+        rc = launch_d4c_big<4096>(b, st, d_x, d_t, d_f0, tab, d_ap);
         if (rc) return rc;
       } break;
       case 8192: {              // the same on the 2048-point transform (fs above 48.1 kHz)
-        rc = launch_d4c_big<8192>(b, d_x, d_t, d_f0, tab, d_ap);
+        rc = launch_d4c_big<8192>(b, st, d_x, d_t, d_f0, tab, d_ap);
         if (rc) return rc;
       } break;
     }
@@ -816,9 +812,10 @@ int d4c_run(Batch& b, const double* d_x, const double* d_t, const double* d_f0, 
 }
 
 int launch_d4c(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
-  int rc = d4c_prepare(b, d_x, d_t, d_f0);
-  rc = rc ? rc : d4c_rare(b, d_x, d_t, d_f0, d_ap);
-  return rc ? rc : d4c_run(b, d_x, d_t, d_f0, d_ap);
+  const hipStream_t st = b.ctx->stream;
+  int rc = d4c_prepare(b, st, d_x, d_t, d_f0);
+  rc = rc ? rc : d4c_rare(b, st, d_x, d_t, d_f0, d_ap);
+  return rc ? rc : d4c_run(b, st, d_x, d_t, d_f0, d_ap);
 }
 
 #ifdef WM_PHASE

@@ -705,7 +705,7 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
     const bool small = ntap <= zc_max_taps<kZcStrideHarvest>();
     if (!m.lc_conv && !small && ntap > zc_max_taps<kZcStrideLong>()) return WM_ERR_UNSUPPORTED;
     const size_t lds = sizeof(double) * (size_t)((small ? kZcStrideHarvest : kZcStrideLong) * kBandK + zc_pad16(ntap));
-    TimedScope ts_(b.ctx, "dio_lowcut_kernel");
+    TimedScope ts_(b.ctx, st, "dio_lowcut_kernel");
     if (m.lc_conv) {
       const int V = m.lc_conv - ntap + 1;
       const dim3 grid((total_max + V - 1) / V, b.n_utt);
@@ -732,7 +732,7 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
     const size_t lds = sizeof(double) * (size_t)(small ? zc_lds_doubles<kZcStrideDio>(ntap_max)
                                                        : zc_lds_doubles<kZcStrideHarvest>(ntap_max));
     const int tiles_max = dio_tiles(b.max_x_len / m.ratio + 1, m.step);
-    TimedScope ts_(b.ctx, "dio_band_kernel");
+    TimedScope ts_(b.ctx, st, "dio_band_kernel");
     if (m.band_conv) {
       const cpx* Hb = W.d_H + (m.lc_conv ? m.lc_conv / 2 + 1 : 0);
       if (m.band_conv == 4096) {
@@ -762,13 +762,13 @@ int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   }
   {
     const int gx = (int)((b.total_f + 255) / 256);
-    TimedScope ts_(b.ctx, "dio_candidate_kernel");
+    TimedScope ts_(b.ctx, st, "dio_candidate_kernel");
     hipLaunchKernelGGL(dio_candidate_kernel, dim3(gx, m.nb), dim3(256), 0, st, W.d_ylen, b.d_f_off,
                        b.d_frame_utt, b.p.frame_period, m, b.p.f0_floor, b.p.f0_ceil, W.d_ev_off, W.d_events,
                        W.d_ev_cnt, b.total_f, W.d_cand, W.d_score);
   }
   {
-  TimedScope ts_(b.ctx, "dio_fix_kernel");
+  TimedScope ts_(b.ctx, st, "dio_fix_kernel");
   const int edge_cap = b.max_f0_len / 2 + 2;
   const size_t lds = sizeof(int) * 2 * (size_t)edge_cap;
   if (lds <= 48 * 1024) {

@@ -1493,7 +1493,7 @@ int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   if (m.r > 1) {
     const int len_max = b.max_x_len + 2 * m.lag + 18;
     const int blocks = (len_max + 64 * kDecChunk - 1) / (64 * kDecChunk);
-    TimedScope ts_(b.ctx, "hv_decimate");
+    TimedScope ts_(b.ctx, st, "hv_decimate");
     (void)hipMemsetAsync(W.d_y, 0, sizeof(double) * (size_t)W.tot_y, st);
     const DecMeta dm = make_dec_meta(m.r, m.lag);
     hipLaunchKernelGGL(decim_fwd_kernel, dim3(blocks, n_utt), dim3(64), 0, st, d_x, b.d_x_off, b.d_x_len, dm,
@@ -1508,11 +1508,11 @@ int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   hipLaunchKernelGGL(hv_mean_sub_kernel, dim3(kHvMeanTiles, n_utt), dim3(256), 0, st, W.d_yoff, W.d_ylen,
                      (const double*)W.d_mean_part, W.d_y);
   {
-    TimedScope ts_(b.ctx, "hv_band_kernel");
+    TimedScope ts_(b.ctx, st, "hv_band_kernel");
     if (m.conv) {
       allow_dynamic_lds(*b.ctx, hv_band_fft_kernel<2048>, (int)(ConvEvCfg<2048, kHvConvC>::kLdsBytes));
       const int groups = (m.nch + kHvChGroup - 1) / kHvChGroup;
-      TimedScope tf_(b.ctx, "hv_band_fft_kernel");
+      TimedScope tf_(b.ctx, st, "hv_band_fft_kernel");
       hipLaunchKernelGGL(hv_band_fft_kernel<2048>, dim3(W.tiles_max, groups, n_utt), dim3(64),
                          (ConvEvCfg<2048, kHvConvC>::kLdsBytes), st, W.d_yoff, W.d_ylen, W.d_y, (const cpx*)W.d_H, m.nch, m.half0,
                          m.step, W.tiles_max, W.d_tile_cnt, W.d_slot_off, W.d_slots);
@@ -1528,7 +1528,7 @@ int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
     // (no compaction of the staged events into contiguous lists any more: hv_raw_kernel reads the slots, SlotList)
   }
   {
-    TimedScope ts_(b.ctx, "hv_raw_kernel");
+    TimedScope ts_(b.ctx, st, "hv_raw_kernel");
     const int64_t items = W.n_runs * m.nch;                      // four threads (the four tracks) each
     hipLaunchKernelGGL(hv_raw_kernel, dim3((unsigned)((items * 4 + 255) / 256)), dim3(256), 0, st, W.d_run_utt, W.d_run_first,
                        items, W.d_boff, W.d_nb1, W.d_ylen, m, W.d_bf, b.p.f0_floor, b.p.f0_ceil, W.tiles_max,
@@ -1538,13 +1538,13 @@ int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
   (void)hipMemsetAsync(W.d_ncand1, 0, sizeof(int) * (size_t)n_utt, st);
   if (m.nch > 192) return WM_ERR_UNSUPPORTED;                    // hv_detect_kernel: channel mask of 3 words
   {
-    TimedScope ts_(b.ctx, "hv_detect_kernel");
+    TimedScope ts_(b.ctx, st, "hv_detect_kernel");
     const int64_t gd = W.tot_b < (int64_t)c.num_cu * 64 ? W.tot_b : (int64_t)c.num_cu * 64;
     hipLaunchKernelGGL(hv_detect_kernel, dim3((unsigned)gd), dim3(64), 0, st, W.d_bframe_utt, m, W.d_raw, W.tot_b,
                        W.d_offc, W.d_cnt, W.d_ncand1);
   }
   {
-    TimedScope ts_(b.ctx, "hv_refine_kernel");
+    TimedScope ts_(b.ctx, st, "hv_refine_kernel");
     const size_t lds = sizeof(double) * (size_t)((kRfChunk + 6) * m.cpf) + sizeof(int) * kRfBins + sizeof(int4) * kRfChunk +
                        sizeof(unsigned short) * (size_t)(kRfChunk * m.maxc);
     if (m.maxc > 255) return WM_ERR_UNSUPPORTED;                  // a slot is eight bits of a listed pair
@@ -1555,13 +1555,13 @@ int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
                        (const cpx*)W.d_twid, W.d_rc, W.d_rs);
   }
   {
-    TimedScope ts_(b.ctx, "hv_remove_kernel");
+    TimedScope ts_(b.ctx, st, "hv_remove_kernel");
     const size_t lds_rm = sizeof(double) * (size_t)((kRmFrames + 2) * m.maxc);
     hipLaunchKernelGGL(hv_remove_kernel, dim3((unsigned)((W.tot_b + kRmFrames - 1) / kRmFrames)), dim3(256), lds_rm, st,
                        W.d_bframe_utt, W.d_boff, W.d_nb1, m, W.d_ncand1, W.d_rc, W.d_rs, W.tot_b, W.d_rc2, W.d_rs2);
   }
   {
-    TimedScope ts_(b.ctx, "hv_contour_kernel");
+    TimedScope ts_(b.ctx, st, "hv_contour_kernel");
     hipLaunchKernelGGL(hv_base_kernel, dim3((unsigned)((W.tot_b + 255) / 256)), dim3(256), 0, st, W.d_bframe_utt, W.d_boff, m,
                        W.d_ncand1, W.d_rc2, W.d_rs2, W.tot_b, W.d_work, W.d_work + W.tot_b, W.d_work + 2 * W.tot_b,
                        W.d_work + 3 * W.tot_b);

@@ -270,7 +270,7 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
   }
   rc = wm_check(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)tf, c.stream));    // stonemask.cpp:186-187
   if (rc) return rc;
-  TimedScope ts_(b.ctx, "stonemask_kernel");
+  TimedScope ts_(b.ctx, c.stream, "stonemask_kernel");
   launch_partition(c.stream, StoneMaskPred{d_f0, fs / 12.0}, (int)tf, b.d_part_cnt, b.d_perm, b.d_part_n);
   const int64_t chunks = (tf + kSmChunk - 1) / kSmChunk;
   const int64_t cap = (int64_t)c.num_cu * 64;

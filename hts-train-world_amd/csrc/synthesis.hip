@@ -984,7 +984,7 @@ struct SynWs : StageWs {
 };
 static SynWs& syn_ws(Batch& b) { return static_cast<SynWs&>(*b.syn); }
 
-static int synthesis_arena(Batch& b) {
+static int synthesis_arena(Batch& b, hipStream_t st) {
   Context& c = *b.ctx;
   const int F = b.p.fft_size;
   if (b.syn) return WM_OK;
@@ -1002,18 +1002,20 @@ static int synthesis_arena(Batch& b) {
   int rc = c.table({kDcRemover, {(double)F}}, dcr, [&](Table& t) {
     int r = wm_check(t.alloc(&t.d[0], sizeof(double) * (size_t)F));
     if (r) return r;
-    hipLaunchKernelGGL(synth_dc_remover_kernel, dim3(1), dim3(64), 0, c.stream, F, (double*)t.d[0]);
-    return wm_check(hipStreamSynchronize(c.stream));              // later calls may come on other streams
+    hipLaunchKernelGGL(synth_dc_remover_kernel, dim3(1), dim3(64), 0, st, F, (double*)t.d[0]);
+    return wm_check(hipStreamSynchronize(st));                    // later calls may come on other streams
   });
   if (rc) return rc;
   std::unique_ptr<SynWs> W(new SynWs());
   unsigned char* base = nullptr;
   rc = wm_check(W->alloc(&base, at));
   if (rc) return rc;
-  if (!c.h_pulse_info) {            // per context: two pinned, device-visible integers
-    rc = wm_check(hipHostMalloc((void**)&c.h_pulse_info, sizeof(int64_t) * 2, hipHostMallocMapped));
-    if (!rc) rc = wm_check(hipHostGetDevicePointer((void**)&c.d_pulse_info, c.h_pulse_info, 0));
+  if (!c.pulse) {                   // per context: two pinned, device-visible integers
+    std::unique_ptr<PulseInfo> pi(new PulseInfo());
+    rc = wm_check(hipHostMalloc((void**)&pi->h, sizeof(int64_t) * 2, hipHostMallocMapped));
+    if (!rc) rc = wm_check(hipHostGetDevicePointer((void**)&pi->d, pi->h, 0));
     if (rc) return rc;
+    c.pulse = std::move(pi);
   }
   W->d_pulse_idx = (int*)(base + o_idx); W->d_pulse_shift = (double*)(base + o_shift);
   W->d_vuv = (double*)(base + o_vuv); W->d_phase = (double*)(base + o_phase);
@@ -1029,32 +1031,31 @@ static int synthesis_arena(Batch& b) {
   W->sorted.assign(order.begin() + (long)nu, order.end());
   // (a copy from pageable memory returns once the source has been read or staged: no wait here -- it was 20 us of
   // every Synthesis() of a new utterance length)
-  rc = wm_check(hipMemcpyAsync(W->d_order, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, c.stream));
+  rc = wm_check(hipMemcpyAsync(W->d_order, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, st));
   if (rc) return rc;
   b.syn = std::move(W);
   return WM_OK;
 }
 
-// The f0-only kernels of a part, up to its pulse numbers: asynchronous on the context's stream.
-static int synthesis_prepare_launch(Batch& b, const SynPart& part, const double* d_f0) {
+// The f0-only kernels of a part, up to its pulse numbers: asynchronous on `st`.
+static int synthesis_prepare_launch(Batch& b, hipStream_t st, const SynPart& part, const double* d_f0) {
   Context& c = *b.ctx;
   SynWs& W = syn_ws(b);
-  hipStream_t st = c.stream;
   const int F = b.p.fft_size, fs = b.p.fs;
   const double fp = b.p.frame_period / 1000.0;
   const double lowest_f0 = fs / F + 1.0;                  // integer division as in synthesis.cpp:359
   {
     const int tiles = imin(64, (part.max_y_len + 255) / 256);
     {
-      TimedScope ts_(b.ctx, "synth_inc_kernel");
+      TimedScope ts_(b.ctx, st, "synth_inc_kernel");
       hipLaunchKernelGGL(synth_inc_kernel, dim3(tiles, part.n), dim3(256), 0, st, part.d_list, d_f0, b.d_f_off,
                          b.d_y_off, fs, fp, lowest_f0, W.d_vuv, W.d_phase);
     }
-    TimedScope ts_(b.ctx, "synth_timebase_kernel");
+    TimedScope ts_(b.ctx, st, "synth_timebase_kernel");
     hipLaunchKernelGGL(synth_timebase_kernel, dim3(part.n), dim3(64), 0, st, part.d_list, b.d_y_off, W.d_phase);
   }
   {
-    TimedScope ts_(b.ctx, "synth_search_kernel");
+    TimedScope ts_(b.ctx, st, "synth_search_kernel");
     const int tiles_max = (b.max_y_len + kSearchTile - 1) / kSearchTile + 1;        // the row length of the tile counts
     const int tiles_part = (part.max_y_len + kSearchTile - 1) / kSearchTile + 1;
     hipLaunchKernelGGL(synth_pulse_search_kernel<false>, dim3(tiles_part, part.n), dim3(256), 0, st, part.d_list,
@@ -1070,19 +1071,18 @@ static int synthesis_prepare_launch(Batch& b, const SynPart& part, const double*
   // transfer another stream has in flight (a 1 GB feature download held this synchronisation, and with it the
   // whole step, for 20 ms).
   hipLaunchKernelGGL(synth_pulse_off_kernel, dim3(1), dim3(256), 0, st, part.d_list, (const int*)W.d_pulse_cnt, part.n,
-                     part.p_base, W.d_pulse_off, c.d_pulse_info);
+                     part.p_base, W.d_pulse_off, c.pulse->d);
   return wm_check(hipGetLastError());
 }
 
 // After the host round trip: the part's totals are known.  `in_flight`: kernels of an earlier part may be using the
 // pulse records and the response scratch, which therefore must not move.
-static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more, bool in_flight) {
+static int synthesis_prepare_finish(Batch& b, hipStream_t st, SynPart& part, int64_t expect_more, bool in_flight) {
   Context& c = *b.ctx;
   SynWs& W = syn_ws(b);
-  hipStream_t st = c.stream;
   const int F = b.p.fft_size;
-  part.total_p = c.h_pulse_info[0];
-  part.max_np = (int)c.h_pulse_info[1];
+  part.total_p = c.pulse->h[0];
+  part.max_np = (int)c.pulse->h[1];
   if (part.total_p == 0) return WM_OK;
   // The responses of a piece of the pulse list wait in scratch memory for the overlap-add.  The scratch holds two
   // pieces: while one is added into y on the second stream the pulse kernel fills the other (synthesis_render).
@@ -1107,7 +1107,7 @@ static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more
   } else {
     // one half only when this part is the whole call AND fits one piece: a later part (expect_more > 0) starts at
     // whatever piece parity the earlier one ended on, so the split path always lays out both halves
-    rc = c.ensure_scratch((chunk < list || expect_more > 0 ? 2 : 1) * chunk * F);
+    rc = c.ensure_scratch((chunk < list || expect_more > 0 ? 2 : 1) * chunk * F, st);
     if (rc) return rc;
     W.chunk = chunk;
   }
@@ -1148,19 +1148,19 @@ static int synthesis_prepare_finish(Batch& b, SynPart& part, int64_t expect_more
   return wm_check(hipGetLastError());
 }
 
-// The pulses [part.p_base, part.p_base + part.total_p): responses by the pulse kernel on the caller's stream, added
-// into y on the second stream.  `piece` counts the pieces of the whole call (the halves of the scratch alternate
+// The pulses [part.p_base, part.p_base + part.total_p): responses by the pulse kernel on `st`, added into y on the
+// second stream.  `piece` counts the pieces of the whole call (the halves of the scratch alternate
 // across parts).
-static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_sp, const double* d_ap, double* d_y,
-                                 int& piece) {
+static int synthesis_render_part(Batch& b, hipStream_t st, const SynPart& part, const double* d_sp, const double* d_ap,
+                                 double* d_y, int& piece) {
   Context& c = *b.ctx;
+  const SideStreams& s = *c.fork;
   SynWs& W = syn_ws(b);
-  hipStream_t st = c.stream;
   const int F = b.p.fft_size, fs = b.p.fs;
   const double fp = b.p.frame_period / 1000.0;
   const int64_t chunk = W.chunk;
   const int ola_tiles = (part.max_y_len + kOlaSeg * kOlaWaves - 1) / (kOlaSeg * kOlaWaves);
-  // Piece k: pulse kernel on the caller's stream into half k & 1 of the scratch, overlap-add on the second stream.
+  // Piece k: pulse kernel on `st` into half k & 1 of the scratch, overlap-add on the second stream.
   // The overlap-adds run in list order on one stream, so every sample is summed in the order of one piece per launch
   // whatever the timing; the pulse kernel of piece k + 2 waits for the overlap-add of piece k to release its half.
   int rc = WM_OK;
@@ -1171,7 +1171,7 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
     const int h = piece & 1;
     double* resp = c.d_scratch + (int64_t)h * chunk * F;
     const int grid = (int)(np < (int64_t)c.frame_grid ? np : (int64_t)c.frame_grid);
-    if (piece >= 2) rc = wm_check(hipStreamWaitEvent(st, c.ev_ola[h], 0));
+    if (piece >= 2) rc = wm_check(hipStreamWaitEvent(st, s.ev_ola[h], 0));
     if (rc) break;
 #define WM_SY_CASE(FF, KERNEL)                                                                                  \
   case FF: {                                                                                                    \
@@ -1181,7 +1181,7 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
                        (const int*)W.d_pulse_perm + p0, resp);                                                  \
   } break;
     {
-      TimedScope ts_(b.ctx, "synth_pulse_kernel");
+      TimedScope ts_(b.ctx, st, "synth_pulse_kernel");
       // fft 2048 (two waves per SIMD): spectra by pairs in registers (synth_pulse_bp.hpp)
       switch (F) {
         WM_SY_CASE(512, synth_pulse_kernel)
@@ -1191,97 +1191,86 @@ static int synthesis_render_part(Batch& b, const SynPart& part, const double* d_
       }
     }
 #undef WM_SY_CASE
-    hipStream_t so = c.side;
-    rc = wm_check(hipEventRecord(c.ev_pulse[h], st));
-    rc = rc ? rc : wm_check(hipStreamWaitEvent(so, c.ev_pulse[h], 0));
+    hipStream_t so = s.side;
+    rc = wm_check(hipEventRecord(s.ev_pulse[h], st));
+    rc = rc ? rc : wm_check(hipStreamWaitEvent(so, s.ev_pulse[h], 0));
     if (rc) break;
     {
-      c.stream = so;                                       // the timing bracket records on the context's stream
-      TimedScope ts2_(b.ctx, "synth_ola_kernel");
+      TimedScope ts2_(b.ctx, so, "synth_ola_kernel");
       hipLaunchKernelGGL(synth_ola_kernel, dim3(ola_tiles, part.n), dim3(64 * kOlaWaves), 0, so, part.d_list, b.d_y_off,
                          W.d_pulse_off, (const int*)W.d_pulse_cnt, W.d_pulse_idx, (const int*)W.d_pulse_first, F, p0,
                          p1, resp, d_y);
     }
-    c.stream = st;
-    rc = wm_check(hipEventRecord(c.ev_ola[h], so));
+    rc = wm_check(hipEventRecord(s.ev_ola[h], so));
   }
-  c.stream = st;
   return rc ? rc : wm_check(hipGetLastError());
 }
 
 // y is complete, and both halves of the scratch are free again, when the last overlap-add is: everything after the
-// call on the caller's stream is ordered behind it
-static int synthesis_join(Batch& b, int pieces) {
-  Context& c = *b.ctx;
+// call on its stream `st` is ordered behind it
+static int synthesis_join(Batch& b, hipStream_t st, int pieces) {
   if (pieces == 0) return WM_OK;
-  return wm_check(hipStreamWaitEvent(c.stream, c.ev_ola[(pieces - 1) & 1], 0));
+  return wm_check(hipStreamWaitEvent(st, b.ctx->fork->ev_ola[(pieces - 1) & 1], 0));
+}
+
+// What every form starts with: the randn table, the batch's work arrays, y cleared
+static int synthesis_setup(Batch& b, hipStream_t st, double* d_y) {
+  const int F = b.p.fft_size;
+  if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
+  int rc = b.ctx->ensure_rng(b.rng_bound_synthesis(), st);
+  rc = rc ? rc : synthesis_arena(b, st);
+  return rc ? rc : wm_check(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)b.total_y, st));
 }
 
 // ---- the whole batch as one part (launch_analyze_synthesize: prepare on a side stream, render on the main one) ----
 // synthesis_begin() queues the f0-only kernels and returns; synthesis_prepare_wait() is the host round trip behind
 // them.  Between the two the host is free: the drop-in Synthesis() gathers the caller's `double**` rows of sp / ap
 // into pinned memory there, i.e. while the phase chain of the utterance runs (capi.cpp).
-int synthesis_begin(Batch& b, const double* d_f0, double* d_y) {
-  Context& c = *b.ctx;
-  const int F = b.p.fft_size;
-  if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
-  int rc = c.ensure_rng(b.rng_bound_synthesis());
-  rc = rc ? rc : synthesis_arena(b);
-  rc = rc ? rc : wm_check(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)b.total_y, c.stream));
+int synthesis_begin(Batch& b, hipStream_t st, const double* d_f0, double* d_y) {
+  const int rc = synthesis_setup(b, st, d_y);
   if (rc) return rc;
   SynPart part{syn_ws(b).d_order, b.n_utt, b.max_y_len, 0};
-  return synthesis_prepare_launch(b, part, d_f0);
+  return synthesis_prepare_launch(b, st, part, d_f0);
 }
-int synthesis_prepare_wait(Batch& b) {
-  Context& c = *b.ctx;
+int synthesis_prepare_wait(Batch& b, hipStream_t st) {
   SynWs& W = syn_ws(b);
   SynPart part{W.d_order, b.n_utt, b.max_y_len, 0};
-  int rc = wm_check(hipStreamSynchronize(c.stream));            // the one host round trip of the path
+  int rc = wm_check(hipStreamSynchronize(st));                  // the one host round trip of the path
   W.chunk = 0;
-  rc = rc ? rc : synthesis_prepare_finish(b, part, 0, false);
+  rc = rc ? rc : synthesis_prepare_finish(b, st, part, 0, false);
   W.total_p = part.total_p;
   return rc;
 }
-int synthesis_prepare(Batch& b, const double* d_f0, double* d_y) {
-  int rc = synthesis_begin(b, d_f0, d_y);
-  return rc ? rc : synthesis_prepare_wait(b);
+int synthesis_prepare(Batch& b, hipStream_t st, const double* d_f0, double* d_y) {
+  int rc = synthesis_begin(b, st, d_f0, d_y);
+  return rc ? rc : synthesis_prepare_wait(b, st);
 }
 
-int synthesis_render(Batch& b, const double* d_sp, const double* d_ap, double* d_y) {
+int synthesis_render(Batch& b, hipStream_t st, const double* d_sp, const double* d_ap, double* d_y) {
   const SynWs& W = syn_ws(b);
   if (W.total_p == 0) return WM_OK;
   SynPart part{W.d_order, b.n_utt, b.max_y_len, 0};
   part.total_p = W.total_p;
   int piece = 0;
-  int rc = synthesis_render_part(b, part, d_sp, d_ap, d_y, piece);
-  return rc ? rc : synthesis_join(b, piece);
+  int rc = synthesis_render_part(b, st, part, d_sp, d_ap, d_y, piece);
+  return rc ? rc : synthesis_join(b, st, piece);
 }
 
 // ---- Synthesis alone: the batch in two parts (see the top of this section) ----
 int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y) {
   Context& c = *b.ctx;
+  const hipStream_t st = c.stream;
   // worth it from a few hundred thousand output samples per part on: below, the parts do not fill the machine
   if (b.n_utt < 16 || b.total_y < (int64_t)4 << 20) {
-    int rc = synthesis_prepare(b, d_f0, d_y);
-    return rc ? rc : synthesis_render(b, d_sp, d_ap, d_y);
+    int rc = synthesis_prepare(b, st, d_f0, d_y);
+    return rc ? rc : synthesis_render(b, st, d_sp, d_ap, d_y);
   }
-  const int F = b.p.fft_size;
-  if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
-  int rc = c.ensure_rng(b.rng_bound_synthesis());
-  rc = rc ? rc : synthesis_arena(b);
+  int rc = synthesis_setup(b, st, d_y);
   rc = rc ? rc : c.ensure_side();
-  if (!rc && !c.prep) {
-    // the highest priority there is: its workgroups are few and latency-bound, and they only get the slots the
-    // pulse kernel's workgroups leave as they retire
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    rc = wm_check(hipStreamCreateWithPriority(&c.prep, hipStreamNonBlocking, prio_hi));
-    rc = rc ? rc : wm_check(hipEventCreateWithFlags(&c.ev_call, hipEventDisableTiming));
-    rc = rc ? rc : wm_check(hipEventCreateWithFlags(&c.ev_prep_b, hipEventDisableTiming));
-  }
+  rc = rc ? rc : c.ensure_split();
   if (rc) return rc;
   SynWs& W = syn_ws(b);
-  hipStream_t st = c.stream;
+  const SplitStreams& s = *c.split;
   // part A: the shortest utterances up to a third of the output samples (profiles/r04_syn_split_sweep.txt)
   int n_a = 0;
   int64_t acc = 0;
@@ -1289,33 +1278,29 @@ int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const dou
   const int* sorted = W.d_order + b.n_utt;
   SynPart pa{sorted, n_a, b.y_len[(size_t)W.sorted[(size_t)n_a - 1]], 0};
   SynPart pb{sorted + n_a, b.n_utt - n_a, b.max_y_len, 0};
-  rc = wm_check(hipMemsetAsync(d_y, 0, sizeof(double) * (size_t)b.total_y, st));
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_call, st));          // the caller's f0 is ready from here on
-  rc = rc ? rc : synthesis_prepare_launch(b, pa, d_f0);
+  rc = wm_check(hipEventRecord(s.ev_call, st));                    // the caller's f0 is ready from here on
+  rc = rc ? rc : synthesis_prepare_launch(b, st, pa, d_f0);
   rc = rc ? rc : wm_check(hipStreamSynchronize(st));               // host round trip of part A
   if (rc) return rc;
   W.chunk = 0;
-  const int64_t guess_b = (int64_t)((double)c.h_pulse_info[0] * (double)(b.total_y - acc) / (double)(acc > 0 ? acc : 1) * 1.25) + 1024;
-  rc = synthesis_prepare_finish(b, pa, guess_b, false);
+  const int64_t guess_b = (int64_t)((double)c.pulse->h[0] * (double)(b.total_y - acc) / (double)(acc > 0 ? acc : 1) * 1.25) + 1024;
+  rc = synthesis_prepare_finish(b, st, pa, guess_b, false);
   if (rc) return rc;
   // part B's f0-only kernels on the third stream, beside part A's render stage
   pb.p_base = pa.total_p;
-  rc = wm_check(hipStreamWaitEvent(c.prep, c.ev_call, 0));
-  c.stream = c.prep;
-  rc = rc ? rc : synthesis_prepare_launch(b, pb, d_f0);
-  c.stream = st;
+  rc = wm_check(hipStreamWaitEvent(s.prep, s.ev_call, 0));
+  rc = rc ? rc : synthesis_prepare_launch(b, s.prep, pb, d_f0);
   int piece = 0;
-  if (!rc && pa.total_p > 0) rc = synthesis_render_part(b, pa, d_sp, d_ap, d_y, piece);
-  rc = rc ? rc : wm_check(hipStreamSynchronize(c.prep));           // host round trip of part B (A's render is queued)
+  if (!rc && pa.total_p > 0) rc = synthesis_render_part(b, st, pa, d_sp, d_ap, d_y, piece);
+  rc = rc ? rc : wm_check(hipStreamSynchronize(s.prep));           // host round trip of part B (A's render is queued)
   if (rc) return rc;
-  c.stream = c.prep;
-  rc = synthesis_prepare_finish(b, pb, 0, pa.total_p > 0);
-  rc = rc ? rc : wm_check(hipEventRecord(c.ev_prep_b, c.prep));
-  c.stream = st;
-  rc = rc ? rc : wm_check(hipStreamWaitEvent(st, c.ev_prep_b, 0));
-  if (!rc && pb.total_p > 0) rc = synthesis_render_part(b, pb, d_sp, d_ap, d_y, piece);
+  // (should B be the first part with pulses, its scratch is sized behind a wait for `prep` alone: nothing renders yet)
+  rc = synthesis_prepare_finish(b, s.prep, pb, 0, pa.total_p > 0);
+  rc = rc ? rc : wm_check(hipEventRecord(s.ev_prep_b, s.prep));
+  rc = rc ? rc : wm_check(hipStreamWaitEvent(st, s.ev_prep_b, 0));
+  if (!rc && pb.total_p > 0) rc = synthesis_render_part(b, st, pb, d_sp, d_ap, d_y, piece);
   W.total_p = pa.total_p + pb.total_p;
-  return rc ? rc : synthesis_join(b, piece);
+  return rc ? rc : synthesis_join(b, st, piece);
 }
 
 #ifdef WM_PHASE

@@ -318,7 +318,7 @@ int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const i
   up((void**)&d_sp, seg_pitch, sizeof(double) * (size_t)nseg);
   if (!rc) rc = wm_check(hipMemsetAsync(W.d_too_long, 0, sizeof(int), st));
   if (!rc) {
-    TimedScope ts_(b.ctx, "vibrato_kernels");
+    TimedScope ts_(b.ctx, st, "vibrato_kernels");
     hipLaunchKernelGGL(vib_scan_kernel, dim3(b.n_utt), dim3(64), 0, st, d_lf0, b.d_f_off, d_soff, d_ss, d_se, d_sp,
                        W.d_slot_off, W.d_f0hz, W.d_df0, W.d_df02, W.d_runs);
     const int grid = (int)(W.total_slots < (int64_t)b.ctx->num_cu * 2 ? W.total_slots : (int64_t)b.ctx->num_cu * 2);

@@ -74,7 +74,8 @@ void WorldMi355DefaultParams(int fs, double frame_period, WorldMi355Params* p);
 typedef void (*WorldMi355ErrorHandler)(const char* where, int code, const char* message, void* user);
 void WorldMi355SetErrorHandler(WorldMi355ErrorHandler handler, void* user);
 
-/* device < 0: current device.  stream == NULL: the legacy default stream (stream 0). */
+/* device < 0: current device.  stream == NULL: the legacy default stream (stream 0).  A context and the batches on it
+ * are driven by one thread at a time: its randn table, scratch, side streams and events are shared by all its calls. */
 int WorldMi355CreateContext(int device, void* hip_stream, WorldMi355Context** out);
 /* Every batch of a context must be destroyed before the context: a batch uses the context's stream and tables. */
 void WorldMi355DestroyContext(WorldMi355Context* ctx);

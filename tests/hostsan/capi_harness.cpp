@@ -22,6 +22,10 @@
 
 extern "C" long HipStubMallocs();
 extern "C" long HipStubLaunches();
+extern "C" long HipStubCreations();
+extern "C" long HipStubDevPtrs();
+extern "C" void HipStubNextPulses(long index);
+extern "C" void HipStubTraceMark(const char* text);
 
 static int g_handler_calls = 0;
 static void on_error(const char* where, int code, const char* message, void* user) {
@@ -104,7 +108,99 @@ static int one_utterance(int fs, double seconds, double frame_period, int fft_ov
   return 0;
 }
 
-int main() {
+// `capi_harness batched`: the multi-stream paths of the batched API on one context, for the stub's call trace
+// (HIP_STUB_TRACE) and its injected creation failures.  Every step is marked in the trace; a step that fails is made
+// once more and must then succeed (a failed set-up leaves nothing behind).  "Device" buffers are host vectors; sp / ap
+// of the large batch are never read by the host layer and get no backing.  HIP_STUB_PULSES gives Synthesis pulses to
+// render: `pulses` is the entry that a step's first launch of the counting kernel reports (a repeated step reports the same).
+static int g_steps_failed = 0;
+template <class Call> static bool step(const char* name, int pulses, Call call) {
+  for (int attempt = 1; attempt <= 2; ++attempt) {
+    HipStubNextPulses(pulses);
+    char mark[96];
+    snprintf(mark, sizeof(mark), "step %s attempt %d", name, attempt);
+    HipStubTraceMark(mark);
+    const int rc = call();
+    printf("%s: rc %d\n", mark, rc);
+    if (rc == 0) return true;
+    ++g_steps_failed;
+  }
+  return false;
+}
+static int batched_sequence() {
+  int last_code = 0;
+  WorldMi355SetErrorHandler(on_error, &last_code);
+  const int fs = 16000, F = 1024, bins = F / 2 + 1;
+  WorldMi355Params p;
+  WorldMi355DefaultParams(fs, 5.0, &p);
+  WorldMi355Context* ctx = nullptr;
+  if (WorldMi355CreateContext(-1, nullptr, &ctx) != 0 || !ctx) return 20;
+  // the large batch: the split form of Synthesis wants 16 utterances and 4 Mi output samples (launch_synthesis)
+  const int lens[3] = {9000, 16000, 4321}, small_f[2] = {200, 300};
+  int big_f[16], big_y[16];
+  int64_t big_tf = 0, big_ty = 0;
+  for (int u = 0; u < 16; ++u) {
+    big_y[u] = (1 << 18) + 4000 * ((u * 7) % 16);                         // not in order of length
+    big_f[u] = (big_y[u] - 1) / 80 + 1;
+    big_tf += big_f[u];
+    big_ty += big_y[u];
+  }
+  if (big_ty < ((int64_t)4 << 20)) return 21;
+  for (int round = 0; round < 2; ++round) {
+    if (round == 1 && WorldMi355TimingEnable(ctx, 1) != 0) return 22;    // the streams TimedScope records on
+    // the drop-in Synthesis(): its own context, its upload stream
+    {
+      const int T = 120, ylen = (T - 1) * 80 + 1;
+      std::vector<double> f0((size_t)T, 120.0), y((size_t)ylen, NAN);
+      Rows sp(T, bins), ap(T, bins);
+      for (auto r : sp.p) for (int j = 0; j < bins; ++j) r[j] = 1.0;
+      for (auto r : ap.p) for (int j = 0; j < bins; ++j) r[j] = 0.5;
+      if (!step("drop-in Synthesis", 0, [&] {
+            const int before = g_handler_calls;
+            Synthesis(f0.data(), T, sp.p.data(), ap.p.data(), F, 5.0, fs, ylen, y.data());
+            return g_handler_calls == before ? 0 : last_code;
+          })) return 23;
+    }
+    WorldMi355Batch *b = nullptr, *bs = nullptr, *bb = nullptr;
+    if (WorldMi355CreateBatch(ctx, &p, 3, lens, nullptr, nullptr, &b) != 0) return 24;
+    if (WorldMi355CreateBatch(ctx, &p, 2, nullptr, small_f, nullptr, &bs) != 0) return 25;
+    if (WorldMi355CreateBatch(ctx, &p, 16, nullptr, big_f, big_y, &bb) != 0) return 26;
+    if (WorldMi355BatchFftSize(b) != F || WorldMi355BatchTotalOutputSamples(bb) != big_ty) return 27;
+    const size_t tf = (size_t)WorldMi355BatchTotalFrames(b), tfs = (size_t)WorldMi355BatchTotalFrames(bs);
+    std::vector<double> x((size_t)WorldMi355BatchTotalSamples(b), 0.1), t(tf), f0(tf), sp(tf * bins), ap(tf * bins);
+    std::vector<double> y((size_t)WorldMi355BatchTotalOutputSamples(b));
+    std::vector<double> f0s(tfs, 150.0), sps(tfs * bins, 1.0), aps(tfs * bins, 0.5);
+    std::vector<double> ys((size_t)WorldMi355BatchTotalOutputSamples(bs)), f0b((size_t)big_tf, 110.0), yb((size_t)big_ty);
+    const double* no_backing = f0b.data();                                  // sp / ap of the large batch: never read
+    bool ok = step("Analyze 1", 0, [&] { return WorldMi355Analyze(b, x.data(), t.data(), f0.data(), sp.data(), ap.data()); });
+    ok = ok && step("Analyze 2 (D4C's preparation beside CheapTrick)", 0,
+                    [&] { return WorldMi355Analyze(b, x.data(), t.data(), f0.data(), sp.data(), ap.data()); });
+    ok = ok && step("AnalyzeSynthesize 1", 1, [&] {
+           return WorldMi355AnalyzeSynthesize(b, x.data(), t.data(), f0.data(), sp.data(), ap.data(), y.data());
+         });
+    ok = ok && step("AnalyzeSynthesize 2 (warm, overlapped)", 2, [&] {
+           return WorldMi355AnalyzeSynthesize(b, x.data(), t.data(), f0.data(), sp.data(), ap.data(), y.data());
+         });
+    ok = ok && step("Synthesis in one part", 3, [&] { return WorldMi355Synthesis(bs, f0s.data(), sps.data(), aps.data(), ys.data()); });
+    ok = ok && step("Synthesis in two parts", 4, [&] { return WorldMi355Synthesis(bb, f0b.data(), no_backing, no_backing, yb.data()); });
+    HipStubTraceMark("end of round");
+    if (!ok || WorldMi355Synchronize(ctx) != 0) return 28;
+    WorldMi355DestroyBatch(b);
+    WorldMi355DestroyBatch(bs);
+    WorldMi355DestroyBatch(bb);
+  }
+  double ms = 0.0;
+  int launches = 0;
+  if (WorldMi355TimingQuery(ctx, "synth_ola_kernel", &ms, &launches) != 0 || launches == 0) return 29;
+  WorldMi355DestroyContext(ctx);
+  WorldMi355SetErrorHandler(nullptr, nullptr);
+  printf("capi batched ok: %d failed steps, %ld creations, %ld device pointers, %ld launches\n", g_steps_failed,
+         HipStubCreations(), HipStubDevPtrs(), HipStubLaunches());
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "batched") == 0) return batched_sequence();
   int last_code = 0;
   if (getenv("HIP_STUB_DEVICES") && atoi(getenv("HIP_STUB_DEVICES")) == 0) {
     // no device: the drop-in entry points report to the handler and return (reference entry points are void)

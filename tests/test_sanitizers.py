@@ -2,7 +2,9 @@
 none; `make -C oracle asan`).  The golden-vector and primitive suites are re-run in a child interpreter with the
 sanitizer runtimes preloaded and ORACLE_LIB pointing at the instrumented build; any report fails the run.
 CPU only: the GPU pool offers no sanitizers."""
+import collections
 import os
+import re
 import subprocess
 import sys
 
@@ -63,7 +65,19 @@ def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
     calls WORLD's C ABI like the reference CLIs: `double**` rows allocated one by one at their exact size, ten
     utterance shapes (8 ... 48 kHz, 1 / 5 / 10 ms, non-default fft sizes, Harvest, 7 frames), the codec entry points,
     refused arguments through the error handler, a box without a device, and device-allocation failures injected at a
-    dozen points of the run (every one must reach the handler; nothing may leak or touch freed memory)."""
+    dozen points of the run (every one must reach the handler; nothing may leak or touch freed memory).
+
+    `capi_harness batched` drives the multi-stream paths of the batched API on one context (Analyze beside CheapTrick,
+    AnalyzeSynthesize cold and overlapped, Synthesis in one part and in two, the drop-in Synthesis with its upload
+    stream; all of it again with timing on) while the stub writes every call that carries a stream or an event to a
+    trace.  The trace must equal tests/golden/host_call_trace.txt line for line, up to a one-to-one renaming of streams
+    and events: that file was recorded from the library as it was BEFORE launchers took their stream as an argument,
+    so a call that moves to another stream or another place fails here (whoever changes launches on purpose records it
+    anew: HIP_STUB_TRACE=tests/golden/host_call_trace.txt HIP_STUB_PULSES=... capi_harness batched).  Then every
+    creation of a stream, an event or the mapped pulse counters fails once, in turn: the call it fails in returns an
+    error, the same call made again succeeds and queues what an undisturbed call queues -- less only what the failed
+    attempt had already queued for set-ups that are made once (a table, a work arena) -- and everything after it is
+    unchanged."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     rt = [p for p in ("/opt/rocm/lib/llvm/lib/clang",) if os.path.isdir(p)]
     if not os.path.exists(hipcc) or not rt:
@@ -89,3 +103,65 @@ def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
     assert "capi no-device ok" in run(HIP_STUB_DEVICES="0")
     for n in (0, 1, 3, 8, 21, 34, 55, 89, 120):
         assert "handler:" in run(HIP_STUB_FAIL_MALLOC_AFTER=str(n))
+
+    # pulse totals : per-utterance maxima of the six counting launches of a round: lists rendered in one piece (below
+    # 2 x 16384 pulses, synthesis_prepare_finish) and in two, and a second part that outgrows the first one's records
+    pulses = "1000:50,1000:50,40000:300,33000:200,20000:100,90000:400"
+    trace_file = tmp_path / "trace.txt"
+
+    def canonical(lines):                   # streams and events renamed in order of first appearance
+        names = {}
+
+        def rename(m):
+            return names.setdefault(m.group(0), m.group(0)[0] + str(sum(1 for k in names if k[0] == m.group(0)[0])))
+        return [re.sub(r"(?<= )[se]\d+\b", rename, line) for line in lines]
+
+    def batched(**extra):
+        p = subprocess.run([str(exe), "batched"], capture_output=True, text=True, timeout=300,
+                           env=dict(env, HIP_STUB_TRACE=str(trace_file), HIP_STUB_PULSES=pulses, **extra))
+        text = p.stdout + p.stderr
+        assert p.returncode == 0 and "capi batched ok" in text, text[-4000:]
+        assert "AddressSanitizer" not in text and "LeakSanitizer" not in text and "runtime error" not in text, text[-4000:]
+        segments = []                       # [marker line, its calls]
+        for line in trace_file.read_text().splitlines():
+            if line.startswith("#"):
+                segments.append([line, []])
+            else:
+                segments[-1][1].append(line)
+        return text, segments
+
+    text, plain = batched()
+    assert "capi batched ok: 0 failed steps" in text
+    flat = [line for mark, calls in plain for line in [mark] + calls]
+    golden = open(os.path.join(ROOT, "tests", "golden", "host_call_trace.txt")).read().splitlines()
+    print("host call trace: %d lines, %d of them calls" % (len(flat), sum(1 for line in flat if line[0] != "#")))
+    assert canonical(flat) == canonical(golden)
+    # both forms of the render stage are in it: a third piece waits for the overlap-add of the first
+    assert any("hipDeviceSynchronize" in line for line in flat) and any("synth_ola_kernel" in line for line in flat)
+    n_create = int(re.search(r"(\d+) creations", text).group(1))
+    n_devptr = int(re.search(r"(\d+) device pointers", text).group(1))
+    assert n_create == 2 * 10 + 3 + 2 and n_devptr == 2      # two contexts' side streams, the split's, the upload's
+
+    def strip(line):
+        return re.sub(r" [se]\d+\b", "", line)
+
+    for var, count in (("HIP_STUB_FAIL_CREATE_AT", n_create), ("HIP_STUB_FAIL_DEVPTR_AT", n_devptr)):
+        for k in range(count):
+            text, segs = batched(**{var: str(k)})
+            assert "capi batched ok: 1 failed steps" in text, (var, k, text[-2000:])
+            failed = [i for i, (mark, calls) in enumerate(segs) if mark.endswith("attempt 2")]
+            assert len(failed) == 1 and segs[failed[0] - 1][0].endswith("attempt 1"), (var, k)
+            first_try = segs.pop(failed[0] - 1)
+            retried = failed[0] - 1
+            assert [mark.replace("attempt 2", "attempt 1") for mark, _ in segs] == [mark for mark, _ in plain]
+            want = canonical([line for _, calls in plain for line in calls])
+            got = canonical([line for _, calls in segs for line in calls])
+            if got != want:
+                # only the retried call may differ, and only by lacking calls that its first attempt had made
+                at = sum(len(calls) for _, calls in plain[:retried])
+                n_want, n_got = len(plain[retried][1]), len(segs[retried][1])
+                assert got[:at] == want[:at] and got[at + n_got:] == want[at + n_want:], (var, k)
+                it = iter(want[at:at + n_want])
+                assert all(line in it for line in got[at:at + n_got]), (var, k)         # a subsequence, in order
+                missing = collections.Counter(map(strip, want[at:at + n_want])) - collections.Counter(map(strip, got[at:at + n_got]))
+                assert not missing - collections.Counter(map(strip, first_try[1])), (var, k, missing)
