@@ -170,14 +170,18 @@ __global__ __launch_bounds__(64) void synth_timebase_kernel(const int* __restric
 }
 
 // wrap = fmod(total, 2 pi) (synthesis.cpp:249, :253): the remainder is exactly representable, so one
-// fused multiply-add from the unrounded total gives it once k is right
+// fused multiply-add from the unrounded total gives it once k is right.  fmod keeps the sign of its dividend, and the
+// total does turn negative: past the last frame the contour is extrapolated (the knot 2 f0[nf-1] - f0[nf-2]), after a
+// fall to negative f0, and a y_length far enough beyond the frames runs the phase back through zero.  The time shift
+// of a pulse (wrap[i] - 2 pi against wrap[i+1]) depends on which side of zero the remainder lies.
 __device__ __forceinline__ double wrap_two_pi(double t) {
   const double two_pi = 2.0 * kPi;
-  double kq = floor(t * (1.0 / two_pi));
-  double w = __fma_rn(-kq, two_pi, t);
-  if (w < 0.0) { kq -= 1.0; w = __fma_rn(-kq, two_pi, t); }
-  if (w >= two_pi) { kq += 1.0; w = __fma_rn(-kq, two_pi, t); }
-  return w;
+  const double a = fabs(t);
+  double kq = floor(a * (1.0 / two_pi));
+  double w = __fma_rn(-kq, two_pi, a);
+  if (w < 0.0) { kq -= 1.0; w = __fma_rn(-kq, two_pi, a); }
+  if (w >= two_pi) { kq += 1.0; w = __fma_rn(-kq, two_pi, a); }
+  return copysign(w, t);
 }
 
 // Part 3 (synthesis.cpp:253-285): pulses where the wrapped phase jumps by more than pi, compacted in order.
