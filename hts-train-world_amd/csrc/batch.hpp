@@ -285,5 +285,8 @@ int launch_recipe_features(Batch& b, const double* d_f0, const double* d_sp, con
                            int ap_dim, float* d_lf0, float* d_mgc, float* d_bap);
 int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const float* d_bap, int spec_dim,
                          int ap_dim, double* d_f0, double* d_sp, double* d_ap);
+int check_mel_cepstrum(const Batch& b, const double* d_spec, const WorldMi355McepOption& opt, const double* d_mc);
+int launch_mel_cepstrum(Batch& b, hipStream_t st, const double* d_spec, const WorldMi355McepOption& opt, double* d_mc,
+                        int* d_status);
 
 }  // namespace wm

@@ -295,6 +295,25 @@ int WorldMi355RecipeDecode(WorldMi355Batch* b, const float* lf0, const float* mg
   OnDevice dev_(b->b.ctx[0]);
   return launch_recipe_decode(b->b, lf0, mgc, bap, spec_dim, ap_dim, f0, sp, ap);
 }
+void WorldMi355DefaultMcepOption(WorldMi355McepOption* o) {                     // SPTK's mcep / mgcep defaults
+  if (!o) return;
+  o->alpha = 0.35;
+  o->order = 25;
+  o->itr1 = 2;
+  o->itr2 = 30;
+  o->dd = 1e-3;
+  o->etype = 0;
+  o->e = 0.0;
+  o->f = 1e-6;
+  o->itype = 3;
+}
+int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const WorldMi355McepOption* opt, double* mc,
+                          int* status) {
+  if (!b || !opt) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mel_cepstrum(b->b, spectrum, *opt, mc)) return rc;   // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mel_cepstrum(b->b, b->b.ctx->stream, spectrum, *opt, mc, status);
+}
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {

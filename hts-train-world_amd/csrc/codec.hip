@@ -25,6 +25,7 @@
 #include "common.hpp"
 #include "fastmath.hpp"
 #include "fft.hpp"
+#include "freqt.hpp"
 #include "window.hpp"
 
 namespace wm {
@@ -503,42 +504,8 @@ __global__ __launch_bounds__(64) void codec_bap_decode_kernel(const float* __res
     double cin = 0.0;
     if (live && ci >= 0 && ci < ap_dim) cin = (double)bap[frame * (int64_t)ap_dim + ci];
     if (ci == 0) cin += 9.210340;                              // synth.cpp:241
-    double last = 0.0, prev_up = 0.0, own_prev = 0.0;
-    const bool store_lane = live && s == order;
-    // start-up: until step order + 1 some row is still at its first (j = 0) or second (j = 1) element, which
-    // have their own expressions (:620-623)
-    for (int t = 0; t <= order + 1; ++t) {
-      double up = dpp_get<0x138, 0xf, 0xf>(last);              // wave_shr:1 -- lane s reads lane s-1, lane 0 reads 0
-      if (W < 64 && s == 0) up = 0.0;                          // g_{-1} = 0 between two packed frames too
-      const int j = t - s;
-      const double B = up - (j >= 2 ? own_prev : 0.0);
-      const double A = j == 0 ? cin : prev_up * (j == 1 ? b : 1.0);
-      const double val = A + a * B;
-      // a row that has not started (j < 0) computes values nobody reads: its right neighbour is one step
-      // behind it, and j = 0 takes nothing from the row's own state
-      prev_up = up;
-      own_prev = val;
-      last = val;
-      if (store_lane && j >= 0) c[j] = val;
-    }
-    // steady state: every row is at j >= 2, the general element g[j] = d[j-1] + a (d[j] - g[j-1]) (:624-625).
-    // A row that is finished (j > h) again computes values nobody reads.  Every lane stores every step -- the
-    // row that carries the result into the cepstrum, the others into a slot of their own -- so the loop has
-    // no exec-mask branch.
-    {
-      double* dst = store_lane ? c + 2 : c_all + sub * kC + (h + 2) + s;
-      const int adv = store_lane ? 1 : 0;
-      for (int t = order + 2; t <= h + order; ++t) {
-        double up = dpp_get<0x138, 0xf, 0xf>(last);
-        if (W < 64 && s == 0) up = 0.0;
-        const double val = prev_up + a * (up - own_prev);
-        prev_up = up;
-        own_prev = val;
-        last = val;
-        *dst = val;
-        dst += adv;
-      }
-    }
+    // the systolic recurrence itself is shared with the mel-cepstral analysis (freqt.hpp)
+    freqt_expand<W>(cin, s, order, h, a, b, live && s == order, c, c_all + sub * kC + (h + 2) + s);
     wave_sync();
     if (live && s == 0) c[0] = log(exp(c[0]));
     wave_sync();
@@ -698,3 +665,10 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 }
 
 }  // namespace wm
+
+// ---- SURVEY.md section 2, row 15, encoder half: SPTK's mcep + theq, the inverse of the bap decoder above ----------
+// mcep.hip is a file of its own but not a unit of its own: tests/hostsan/build_capi_harness.sh lists the library's
+// sources by name and does not change with a feature, so a new unit would leave the host-sanitizer harness with an
+// undefined launch_mel_cepstrum.  Compiled here, every build that lists codec.hip has it.  Its includes are guarded
+// headers this unit already has, and it reopens namespace wm.
+#include "mcep.hip"

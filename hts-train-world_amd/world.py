@@ -33,6 +33,12 @@ class WorldParams(C.Structure):
                 ("d4c_threshold", C.c_double)]
 
 
+class McepOption(C.Structure):
+    """include/world_mi355.h: WorldMi355McepOption (the arguments of SPTK's mcep)."""
+    _fields_ = [("alpha", C.c_double), ("order", C.c_int), ("itr1", C.c_int), ("itr2", C.c_int), ("dd", C.c_double),
+                ("etype", C.c_int), ("e", C.c_double), ("f", C.c_double), ("itype", C.c_int)]
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -86,6 +92,9 @@ def load_library():
     L.WorldMi355DecodeAperiodicity.argtypes = [vp, vp, vp]
     L.WorldMi355RecipeFeatures.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.WorldMi355RecipeDecode.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.WorldMi355DefaultMcepOption.restype = None
+    L.WorldMi355DefaultMcepOption.argtypes = [C.POINTER(McepOption)]
+    L.WorldMi355MelCepstrum.argtypes = [vp, vp, C.POINTER(McepOption), vp, vp]
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
@@ -340,6 +349,30 @@ class WorldBatch:
                                                      C.c_void_p(bap.data_ptr()), mgc.shape[1], bap.shape[1],
                                                      self._p(f0), self._p(sp), self._p(ap)), "RecipeDecode")
         return f0, sp, ap
+
+    def mel_cepstrum(self, spectrum, order=25, alpha=0.35, **opt):
+        """SPTK's mcep per frame (test/sptkfunctions.cpp:11-184 with flng = fft_size): spectrum is float64 cuda
+        [total_frames][fft_size/2+1], amplitudes (itype=3, the default) or periodograms (itype=4).  Further options
+        as WorldMi355McepOption's fields: itr1, itr2, dd, etype, e, f.  Returns (mc float64 [total_frames][order+1],
+        status int32 [total_frames]: 0 converged, -1 itr2 steps without meeting dd, 1 singular pivot in theq,
+        2 a periodogram value <= 0 or non-finite)."""
+        import torch
+        o = McepOption()
+        load_library().WorldMi355DefaultMcepOption(C.byref(o))
+        o.order, o.alpha = int(order), float(alpha)
+        for k, v in opt.items():
+            if k not in ("itr1", "itr2", "dd", "etype", "e", "f", "itype"):
+                raise TypeError(f"mel_cepstrum: unknown option {k!r}")
+            setattr(o, k, v)
+        if (tuple(spectrum.shape) != (self.total_frames, self.bins) or spectrum.dtype != torch.float64
+                or not spectrum.is_cuda or not spectrum.is_contiguous()):
+            raise ValueError(f"mel_cepstrum: spectrum must be a contiguous float64 cuda tensor "
+                             f"[{self.total_frames}][{self.bins}], got {spectrum.dtype} {tuple(spectrum.shape)}")
+        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MelCepstrum(self.handle, self._p(spectrum), C.byref(o), self._p(mc),
+                                                    C.c_void_p(status.data_ptr())), "MelCepstrum")
+        return mc, status
 
     def compose_cmp(self, streams):
         """streams: list of (float32 cuda tensor [total_frames][dim], list of window coefficient lists).

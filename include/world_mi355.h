@@ -171,6 +171,34 @@ int WorldMi355RecipeFeatures(WorldMi355Batch* b, const double* f0, const double*
 int WorldMi355RecipeDecode(WorldMi355Batch* b, const float* lf0, const float* mgc, const float* bap, int spec_dim,
                            int ap_dim, double* f0, double* sp, double* ap);
 
+/* ---- Mel-cepstral analysis of spectra: the CLIs' SPTK port, mcep (test/sptkfunctions.cpp:11-184) with flng = fft_size
+ * and its solver theq (test/theq.cpp:286-357) -- at gamma 0 what `mgcep -a alpha -m order -l fft_size -q itype` computes
+ * from sp / ap (data/Makefile.in:190-206), and what mgc2sp (sptkfunctions.cpp:186-219) inverts.  Fields as mcep's
+ * arguments (:11-13): alpha a, order m, itr1 / itr2 the least / most Newton steps (:142-158), dd the end condition
+ * (:153), etype 0 nothing or 1 `e` added to the periodogram (:31-33; 2, the dB floor of :104-117, is WM_ERR_UNSUPPORTED),
+ * f theq's singularity threshold (theq.cpp:90-104, negative: 1e-6), itype 3 amplitude or 4 periodogram rows (:85-94;
+ * 0 / 1 / 2 are WM_ERR_UNSUPPORTED). */
+typedef struct {
+  double alpha;
+  int order;
+  int itr1, itr2;
+  double dd;
+  int etype;
+  double e;
+  double f;
+  int itype;
+} WorldMi355McepOption;
+/* SPTK's defaults: alpha 0.35, order 25, itr1 2, itr2 30, dd 1e-3, etype 0, e 0, f 1e-6, itype 3. */
+void WorldMi355DefaultMcepOption(WorldMi355McepOption* opt);
+/* spectrum: DEVICE double[total_frames][fft_size/2+1]; mc: DEVICE double[total_frames][order+1];
+ * status: DEVICE int[total_frames] or NULL: 0 converged, -1 ran itr2 steps without meeting dd (mcep's own return,
+ * :179-182), 1 the solver met a singular pivot (the reference exits the process there, :170-173), 2 a periodogram value
+ * <= 0 or non-finite (the reference exits there too, :119-124); rows of status 1 hold the last iterate, rows of
+ * status 2 zeros.  Frames never exchange data.  1 <= order <= 63, 0 <= itr1, 0 <= itr2 <= 1000, |alpha| < 1, else
+ * WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's stream. */
+int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const WorldMi355McepOption* opt, double* mc,
+                          int* status);
+
 /* ---- `cmp` composition (data/scripts/window.pl:45-146, addhtkheader.pl:45-82), SURVEY.md section 8(f) rank 3 ----
  * Applies each stream's dynamic-feature windows and lays the results side by side per frame:
  *   out[frame] = [stream 0: window 0 (dim) | window 1 | ...][stream 1: ...]...      (float32)
