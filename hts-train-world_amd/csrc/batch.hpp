@@ -288,5 +288,8 @@ int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const
 int check_mel_cepstrum(const Batch& b, const double* d_spec, const WorldMi355McepOption& opt, const double* d_mc);
 int launch_mel_cepstrum(Batch& b, hipStream_t st, const double* d_spec, const WorldMi355McepOption& opt, double* d_mc,
                         int* d_status);
+int check_mgc2sp(const Batch& b, const double* d_mc, const WorldMi355Mgc2spOption& opt, const double* d_sp);
+int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355Mgc2spOption& opt, double* d_sp,
+                  double* d_phase, int* d_status);
 
 }  // namespace wm

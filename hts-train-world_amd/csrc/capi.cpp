@@ -314,6 +314,20 @@ int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const Worl
   OnDevice dev_(b->b.ctx[0]);
   return launch_mel_cepstrum(b->b, b->b.ctx->stream, spectrum, *opt, mc, status);
 }
+void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* o) {                 // SPTK's mgc2sp defaults, ln |H| out
+  if (!o) return;
+  o->alpha = 0.35;
+  o->gamma = 0.0;
+  o->order = 25;
+  o->out_format = 0;
+}
+int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const WorldMi355Mgc2spOption* opt,
+                                    double* spectrum, double* phase, int* status) {
+  if (!b || !opt) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mgc2sp(b->b, mc, *opt, spectrum)) return rc;         // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mgc2sp(b->b, b->b.ctx->stream, mc, *opt, spectrum, phase, status);
+}
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {

@@ -672,3 +672,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 // undefined launch_mel_cepstrum.  Compiled here, every build that lists codec.hip has it.  Its includes are guarded
 // headers this unit already has, and it reopens namespace wm.
 #include "mcep.hip"
+// ---- the decoder half: SPTK's mgc2sp at any gamma, every bin, in double (the same arrangement) ----------------------
+#include "mgc2sp.hip"

@@ -39,6 +39,11 @@ class McepOption(C.Structure):
                 ("etype", C.c_int), ("e", C.c_double), ("f", C.c_double), ("itype", C.c_int)]
 
 
+class Mgc2spOption(C.Structure):
+    """include/world_mi355.h: WorldMi355Mgc2spOption (the arguments of SPTK's mgc2sp)."""
+    _fields_ = [("alpha", C.c_double), ("gamma", C.c_double), ("order", C.c_int), ("out_format", C.c_int)]
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -95,6 +100,9 @@ def load_library():
     L.WorldMi355DefaultMcepOption.restype = None
     L.WorldMi355DefaultMcepOption.argtypes = [C.POINTER(McepOption)]
     L.WorldMi355MelCepstrum.argtypes = [vp, vp, C.POINTER(McepOption), vp, vp]
+    L.WorldMi355DefaultMgc2spOption.restype = None
+    L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
+    L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
@@ -373,6 +381,28 @@ class WorldBatch:
         _check(load_library().WorldMi355MelCepstrum(self.handle, self._p(spectrum), C.byref(o), self._p(mc),
                                                     C.c_void_p(status.data_ptr())), "MelCepstrum")
         return mc, status
+
+    def spectrum_from_mel_cepstrum(self, mc, alpha=0.35, gamma=0.0, out_format=0, phase=False):
+        """SPTK's mgc2sp per frame (test/sptkfunctions.cpp:186-219 with flng = fft_size): mc is float64 cuda
+        [total_frames][order+1], mel-generalized cepstra at (alpha, gamma), -1 <= gamma <= 0.  out_format 0 gives
+        ln|H|, 3 |H|, 4 |H|^2 (as mel_cepstrum's itype).  Returns (spectrum float64 [total_frames][fft_size/2+1],
+        status int32 [total_frames]: 0 fine, 1 a non-finite coefficient or 1 + gamma c0 <= 0, the row is zeros), with
+        phase=True (spectrum, phase, status), phase being the transform's imaginary part."""
+        import torch
+        if (mc.dim() != 2 or mc.shape[0] != self.total_frames or mc.dtype != torch.float64 or not mc.is_cuda
+                or not mc.is_contiguous()):
+            raise ValueError(f"spectrum_from_mel_cepstrum: mc must be a contiguous float64 cuda tensor "
+                             f"[{self.total_frames}][order+1], got {mc.dtype} {tuple(mc.shape)}")
+        o = Mgc2spOption()
+        load_library().WorldMi355DefaultMgc2spOption(C.byref(o))
+        o.alpha, o.gamma, o.order, o.out_format = float(alpha), float(gamma), int(mc.shape[1]) - 1, int(out_format)
+        sp = torch.empty(self.total_frames, self.bins, dtype=torch.float64, device="cuda")
+        ph = torch.empty_like(sp) if phase else None
+        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MelCepstrumToSpectrum(
+            self.handle, self._p(mc), C.byref(o), self._p(sp), self._p(ph) if phase else None,
+            C.c_void_p(status.data_ptr())), "MelCepstrumToSpectrum")
+        return (sp, ph, status) if phase else (sp, status)
 
     def compose_cmp(self, streams):
         """streams: list of (float32 cuda tensor [total_frames][dim], list of window coefficient lists).

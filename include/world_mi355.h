@@ -199,6 +199,32 @@ void WorldMi355DefaultMcepOption(WorldMi355McepOption* opt);
 int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const WorldMi355McepOption* opt, double* mc,
                           int* status);
 
+/* ---- Spectra from mel-generalized cepstra: the CLIs' SPTK port, mgc2sp(mgc, m, a, g, x, y, flng = fft_size)
+ * (test/sptkfunctions.cpp:186-219) = mgc2mgc towards alpha 0, gamma 0 and fft_size/2 coefficients (:221-254: freqt
+ * :596-631, gnorm :313-328, gc2gc :347-385, ignorm :330-345) and c2sp (:256-274, fftr :387-461) -- what `mgc2sp -a alpha
+ * -g gamma -m order -l fft_size` computes, the inverse of WorldMi355MelCepstrum at gamma 0 and the decoder of `mgcep`
+ * features at the GAMMA of data/Makefile.in:138-146, 186-192.  Fields as mgc2sp's arguments (:186-187): alpha a, gamma g,
+ * order m; out_format 0 ln |H| (the reference's x), 3 |H| = exp(x), 4 |H|^2 = exp(2 x) -- numbered as
+ * WorldMi355McepOption.itype, so 3 / 4 here is what itype 3 / 4 takes there.  SPTK's gain-normalized input (-n, -u) and
+ * 20 log10 output are not offered. */
+typedef struct {
+  double alpha;
+  double gamma;
+  int order;
+  int out_format;
+} WorldMi355Mgc2spOption;
+/* SPTK's defaults: alpha 0.35, gamma 0, order 25; out_format 0. */
+void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* opt);
+/* mc: DEVICE double[total_frames][order+1]; spectrum: DEVICE double[total_frames][fft_size/2+1]; phase: the same shape
+ * or NULL: the imaginary part y (:216, fftr's sign: that of sum c[n] exp(-2 pi i k n / fft_size)), whatever out_format;
+ * status: DEVICE int[total_frames] or NULL: 0 fine, 1 a non-finite coefficient or 1 + gamma c0 <= 0 (c0 after the
+ * frequency transformation; the reference's pow returns NaN there, :313-321): such rows are zeros, phase included.
+ * Frames never exchange data.  1 <= order <= 63, order <= fft_size/2, |alpha| < 1, -1 <= gamma <= 0, else
+ * WM_ERR_BAD_ARG; any other out_format WM_ERR_UNSUPPORTED; both before any device call.  Asynchronous on the context's
+ * stream. */
+int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const WorldMi355Mgc2spOption* opt,
+                                    double* spectrum, double* phase, int* status);
+
 /* ---- `cmp` composition (data/scripts/window.pl:45-146, addhtkheader.pl:45-82), SURVEY.md section 8(f) rank 3 ----
  * Applies each stream's dynamic-feature windows and lays the results side by side per frame:
  *   out[frame] = [stream 0: window 0 (dim) | window 1 | ...][stream 1: ...]...      (float32)
