@@ -241,7 +241,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
@@ -291,5 +291,12 @@ int launch_mel_cepstrum(Batch& b, hipStream_t st, const double* d_spec, const Wo
 int check_mgc2sp(const Batch& b, const double* d_mc, const WorldMi355Mgc2spOption& opt, const double* d_sp);
 int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355Mgc2spOption& opt, double* d_sp,
                   double* d_phase, int* d_status);
+int check_mlpg(int n_streams, const float* const* mean, int64_t ld_mean, const float* const* var, int64_t ld_var,
+               const int* dims, const int* n_windows, const double* const* const* windows,
+               const int* const* window_sizes, const WorldMi355MlpgOption* opt, float* const* out);
+int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mean, int64_t ld_mean,
+                const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
+                const WorldMi355MlpgOption& opt, float* const* out, int* d_status);
 
 }  // namespace wm

@@ -334,6 +334,25 @@ int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* 
   OnDevice dev_(b->b.ctx[0]);
   return launch_compose_cmp(b->b, n_streams, streams, dims, n_windows, windows, window_sizes, out);
 }
+void WorldMi355DefaultMlpgOption(WorldMi355MlpgOption* o) {                     // SPTK's mlpg: taps beyond the ends dropped
+  if (!o) return;
+  o->edge = 0;
+  o->var_per_frame = 0;
+  o->input_type = 0;
+  o->unvoiced_value = -1.0e+10;
+}
+int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float* const* mean, int64_t ld_mean,
+                                  const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                                  const double* const* const* windows, const int* const* window_sizes,
+                                  const float* const* msd, const WorldMi355MlpgOption* opt, float* const* out,
+                                  int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mlpg(n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, opt, out))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mlpg(b->b, b->b.ctx->stream, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows,
+                     window_sizes, msd, *opt, out, status);
+}
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
   const int32_t a = n_frames, fs100 = (int32_t)(10000000.0 * frame_shift_samples / sampling_rate);

@@ -674,3 +674,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "mcep.hip"
 // ---- the decoder half: SPTK's mgc2sp at any gamma, every bin, in double (the same arrangement) ----------------------
 #include "mgc2sp.hip"
+// ---- the inverse of cmp_compose_kernel: static trajectories from `cmp`-layout means and variances (SPTK's mlpg) ------
+#include "mlpg.hip"

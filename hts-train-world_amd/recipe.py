@@ -26,6 +26,8 @@ features travel to rank 0, which writes them all.
            --spec-dim 50 --ap-dim 25          # jobs.txt: one "f0 sp ap wav" per line
 
 cmp_files() is the stage after it (data/Makefile.in:244-323: window.pl per stream, merge, addhtkheader.pl).
+gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
+model's `ffo` rows), in front of synth.
 
 There is no CPU path: without a HIP device the library call fails.
 """
@@ -326,6 +328,86 @@ def cmp_files(jobs, streams, sampling_rate, frame_shift, htk_type=9, ctx=None, m
     return done
 
 
+# ---- parameter generation (scripts/Training.pl:2755-2810 gen_param) ------------------------------------------------
+def ffo_layout(streams):
+    """Columns of an `ffo` row (Training.pl:2759-2765, :2778-2787): per stream its voicing column, when it has one, in
+    front of its static and dynamic means.  streams: [(dim, windows, msd)].  Returns ([(msd column or None, first mean
+    column, mean columns)], row width)."""
+    at, out = 0, []
+    for dim, wins, msd in streams:
+        mcol = at if msd else None
+        at += 1 if msd else 0
+        out.append((mcol, at, int(dim) * len(wins)))
+        at += int(dim) * len(wins)
+    return out, at
+
+
+def gen_param_complete(job, n_frames, streams):
+    """True when every stream file of `job` = (ffo, out_0, ..., out_k) exists with the size generation writes
+    (float32 [n_frames][dim_s]): the test behind `resume`, as outputs_complete is for analysis."""
+    try:
+        return all(os.path.getsize(str(p)) == 4 * n_frames * int(d) for p, (d, _, _) in zip(job[1:], streams))
+    except OSError:
+        return False
+
+
+def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx=None,
+                    max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """`gen_param` (scripts/Training.pl:2755-2810) for a file list: SPTK `mlpg` on every stream of every utterance.
+
+    jobs:     [(ffo_in, stream_out_0, ..., stream_out_k)] -- ffo_in: float32 rows of a model's output, per stream
+              [voicing value, if the stream has one][static | delta | ...] (ffo_layout); stream_out_s: float32
+              [T][dim_s], what :2797-2804 writes to $base.$type
+    streams:  [(dim_s, [window files or coefficient lists, the static window first], msd)] in the row's order;
+              a window file is data/win/NAME.winK: its leading size is dropped as `bcut -s 1` drops it (:2794)
+    var_path: one float32 row in the ffo layout, the global variances (:2788-2791)
+    A frame with voicing value below 0.5 (:2782) receives unvoiced_value in every dim of its stream (:2783, :2800-2801).
+    Rank-sharded by frame count; with resume, utterances whose stream files are complete are skipped."""
+    import torch
+    jobs = list(jobs)
+    streams = [(int(d), [read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws],
+                bool(m)) for d, ws, m in streams]
+    layout, width = ffo_layout(streams)
+    var = np.fromfile(var_path, dtype=np.float32)
+    if var.size != width:
+        raise ValueError("%s has %d values, an ffo row has %d" % (var_path, var.size, width))
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 1 + len(streams) or size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not %d output paths" % (j[0], size, width, len(streams)))
+        frames.append(size // (4 * width))
+    todo = [i for i in range(len(jobs)) if not (resume and gen_param_complete(jobs[i], frames[i], streams))]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    dvar = torch.from_numpy(var).cuda()
+    done = 0
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
+            args = [(rows[:, c0:c0 + n], dvar[c0:c0 + n], wins, None if mcol is None else rows[:, mcol])
+                    for (mcol, c0, n), (_, wins, _) in zip(layout, streams)]
+            outs, status = b.parameter_generation(args, edge=edge, unvoiced_value=unvoiced_value)
+            for k in np.nonzero(status.cpu().numpy())[0]:
+                print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
+                      file=sys.stderr)
+            host = [o.cpu().numpy() for o in outs]
+            fo = b.frame_offsets
+            for k, i in enumerate(group):
+                for s_, h in enumerate(host):
+                    writes.append(pool.submit(np.ascontiguousarray(h[fo[k]:fo[k + 1]]).tofile, jobs[i][1 + s_]))
+            done += int(b.total_frames)
+            b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return done
+
+
 # ---- vibrato (data/scripts/Extract.py, data/Makefile.in:215) --------------------------------------------------------
 _SCALE = ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")
 
@@ -399,13 +481,19 @@ def vibrato_files(jobs, frame_period, fs=48000, ctx=None, max_batch_frames=MAX_B
     return done
 
 
-def _read_scp(path):
+def _read_scp(path, n=4):
     with open(path) as f:
         rows = [ln.split() for ln in f if ln.strip() and not ln.startswith("#")]
-    bad = [r for r in rows if len(r) != 4]
+    bad = [r for r in rows if len(r) != n]
     if bad:
-        raise SystemExit("every line needs four paths: %r" % (bad[0],))
+        raise SystemExit("every line needs %s paths: %r" % ({4: "four"}.get(n, n), bad[0]))
     return [tuple(r) for r in rows]
+
+
+def parse_stream(text):
+    """`dim:msd:win0,win1,...` of the command line -> (dim, [window files], msd), e.g. 1:1:lf0.win1,lf0.win2,lf0.win3."""
+    dim, msd, wins = text.split(":", 2)
+    return int(dim), [w for w in wins.split(",") if w], msd not in ("0", "")
 
 
 def main(argv=None):
@@ -425,7 +513,20 @@ def main(argv=None):
                            help="skip utterances whose three output files are already complete (a run that was cut short)")
         if name == "synth":
             p.add_argument("--fs", type=int, required=True)
+    p = sub.add_parser("gen-param", help="gen_param: mlpg on every stream of a list of ffo files")
+    p.add_argument("--scp", required=True, help="job list: the ffo file, then one output path per stream")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help="one per stream in the row's order: dimension, 1 if a voicing column precedes it, window files")
+    p.add_argument("--var", required=True, help="one float32 row of variances in the ffo layout")
+    p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
+    p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
+    p.add_argument("--resume", action="store_true", help="skip utterances whose stream files are already complete")
     a = ap.parse_args(argv)
+    if a.cmd == "gen-param":
+        n = gen_param_files(_read_scp(a.scp, 1 + len(a.stream)), a.stream, a.var, a.edge, a.unvoiced_value,
+                            resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
     jobs = _read_scp(a.scp)
     if a.cmd == "analysis":
         if a.gather and int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -44,6 +44,12 @@ class Mgc2spOption(C.Structure):
     _fields_ = [("alpha", C.c_double), ("gamma", C.c_double), ("order", C.c_int), ("out_format", C.c_int)]
 
 
+class MlpgOption(C.Structure):
+    """include/world_mi355.h: WorldMi355MlpgOption (parameter generation, SPTK's mlpg)."""
+    _fields_ = [("edge", C.c_int), ("var_per_frame", C.c_int), ("input_type", C.c_int),
+                ("unvoiced_value", C.c_double)]
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -104,6 +110,10 @@ def load_library():
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.WorldMi355DefaultMlpgOption.restype = None
+    L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
+    L.WorldMi355ParameterGeneration.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp,
+                                                C.POINTER(MlpgOption), vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -427,6 +437,77 @@ class WorldBatch:
         _check(load_library().WorldMi355ComposeCmp(self.handle, n, data, dims, nwin, wptrs, sptrs,
                                                    C.c_void_p(out.data_ptr())), "ComposeCmp")
         return out
+
+    def parameter_generation(self, streams, var_per_frame=False, edge=0, input_type=0, unvoiced_value=-1e10):
+        """SPTK's mlpg per stream, as gen_param runs it (scripts/Training.pl:2755-2810): the static trajectory c that
+        solves (W' P W) c = W' P mean.  streams: list of (mean, var, windows, msd_or_None).  mean: float32 cuda
+        [total_frames][len(windows) * dim], laid [window 0: dim | window 1: dim | ...] as compose_cmp writes a stream --
+        a tensor of its own or a column view of one matrix (a model's output, compose_cmp's result).  var: the same
+        layout, [len(windows) * dim] (one row for every frame) or with var_per_frame [total_frames][...]; precisions
+        with input_type=1.  windows: the coefficient lists of compose_cmp.  msd: None, or float32 cuda [total_frames]
+        (a column view will do): frames with a value below 0.5 receive unvoiced_value after the solve.  edge 0 drops
+        taps beyond an utterance's ends (SPTK), 1 clamps them (window.pl: the inverse of compose_cmp).
+        Returns ([float32 [total_frames][dim] per stream], status int32 [n_utt]: bit 1 a column with a non-finite or
+        non-positive input, bit 2 a column whose matrix is not positive definite; such columns are zeros).
+        The C call takes one row stride for all streams: tensors that do not share one are packed side by side first."""
+        import torch
+        n = len(streams)
+        tf = self.total_frames
+        for mean, var, wins, msd in streams:
+            if not (mean.is_cuda and mean.dtype == torch.float32 and mean.dim() == 2 and mean.shape[0] == tf
+                    and len(wins) >= 1 and mean.shape[1] % len(wins) == 0):
+                raise ValueError("parameter_generation: mean must be float32 cuda [total_frames][n_windows * dim]")
+            want = (tf, mean.shape[1]) if var_per_frame else (mean.shape[1],)
+            if not (var.is_cuda and var.dtype == torch.float32 and tuple(var.shape) == want):
+                raise ValueError(f"parameter_generation: var must be float32 cuda {want}, got {tuple(var.shape)}")
+            if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and tuple(msd.shape) == (tf,)):
+                raise ValueError("parameter_generation: msd must be float32 cuda [total_frames]")
+
+        def common_stride(rows, cols):
+            """(row stride, rows, columns, what to keep alive): as given when all share one stride, else packed"""
+            ts = list(rows) + [c for c in cols if c is not None]
+            ld = {int(t.stride(0)) for t in ts}
+            if tf > 1 and len(ld) == 1 and all(t.stride(1) == 1 for t in rows):
+                return ld.pop(), rows, cols, ts
+            mat = torch.cat(list(rows) + [c[:, None] for c in cols if c is not None], dim=1)
+            at, r2, c2 = 0, [], []
+            for t in rows:
+                r2.append(mat[:, at:at + t.shape[1]])
+                at += int(t.shape[1])
+            for c in cols:
+                c2.append(None if c is None else mat[:, at])
+                at += 0 if c is None else 1
+            return int(mat.shape[1]), r2, c2, [mat]
+
+        ld_mean, means, msds, keep_m = common_stride([t for t, _, _, _ in streams], [m for _, _, _, m in streams])
+        if var_per_frame:
+            ld_var, vars_, _, keep_v = common_stride([v for _, v, _, _ in streams], [])
+        else:
+            ld_var, vars_, keep_v = 0, [v.contiguous() for _, v, _, _ in streams], []
+        dp = C.POINTER(C.c_double)
+        vpn = C.c_void_p * n
+        nwin = (C.c_int * n)(*[len(w) for _, _, w, _ in streams])
+        dims = (C.c_int * n)(*[int(t.shape[1]) // len(w) for t, _, w, _ in streams])
+        keep, wptrs, sptrs = [keep_m, keep_v, vars_], (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
+        for s, (_, _, wins, _) in enumerate(streams):
+            arrs = [(C.c_double * len(w))(*w) for w in wins]
+            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
+            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
+            keep += [arrs, pa, sz]
+            wptrs[s] = C.cast(pa, C.POINTER(dp))
+            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        outs = [torch.empty(tf, int(dims[s]), dtype=torch.float32, device="cuda") for s in range(n)]
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        o = MlpgOption()
+        load_library().WorldMi355DefaultMlpgOption(C.byref(o))
+        o.edge, o.var_per_frame, o.input_type = int(edge), 1 if var_per_frame else 0, int(input_type)
+        o.unvoiced_value = float(unvoiced_value)
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        _check(load_library().WorldMi355ParameterGeneration(
+            self.handle, n, vpn(*[ptr(t) for t in means]), ld_mean, vpn(*[ptr(t) for t in vars_]), ld_var, dims, nwin,
+            wptrs, sptrs, vpn(*[ptr(t) for t in msds]), C.byref(o), vpn(*[ptr(t) for t in outs]),
+            C.c_void_p(status.data_ptr())), "ParameterGeneration")
+        return outs, status
 
     def split_frames(self, a):
         return [a[self.frame_offsets[u]:self.frame_offsets[u + 1]] for u in range(self.n_utt)]

@@ -235,6 +235,44 @@ int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const 
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out);
+
+/* ---- Parameter generation: SPTK `mlpg` as gen_param drives it (scripts/Training.pl:2755-2810), the inverse of
+ * WorldMi355ComposeCmp and the stage between a model's `cmp`-layout rows and WorldMi355RecipeDecode /
+ * WorldMi355MelCepstrumToSpectrum.  One column is one utterance, one stream and one dimension, with T frames and the
+ * stream's windows w_0 .. w_{n-1} (odd sizes, centre tap h_i = (size_i - 1) / 2):
+ *   W  is the (n T) x T matrix whose row (t, i) holds w_i[k] at column t + k - h_i,
+ *   mu the n T means, P the diagonal matrix of precisions 1 / variance,
+ *   out the c that solves (W' P W) c = W' P mu     (banded LDL' in double; float32 in and out).
+ * Columns never exchange data, utterances never exchange data. */
+typedef struct {
+  int edge;               /* 0 taps beyond the utterance dropped (SPTK mlpg); 1 clamped (window.pl, inverse of ComposeCmp) */
+  int var_per_frame;      /* 0: var[s] is ONE row, used for every frame (gen_param's global variance, :2788-2791); 1: a row per frame */
+  int input_type;         /* 0 variances, 1 precisions (mlpg -i 0 / -i 1) */
+  double unvoiced_value;  /* written to every dim of an unvoiced frame of a stream with msd; default -1e10 */
+} WorldMi355MlpgOption;
+void WorldMi355DefaultMlpgOption(WorldMi355MlpgOption* opt);   /* 0, 0, 0, -1e10 */
+/* mean[s]: DEVICE, row t of the batch at mean[s] + t * ld_mean: n_windows[s] * dims[s] floats laid
+ *   [window 0: dim | window 1: dim | ...] as ComposeCmp writes a stream; var[s] the same layout with ld_var (ld_var is
+ *   ignored and var[s] is one row when var_per_frame == 0).  One row stride for all streams: the call reads
+ *   ComposeCmp's out (pointers into it, ld_mean = its columns) or an `ffo` row (:2778-2787) as it is.
+ * dims, n_windows, windows, window_sizes: HOST, exactly as ComposeCmp.
+ * msd: NULL, or per stream NULL or DEVICE: the stream's voicing value of frame t at msd[s] + t * ld_mean.  A frame is
+ *   voiced when the value is >= 0.5 (:2782).  The solve runs over the whole utterance whatever the voicing, as gen_param
+ *   does; afterwards every dim of an unvoiced frame holds unvoiced_value (0 gives the lf0 RecipeDecode expects).
+ * out[s]: DEVICE float32 [total_frames][dims[s]], contiguous: what RecipeDecode takes.
+ * status: DEVICE int[n_utt] or NULL, a bit mask per utterance: 1 a column holds a non-finite mean or variance, a
+ *   variance <= 0, or with input_type 1 a precision < 0 (precision 0, an ignored observation, is allowed); 2 a pivot of
+ *   the factorisation <= 0 or non-finite in a column with valid input: W' P W is not positive definite (no static
+ *   window, singular ends).  A flagged column is zeros in every frame, whatever the voicing; no other column and no
+ *   other utterance is affected.
+ * Limits as ComposeCmp: 1-4 streams, 1-4 windows, odd sizes up to 15, dims >= 1.  A limit exceeded, a NULL required
+ * pointer, ld_mean (ld_var with var_per_frame) smaller than a stream's row, edge or input_type out of range:
+ * WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's stream; a batch of zero frames returns WM_OK. */
+int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float* const* mean, int64_t ld_mean,
+                                  const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                                  const double* const* const* windows, const int* const* window_sizes,
+                                  const float* const* msd, const WorldMi355MlpgOption* opt, float* const* out,
+                                  int* status);
 /* The 12-byte HTK header of addhtkheader.pl:60-75 (host only, native byte order). */
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]);
@@ -263,7 +301,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel").  Enable clears earlier records; Query synchronises the stream and returns
+ * "synth_ola_kernel", "mlpg_kernel").  Enable clears earlier records; Query synchronises the stream and returns
  * the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
