@@ -298,5 +298,8 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
                 const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
                 const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
                 const WorldMi355MlpgOption& opt, float* const* out, int* d_status);
+int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
+int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
+                double* d_gain, int* d_status);
 
 }  // namespace wm

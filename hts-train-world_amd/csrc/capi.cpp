@@ -353,6 +353,20 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
   return launch_mlpg(b->b, b->b.ctx->stream, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows,
                      window_sizes, msd, *opt, out, status);
 }
+void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* o) {                     // SPTK's alpha and order, the recipe's beta and IMPLEN
+  if (!o) return;
+  o->alpha = 0.35;
+  o->beta = 1.4;
+  o->order = 25;
+  o->length = 4096;
+}
+int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const WorldMi355McpfOption* opt, double* out,
+                                    double* gain, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mcpf(mc, opt, out)) return rc;                       // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mcpf(b->b, b->b.ctx->stream, mc, *opt, out, gain, status);
+}
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
   const int32_t a = n_frames, fs100 = (int32_t)(10000000.0 * frame_shift_samples / sampling_rate);

@@ -676,3 +676,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "mgc2sp.hip"
 // ---- the inverse of cmp_compose_kernel: static trajectories from `cmp`-layout means and variances (SPTK's mlpg) ------
 #include "mlpg.hip"
+// ---- the recipe's formant emphasis between the two: postfiltering_mcp of gen_wave (the same arrangement) --------------
+#include "mcpf.hip"

@@ -27,7 +27,8 @@ features travel to rank 0, which writes them all.
 
 cmp_files() is the stage after it (data/Makefile.in:244-323: window.pl per stream, merge, addhtkheader.pl).
 gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
-model's `ffo` rows), in front of synth.
+model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is the step gen_wave takes between the two
+(scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).
 
 There is no CPU path: without a HIP device the library call fails.
 """
@@ -408,6 +409,64 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
     return done
 
 
+# ---- mel-cepstral postfilter (scripts/Training.pl:2642-2687 postfiltering_mcp) ----------------------------------------
+def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
+                     io_threads=8, resume=False):
+    """`postfiltering_mcp` (scripts/Training.pl:2642-2687) for a file list, as gen_wave runs it on every generated
+    `.mgc` (:2838-2840) before mgc2sp.
+
+    jobs:  [(mgc_in, p_mgc_out)] -- float32 [T][order+1] in, float32 of the same shape out ($base.p_mgc)
+    alpha, beta, length: $fw, $pf_mcp, $fl of the recipe's configuration
+    The rows go to the device as float32 and are widened there; the result is rounded to float32 once, where the script
+    rounds at every pipe.  Rank-sharded by frame count; with resume, utterances whose output has the input's size are
+    skipped."""
+    import torch
+    jobs = list(jobs)
+    width = int(order) + 1
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 2 or size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not one output path" % (j[0], size, width))
+        frames.append(size // (4 * width))
+
+    def complete(i):
+        try:
+            return os.path.getsize(str(jobs[i][1])) == 4 * width * frames[i]
+        except OSError:
+            return False
+
+    todo = [i for i in range(len(jobs)) if not (resume and complete(i))]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    if not mine:
+        return 0
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    done = 0
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
+            out, status = b.postfilter_mel_cepstrum(rows.double(), alpha, beta, length)
+            host = out.float().cpu().numpy()
+            st = status.cpu().numpy()
+            fo = b.frame_offsets
+            for k, i in enumerate(group):
+                bad = np.nonzero(st[fo[k]:fo[k + 1]])[0]
+                if len(bad):
+                    print("warning: %s: %d frames flagged (first: frame %d, status %d), written as zeros" % (
+                        jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
+                writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][1]))
+            done += int(b.total_frames)
+            b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return done
+
+
 # ---- vibrato (data/scripts/Extract.py, data/Makefile.in:215) --------------------------------------------------------
 _SCALE = ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")
 
@@ -521,7 +580,18 @@ def main(argv=None):
     p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
     p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
     p.add_argument("--resume", action="store_true", help="skip utterances whose stream files are already complete")
+    p = sub.add_parser("postfilter", help="postfiltering_mcp: formant emphasis on a list of mgc files")
+    p.add_argument("--scp", required=True, help="job list: the mgc file, then the p_mgc file to write")
+    p.add_argument("--order", type=int, required=True, help="order of the mel-cepstra: a row holds order + 1 float32")
+    p.add_argument("--alpha", type=float, required=True, help="frequency warping of the mgc stream")
+    p.add_argument("--beta", type=float, default=1.4, help="the postfiltering coefficient (pf_mcp)")
+    p.add_argument("--length", type=int, default=4096, help="bins of the energy sums (IMPLEN)")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
     a = ap.parse_args(argv)
+    if a.cmd == "postfilter":
+        n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
     if a.cmd == "gen-param":
         n = gen_param_files(_read_scp(a.scp, 1 + len(a.stream)), a.stream, a.var, a.edge, a.unvoiced_value,
                             resume=a.resume)

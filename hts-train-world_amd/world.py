@@ -50,6 +50,11 @@ class MlpgOption(C.Structure):
                 ("unvoiced_value", C.c_double)]
 
 
+class McpfOption(C.Structure):
+    """include/world_mi355.h: WorldMi355McpfOption (the recipe's mel-cepstral postfilter, postfiltering_mcp)."""
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("order", C.c_int), ("length", C.c_int)]
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -109,6 +114,9 @@ def load_library():
     L.WorldMi355DefaultMgc2spOption.restype = None
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
+    L.WorldMi355DefaultMcpfOption.restype = None
+    L.WorldMi355DefaultMcpfOption.argtypes = [C.POINTER(McpfOption)]
+    L.WorldMi355MelCepstrumPostfilter.argtypes = [vp, vp, C.POINTER(McpfOption), vp, vp, vp]
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.WorldMi355DefaultMlpgOption.restype = None
     L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
@@ -413,6 +421,29 @@ class WorldBatch:
             self.handle, self._p(mc), C.byref(o), self._p(sp), self._p(ph) if phase else None,
             C.c_void_p(status.data_ptr())), "MelCepstrumToSpectrum")
         return (sp, ph, status) if phase else (sp, status)
+
+    def postfilter_mel_cepstrum(self, mc, alpha=0.35, beta=1.4, length=4096, gain=False):
+        """The recipe's formant emphasis per frame (scripts/Training.pl:2642-2687, postfiltering_mcp): mc is float64
+        cuda [total_frames][order+1], mel-cepstra at warp alpha.  out[0] = c[0] + delta, out[k] = w[k] c[k] with
+        w = [1, 1, beta, ..., beta] and delta = 1/2 ln(E(c) / E(w c)), E the mean of the power spectrum over `length`
+        bins.  Returns (out float64 [total_frames][order+1], status int32 [total_frames]: 0 fine, 1 a non-finite
+        coefficient, 2 a sum that is not finite and positive; flagged rows are zeros), with gain=True
+        (out, gain float64 [total_frames] = delta, status).  beta == 1 or order == 1 copies the rows."""
+        import torch
+        if (mc.dim() != 2 or mc.shape[0] != self.total_frames or mc.dtype != torch.float64 or not mc.is_cuda
+                or not mc.is_contiguous()):
+            raise ValueError(f"postfilter_mel_cepstrum: mc must be a contiguous float64 cuda tensor "
+                             f"[{self.total_frames}][order+1], got {mc.dtype} {tuple(mc.shape)}")
+        o = McpfOption()
+        load_library().WorldMi355DefaultMcpfOption(C.byref(o))
+        o.alpha, o.beta, o.order, o.length = float(alpha), float(beta), int(mc.shape[1]) - 1, int(length)
+        out = torch.empty_like(mc)
+        g = torch.empty(self.total_frames, dtype=torch.float64, device="cuda") if gain else None
+        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MelCepstrumPostfilter(
+            self.handle, self._p(mc), C.byref(o), self._p(out), self._p(g) if gain else None,
+            C.c_void_p(status.data_ptr())), "MelCepstrumPostfilter")
+        return (out, g, status) if gain else (out, status)
 
     def compose_cmp(self, streams):
         """streams: list of (float32 cuda tensor [total_frames][dim], list of window coefficient lists).

@@ -273,6 +273,36 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
                                   const double* const* const* windows, const int* const* window_sizes,
                                   const float* const* msd, const WorldMi355MlpgOption* opt, float* const* out,
                                   int* status);
+/* ---- Mel-cepstral postfilter: the recipe's formant emphasis, postfiltering_mcp (scripts/Training.pl:2642-2687), which
+ * gen_wave (:2813-2845) runs on every generated `.mgc` before mgc2sp -- the stage between
+ * WorldMi355ParameterGeneration and WorldMi355MelCepstrumToSpectrum.  For one frame c[0 .. order] at warp alpha and
+ * w = [1, 1, beta, ..., beta] (:2646-2651):
+ *   out[0] = c[0] + delta,   out[k] = w[k] c[k] (k >= 1),   delta = 1/2 ln(E(c) / E(w c)),
+ * E(v) being `freqt -m order -a alpha -M co -A 0 | c2acr -m co -M 0 -l length` of v (:2654-2662): the mean over the
+ * `length` bins of the power spectrum of v.  mc2b, the addition to b[0] and b2mc (:2664-2682) amount to the first line.
+ * E is evaluated in double at the script's bins in the limit co -> infinity, directly at the warped frequencies; the
+ * script's co = 2047 leaves out at most twice sum_{n > co} |freqt(w c)[n]| (5e-431 at order 49, alpha 0.55), far
+ * below the float32 rounding of its intermediate files (1e-7).  Fields: alpha the `mgc` stream's warp ($fw), beta $pf_mcp
+ * (config default 1.4), order m, length $fl = IMPLEN (4096), independent of the batch's fft_size.  hts_engine's -b
+ * postfilter (:810), the LSP postfilter (:2690-2752) and the modulation-spectrum postfilter (:2950) are not offered. */
+typedef struct {
+  double alpha;
+  double beta;
+  int order;
+  int length;
+} WorldMi355McpfOption;
+/* alpha 0.35, beta 1.4, order 25, length 4096. */
+void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* opt);
+/* mc, out: DEVICE double[total_frames][order+1]; out == mc (in place) is allowed.  gain: DEVICE double[total_frames] or
+ * NULL: delta.  out[0] is exactly the rounded sum c[0] + delta with that delta, out[k] exactly the one product
+ * w[k] c[k]; c[0] does not enter delta.  status: DEVICE int[total_frames] or NULL: 0 fine, 1 a non-finite coefficient,
+ * 2 a sum that is not finite and positive (exp overflowed); such rows are zeros with gain 0.  Frames never exchange
+ * data.  beta == 1 or order == 1 is the identity (gen_wave skips the step at 1.0, :2838): rows copied bit for bit,
+ * gain 0, status 0, no energy computed.  A NULL mc, opt or out, order outside 1 .. 63, not |alpha| < 1, a non-finite
+ * beta, length not a power of two in 64 .. 8192: WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's
+ * stream; a batch of zero frames returns WM_OK. */
+int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const WorldMi355McpfOption* opt, double* out,
+                                    double* gain, int* status);
 /* The 12-byte HTK header of addhtkheader.pl:60-75 (host only, native byte order). */
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]);
@@ -301,8 +331,8 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel", "mlpg_kernel").  Enable clears earlier records; Query synchronises the stream and returns
- * the summed duration and the number of launches since Enable. */
+ * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
 
