@@ -241,7 +241,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
@@ -301,5 +301,17 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);
+int check_column_means(const double* d_x, int dim, const double* d_mean);
+int launch_column_means(Batch& b, hipStream_t st, const double* d_x, int dim, double* d_mean);
+int check_mspf(const double* d_x, int dim, const WorldMi355MspfOption* opt, const double* mean_gen, const double* std_gen,
+               const double* mean_nat, const double* std_nat, const double* d_out);
+int launch_mspf(Batch& b, hipStream_t st, const double* d_x, int dim, const WorldMi355MspfOption& opt,
+                const double* mean_gen, const double* std_gen, const double* mean_nat, const double* std_nat,
+                double* d_out, int* d_status);
+int check_mspf_stats(const double* d_x, int dim, const WorldMi355MspfOption* opt, const double* d_sum,
+                     const double* d_sumsq, const int64_t* n_frames);
+int launch_mspf_stats(Batch& b, hipStream_t st, const double* d_x, int dim, const WorldMi355MspfOption& opt,
+                      const double* d_mean, double* d_sum, double* d_sumsq, int64_t* n_frames);
+int mspf_segment_frames();
 
 }  // namespace wm

@@ -367,6 +367,34 @@ int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const 
   OnDevice dev_(b->b.ctx[0]);
   return launch_mcpf(b->b, b->b.ctx->stream, mc, *opt, out, gain, status);
 }
+void WorldMi355DefaultMspfOption(WorldMi355MspfOption* o) {                     // the recipe's $mspfLength, $mspfFFTLen, $mspfe{'mgc'}
+  if (!o) return;
+  o->frame_length = 25;
+  o->fft_length = 64;
+  o->emphasis = 1.0;
+}
+int WorldMi355MspfSegmentFrames(void) { return mspf_segment_frames(); }
+int WorldMi355ColumnMeans(WorldMi355Batch* b, const double* x, int dim, double* mean) {
+  if (const int rc = check_column_means(x, dim, mean)) return rc;               // refused before any device call
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_column_means(b->b, b->b.ctx->stream, x, dim, mean);
+}
+int WorldMi355ModulationSpectrumPostfilter(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
+                                           const double* mean_gen, const double* std_gen, const double* mean_nat,
+                                           const double* std_nat, double* out, int* status) {
+  if (const int rc = check_mspf(x, dim, opt, mean_gen, std_gen, mean_nat, std_nat, out)) return rc;
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mspf(b->b, b->b.ctx->stream, x, dim, *opt, mean_gen, std_gen, mean_nat, std_nat, out, status);
+}
+int WorldMi355ModulationSpectrumStats(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
+                                      const double* mean, double* sum, double* sumsq, int64_t* n_frames) {
+  if (const int rc = check_mspf_stats(x, dim, opt, sum, sumsq, n_frames)) return rc;
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_mspf_stats(b->b, b->b.ctx->stream, x, dim, *opt, mean, sum, sumsq, n_frames);
+}
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
   const int32_t a = n_frames, fs100 = (int32_t)(10000000.0 * frame_shift_samples / sampling_rate);

@@ -678,3 +678,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "mlpg.hip"
 // ---- the recipe's formant emphasis between the two: postfiltering_mcp of gen_wave (the same arrangement) --------------
 #include "mcpf.hip"
+// ---- the branch gen_wave takes instead with USEMSPF: postfiltering_mspf and make_mspf's sums (the same arrangement) ---
+#include "mspf.hip"

@@ -28,7 +28,9 @@ features travel to rank 0, which writes them all.
 cmp_files() is the stage after it (data/Makefile.in:244-323: window.pl per stream, merge, addhtkheader.pl).
 gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
 model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is the step gen_wave takes between the two
-(scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).
+(scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With USEMSPF gen_wave takes
+postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
+`mspf-stats` write (make_mspf, :3133-3221).
 
 There is no CPU path: without a HIP device the library call fails.
 """
@@ -467,6 +469,175 @@ def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_ba
     return done
 
 
+# ---- modulation-spectrum postfilter (scripts/Training.pl:2950-3038 postfiltering_mspf, :3133-3221 make_mspf) ----------
+def mspf_label_rows(lines, frame_shift_s, n_rows, silences=()):
+    """Rows that make_mspf's silence removal keeps: label lines "start end name" in 100 ns units; a segment's frames are
+    int(start 1e-7 / shift) .. int(end 1e-7 / shift), both ends inclusive (`bcut -s -e`), clipped to the file, so
+    adjacent segments repeat their boundary frame; segments named in `silences` are dropped, the rest butted together."""
+    keep = []
+    for line in lines:
+        f = line.split()
+        if len(f) < 3 or f[2] in silences:
+            continue
+        a = max(int(int(f[0]) * 1e-7 / frame_shift_s), 0)
+        b = min(int(int(f[1]) * 1e-7 / frame_shift_s), n_rows - 1)
+        keep.extend(range(a, b + 1))
+    return np.asarray(keep, dtype=np.int64)
+
+
+def _mspf_stat_paths(directory, name, d):
+    base = os.path.join(str(directory), "%s_dim%d" % (name, d))
+    return base + ".mean", base + ".stdd"
+
+
+def mspf_stats_files(jobs, dim, out_dir, name="mgc", silences=(), frame_shift_s=0.005, frame_length=25, fft_length=64,
+                     ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8):
+    """`make_mspf` (scripts/Training.pl:3133-3221) for one side (natural or generated) of a file list.
+
+    jobs:     [(feature_file, label_file or None)] -- float32 [T][dim] rows
+    silences: label names to drop; with none (or no label file) the whole file is used.  With silence removal the mean
+              is the whole file's and the kept segments are butted together (mspf_label_rows).
+    Rank-sharded by frame count; the ranks' sums are added (all-reduce when a process group is up) and rank 0 writes
+    out_dir/<name>_dim<d>.mean and .stdd, d = 0 .. dim-1, fft_length/2+1 float32 each.  Returns the frames counted."""
+    import torch
+    jobs = [tuple(j) for j in jobs]
+    width, K = int(dim), int(fft_length) // 2 + 1
+    silences = tuple(silences)
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 2 or size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not one label path" % (j[0], size, width))
+        frames.append(size // (4 * width))
+    some = [i for i in range(len(jobs)) if frames[i] > 0]            # a batch holds no utterance without frames
+    mine = [some[k] for k in _my_share([frames[i] for i in some])]
+    rank, world = _rank_world()
+    s1 = torch.zeros(width, K, dtype=torch.float64)
+    s2 = torch.zeros(width, K, dtype=torch.float64)
+    count = 0
+    if mine:
+        own_ctx = ctx is None
+        ctx = ctx or _own_context()
+        with ThreadPoolExecutor(io_threads) as pool:
+            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+                rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
+                rows = rows.double()
+                lengths = [frames[i] for i in group]
+                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)
+                mean = None
+                if silences and any(jobs[i][1] for i in group):
+                    mean = b.utterance_means(rows)
+                    fo, keep, kept = b.frame_offsets, [], []
+                    for k, i in enumerate(group):
+                        if jobs[i][1]:
+                            with open(jobs[i][1]) as f:
+                                idx = mspf_label_rows(f.readlines(), frame_shift_s, frames[i], silences)
+                        else:
+                            idx = np.arange(frames[i], dtype=np.int64)
+                        keep.append(idx + int(fo[k]))
+                        kept.append(len(idx))
+                    b.close()
+                    some_left = [k for k, n_ in enumerate(kept) if n_ > 0]      # all silence: nothing to count
+                    if not some_left:
+                        continue
+                    rows = rows[torch.from_numpy(np.concatenate(keep)).cuda()].contiguous()
+                    mean = mean[torch.tensor(some_left, device="cuda")].contiguous()
+                    b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[kept[k] for k in some_left])
+                a1, a2, n = b.modulation_spectrum_stats(rows, frame_length, fft_length, mean)
+                s1 += a1.cpu()
+                s2 += a2.cpu()
+                count += n
+                b.close()
+        if own_ctx:
+            ctx.close()
+    if world > 1:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("mspf_stats_files with WORLD_SIZE > 1 needs torch.distributed to be initialised: the "
+                               "ranks' sums have to be added")
+        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+        packed = torch.cat([s1.flatten(), s2.flatten()]).to(dev)
+        cnt = torch.tensor([count], dtype=torch.int64, device=dev)
+        dist.all_reduce(packed)
+        dist.all_reduce(cnt)
+        packed = packed.cpu()
+        s1, s2, count = packed[:width * K].view(width, K), packed[width * K:].view(width, K), int(cnt.item())
+    if rank == 0 and count > 0:
+        mean, std = W.mspf_finalize(s1.numpy(), s2.numpy(), count)
+        os.makedirs(str(out_dir), exist_ok=True)
+        for d in range(width):
+            pm, ps = _mspf_stat_paths(out_dir, name, d)
+            mean[d].astype(np.float32).tofile(pm)
+            std[d].astype(np.float32).tofile(ps)
+    return count
+
+
+def mspf_files(jobs, dim, gen_stats_dir, nat_stats_dir, name="mgc", emphasis=1.0, frame_length=25, fft_length=64,
+               ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """`postfiltering_mspf` (scripts/Training.pl:2950-3038) for a file list, as gen_wave runs it with USEMSPF in the
+    place of postfiltering_mcp.
+
+    jobs:  [(mgc_in, p_mgc_out)] -- float32 [T][dim] in, float32 of the same shape out
+    gen_stats_dir, nat_stats_dir: where mspf_stats_files wrote <name>_dim<d>.mean / .stdd for generated and natural
+    parameters.  The rows are widened on the device and the result is rounded to float32 once.  Rank-sharded by frame
+    count; with resume, utterances whose output has the input's size are skipped.  A flagged utterance is reported."""
+    import torch
+    jobs = list(jobs)
+    width, K = int(dim), int(fft_length) // 2 + 1
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 2 or size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not one output path" % (j[0], size, width))
+        frames.append(size // (4 * width))
+
+    def table(directory, which):
+        rows = [np.fromfile(_mspf_stat_paths(directory, name, d)[which], dtype=np.float32) for d in range(width)]
+        if any(len(r) != K for r in rows):
+            raise ValueError("%s: the %s statistics do not hold %d bins per dimension" % (directory, name, K))
+        return np.stack(rows).astype(np.float64)
+
+    def complete(i):
+        try:
+            return os.path.getsize(str(jobs[i][1])) == 4 * width * frames[i]
+        except OSError:
+            return False
+
+    todo = [i for i in range(len(jobs)) if not (resume and complete(i))]
+    for i in [i for i in todo if frames[i] == 0]:                     # nothing to filter: the output is empty as well
+        if _rank_world()[0] == 0:
+            open(jobs[i][1], "wb").close()
+    todo = [i for i in todo if frames[i] > 0]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    if not mine:
+        return 0
+    tabs = (table(gen_stats_dir, 0), table(gen_stats_dir, 1), table(nat_stats_dir, 0), table(nat_stats_dir, 1))
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    done = 0
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
+            out, status = b.postfilter_modulation_spectrum(rows.double(), *tabs, emphasis, frame_length, fft_length)
+            host = out.float().cpu().numpy()
+            st = status.cpu().numpy()
+            fo = b.frame_offsets
+            for k, i in enumerate(group):
+                if st[k]:
+                    print("warning: %s: flagged (status %d), the affected columns written as zeros" % (
+                        jobs[i][0], int(st[k])), file=sys.stderr)
+                writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][1]))
+            done += int(b.total_frames)
+            b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return done
+
+
 # ---- vibrato (data/scripts/Extract.py, data/Makefile.in:215) --------------------------------------------------------
 _SCALE = ("C", "Db", "D", "Eb", "E", "F", "Gb", "G", "Ab", "A", "Bb", "B")
 
@@ -587,7 +758,41 @@ def main(argv=None):
     p.add_argument("--beta", type=float, default=1.4, help="the postfiltering coefficient (pf_mcp)")
     p.add_argument("--length", type=int, default=4096, help="bins of the energy sums (IMPLEN)")
     p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
+    for cmd in ("mspf-stats", "mspf"):
+        p = sub.add_parser(cmd, help="make_mspf: statistics of the modulation spectra of a list of files" if cmd == "mspf-stats"
+                           else "postfiltering_mspf: the modulation-spectrum postfilter on a list of mgc files")
+        p.add_argument("--scp", required=True, help="job list: the feature file and its label file ('-' for none)"
+                       if cmd == "mspf-stats" else "job list: the mgc file, then the p_mgc file to write")
+        p.add_argument("--dim", type=int, required=True, help="float32 values per row")
+        p.add_argument("--name", default="mgc", help="the statistics files are <name>_dim<d>.mean / .stdd")
+        p.add_argument("--frame-length", type=int, default=25, help="mspfLength")
+        p.add_argument("--fft-length", type=int, default=64, help="mspfFFTLen")
+        if cmd == "mspf-stats":
+            p.add_argument("--out-dir", required=True)
+            p.add_argument("--silence", action="append", default=[], help="a label name to drop (may be repeated)")
+            p.add_argument("--frame-shift", type=float, default=0.005, help="seconds per frame")
+        else:
+            p.add_argument("--gen-stats", required=True, help="directory of the generated parameters' statistics")
+            p.add_argument("--nat-stats", required=True, help="directory of the natural parameters' statistics")
+            p.add_argument("--emphasis", type=float, default=1.0, help="mspfe")
+            p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
     a = ap.parse_args(argv)
+    if a.cmd == "mspf-stats":
+        jobs = [(f, None if lab == "-" else lab) for f, lab in _read_scp(a.scp, 2)]
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                # torchrun: the ranks' sums are all-reduced
+            import torch
+            import torch.distributed as dist
+            torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+            if not dist.is_initialized():
+                dist.init_process_group(os.environ.get("WM_BACKEND", "nccl"))
+        n = mspf_stats_files(jobs, a.dim, a.out_dir, a.name, a.silence, a.frame_shift, a.frame_length, a.fft_length)
+        print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "mspf":
+        n = mspf_files(_read_scp(a.scp, 2), a.dim, a.gen_stats, a.nat_stats, a.name, a.emphasis, a.frame_length,
+                       a.fft_length, resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)
         print("complete. %d frames" % n)

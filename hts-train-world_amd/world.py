@@ -55,6 +55,11 @@ class McpfOption(C.Structure):
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("order", C.c_int), ("length", C.c_int)]
 
 
+class MspfOption(C.Structure):
+    """include/world_mi355.h: WorldMi355MspfOption (the recipe's modulation-spectrum postfilter, postfiltering_mspf)."""
+    _fields_ = [("frame_length", C.c_int), ("fft_length", C.c_int), ("emphasis", C.c_double)]
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -117,6 +122,13 @@ def load_library():
     L.WorldMi355DefaultMcpfOption.restype = None
     L.WorldMi355DefaultMcpfOption.argtypes = [C.POINTER(McpfOption)]
     L.WorldMi355MelCepstrumPostfilter.argtypes = [vp, vp, C.POINTER(McpfOption), vp, vp, vp]
+    L.WorldMi355DefaultMspfOption.restype = None
+    L.WorldMi355DefaultMspfOption.argtypes = [C.POINTER(MspfOption)]
+    L.WorldMi355ModulationSpectrumPostfilter.argtypes = [vp, vp, C.c_int, C.POINTER(MspfOption), vp, vp, vp, vp, vp, vp]
+    L.WorldMi355ModulationSpectrumStats.argtypes = [vp, vp, C.c_int, C.POINTER(MspfOption), vp, vp, vp,
+                                                    C.POINTER(C.c_int64)]
+    L.WorldMi355ColumnMeans.argtypes = [vp, vp, C.c_int, vp]
+    L.WorldMi355MspfSegmentFrames.argtypes = []
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.WorldMi355DefaultMlpgOption.restype = None
     L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
@@ -445,6 +457,73 @@ class WorldBatch:
             C.c_void_p(status.data_ptr())), "MelCepstrumPostfilter")
         return (out, g, status) if gain else (out, status)
 
+    def _mspf_rows(self, x, where):
+        import torch
+        if (x.dim() != 2 or x.shape[0] != self.total_frames or x.shape[1] < 1 or x.dtype != torch.float64
+                or not x.is_cuda or not x.is_contiguous()):
+            raise ValueError(f"{where}: x must be a contiguous float64 cuda tensor [{self.total_frames}][dim], "
+                             f"got {x.dtype} {tuple(x.shape)}")
+        return int(x.shape[1])
+
+    @staticmethod
+    def _mspf_option(frame_length, fft_length, emphasis=1.0):
+        o = MspfOption()
+        load_library().WorldMi355DefaultMspfOption(C.byref(o))
+        o.frame_length, o.fft_length, o.emphasis = int(frame_length), int(fft_length), float(emphasis)
+        return o
+
+    def utterance_means(self, x):
+        """Column means per utterance of x, float64 cuda [total_frames][dim]: float64 [n_utt][dim], summed in a fixed
+        order that depends on the utterance's length alone (a batch holds no utterance without frames)."""
+        dim = self._mspf_rows(x, "utterance_means")
+        mean = self._new(self.n_utt, dim)
+        _check(load_library().WorldMi355ColumnMeans(self.handle, self._p(x), dim, self._p(mean)), "ColumnMeans")
+        return mean
+
+    def modulation_spectrum_stats(self, x, frame_length=25, fft_length=64, mean=None):
+        """The sums behind make_mspf's statistics (scripts/Training.pl:3133-3221) over this batch: x float64 cuda
+        [total_frames][dim]; mean None (each utterance's own column means) or float64 cuda [n_utt][dim] (silence
+        removal: the whole utterance's).  Returns (sum, sumsq float64 cuda [dim][fft_length/2+1], n_frames int): add
+        them across batches and hand them to mspf_finalize."""
+        import torch
+        dim = self._mspf_rows(x, "modulation_spectrum_stats")
+        if mean is not None and (tuple(mean.shape) != (self.n_utt, dim) or mean.dtype != torch.float64
+                                 or not mean.is_cuda or not mean.is_contiguous()):
+            raise ValueError(f"modulation_spectrum_stats: mean must be a contiguous float64 cuda tensor "
+                             f"[{self.n_utt}][{dim}], got {mean.dtype} {tuple(mean.shape)}")
+        o = self._mspf_option(frame_length, fft_length)
+        K = int(fft_length) // 2 + 1
+        s1, s2 = self._new(dim, K), self._new(dim, K)
+        n = C.c_int64(0)
+        _check(load_library().WorldMi355ModulationSpectrumStats(
+            self.handle, self._p(x), dim, C.byref(o), self._p(mean) if mean is not None else None, self._p(s1),
+            self._p(s2), C.byref(n)), "ModulationSpectrumStats")
+        return s1, s2, int(n.value)
+
+    def postfilter_modulation_spectrum(self, x, mean_gen, std_gen, mean_nat, std_nat, emphasis=1.0, frame_length=25,
+                                       fft_length=64):
+        """The recipe's modulation-spectrum postfilter (scripts/Training.pl:2950-3038, postfiltering_mspf), which
+        gen_wave runs instead of postfilter_mel_cepstrum with USEMSPF: x float64 cuda [total_frames][dim]; the four
+        tables [dim][fft_length/2+1] (numpy or tensors; they are validated and uploaded by the library).  Returns
+        (out float64 [total_frames][dim], status int32 [n_utt]: bit 1 a column with a non-finite input, bit 2 a result
+        that is not finite; such a column is zeros in that utterance)."""
+        import torch
+        dim = self._mspf_rows(x, "postfilter_modulation_spectrum")
+        K = int(fft_length) // 2 + 1
+        tabs = []
+        for name, t in (("mean_gen", mean_gen), ("std_gen", std_gen), ("mean_nat", mean_nat), ("std_nat", std_nat)):
+            a = np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)
+            if a.shape != (dim, K):
+                raise ValueError(f"postfilter_modulation_spectrum: {name} must be [{dim}][{K}], got {a.shape}")
+            tabs.append(a)
+        o = self._mspf_option(frame_length, fft_length, emphasis)
+        out = torch.empty_like(x)
+        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355ModulationSpectrumPostfilter(
+            self.handle, self._p(x), dim, C.byref(o), *[a.ctypes.data_as(C.c_void_p) for a in tabs], self._p(out),
+            C.c_void_p(status.data_ptr())), "ModulationSpectrumPostfilter")
+        return out, status
+
     def compose_cmp(self, streams):
         """streams: list of (float32 cuda tensor [total_frames][dim], list of window coefficient lists).
         Returns float32 [total_frames][sum n_windows * dim] (window.pl + merge of the recipe's cmp stage)."""
@@ -550,6 +629,18 @@ class WorldBatch:
         if self.handle:
             load_library().WorldMi355DestroyBatch(self.handle)
             self.handle = None
+
+
+def mspf_finalize(sum, sumsq, n):
+    """make_mspf's statistics from the sums of modulation_spectrum_stats (numpy arrays or tensors, added over all
+    batches and ranks): (mean, std) with std the population standard deviation sqrt(E[m^2] - E[m]^2)."""
+    mean = sum / n
+    return mean, (sumsq / n - mean * mean).clip(0) ** 0.5
+
+
+def mspf_segment_frames() -> int:
+    """The output frames one wave of the modulation-spectrum postfilter handles (csrc/mspf.hip)."""
+    return int(load_library().WorldMi355MspfSegmentFrames())
 
 
 def write_files(items, threads=16):

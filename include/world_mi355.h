@@ -284,7 +284,8 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
  * script's co = 2047 leaves out at most twice sum_{n > co} |freqt(w c)[n]| (5e-431 at order 49, alpha 0.55), far
  * below the float32 rounding of its intermediate files (1e-7).  Fields: alpha the `mgc` stream's warp ($fw), beta $pf_mcp
  * (config default 1.4), order m, length $fl = IMPLEN (4096), independent of the batch's fft_size.  hts_engine's -b
- * postfilter (:810), the LSP postfilter (:2690-2752) and the modulation-spectrum postfilter (:2950) are not offered. */
+ * postfilter (:810) and the LSP postfilter (:2690-2752) are not offered; the modulation-spectrum postfilter (:2950),
+ * which gen_wave runs INSTEAD of this one with USEMSPF, is WorldMi355ModulationSpectrumPostfilter below. */
 typedef struct {
   double alpha;
   double beta;
@@ -303,6 +304,57 @@ void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* opt);
  * stream; a batch of zero frames returns WM_OK. */
 int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const WorldMi355McpfOption* opt, double* out,
                                     double* gain, int* status);
+/* ---- Modulation-spectrum postfilter: postfiltering_mspf (scripts/Training.pl:2950-3000, msmp2seq :3003-3038), which
+ * gen_wave runs on every generated `.mgc` INSTEAD of postfiltering_mcp when the recipe is configured with USEMSPF=1,
+ * and the sums behind its statistics files (make_mspf, :3133-3221).  Settings: frame_length Lw ($mspfLength, odd),
+ * fft_length N ($mspfFFTLen), emphasis e ($mspfe{'mgc'}); S = (Lw - 1) / 2, K = N / 2 + 1.  For one utterance of T >= 1
+ * frames and one column x[0 .. T):
+ *   1  mu = mean(x), y = x - mu                                                        (vstat -o 1, vopr -s)
+ *   2  J = ceil((T + S) / S) frames, z_j[i] = w[i] y[j S - S + i], i < Lw, y = 0 outside [0, T), zeros up to N
+ *   3  w = SPTK's Bartlett window (window -w 3 -n 0): 2 i / (Lw - 1) for i < Lw / 2, else 2 - 2 i / (Lw - 1)
+ *   4  X_j = DFT_N(z_j), m_j[k] = 1/2 ln(|X_j[k]|^2 + 1e-30), k < K                    (spec -o 1 -e 1e-30)
+ *   5  m' = m + e (((m - mean_gen[k]) / std_gen[k]) std_nat[k] + mean_nat[k] - m)       (:2973-2982)
+ *   6  X'_j[k] = exp(m') X_j[k] / |X_j[k]| (exp(m') where X_j[k] = 0), v_j the N-point inverse real transform
+ *   7  seq[j S + n] += v_j[n] for all n < N (the circular tail included), out[t] = seq[S + t] + mu
+ * The statistics are the mean and the population standard deviation sqrt(E[m^2] - E[m]^2) of m per column and bin over
+ * every frame of every sequence, the all-zero trailing frames included, as the script counts them.  Two things are
+ * taken from SPTK's documented behaviour and were not confirmed against its binaries: the division by n in vstat's
+ * variance and the frame count of `frame`.  The script rounds to float32 at every pipe and to about 6 digits at
+ * `x2x +fa`; the library computes in double throughout (std_nat / std_gen is formed once per bin on the host).  A column
+ * that is zero after its mean has bins whose phase is rounding noise, which a std_nat / std_gen below 1 lifts out of
+ * the 1e-30 floor: there the script itself is unstable. */
+typedef struct {
+  int frame_length;
+  int fft_length;
+  double emphasis;
+} WorldMi355MspfOption;
+/* frame_length 25, fft_length 64, emphasis 1.0. */
+void WorldMi355DefaultMspfOption(WorldMi355MspfOption* opt);
+/* x, out: DEVICE double[total_frames][dim], out != x (a time segment reads its neighbours' input).  mean_gen, std_gen,
+ * mean_nat, std_nat: HOST double[dim][K], validated here and uploaded to the batch's workspace.  status: DEVICE
+ * int[n_utt] or NULL, a bit mask per utterance: 1 a column holds a non-finite input (or its mean overflows), 2 a result
+ * is not finite (exp overflowed).  Such a column is zeros in every frame of that utterance; nothing else is affected.
+ * A result depends on its own utterance and column alone: the same bits whatever the batch around it.  A NULL x, out
+ * or table, dim < 1, fft_length outside {16, 32, 64}, frame_length even, below 3 or above fft_length - 1, a non-finite
+ * emphasis or table entry, a std_gen entry <= 0, out == x: WM_ERR_BAD_ARG before any device call.  Asynchronous on the
+ * context's stream; a batch of zero frames returns WM_OK, an utterance of zero frames contributes nothing. */
+int WorldMi355ModulationSpectrumPostfilter(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
+                                           const double* mean_gen, const double* std_gen, const double* mean_nat,
+                                           const double* std_nat, double* out, int* status);
+/* Steps 1-4 over the batch: sum, sumsq: DEVICE double[dim][K], overwritten with the sums of m and m^2 over every frame
+ * of every utterance (per utterance in frame order, the utterances added in index order: no atomics, the same bits
+ * every time).  mean: DEVICE double[n_utt][dim] or NULL; NULL takes each utterance's own column means, non-NULL serves
+ * silence removal, where the mean is the whole utterance's and x holds the kept segments.  n_frames: HOST, receives the
+ * sum of J over the utterances, at once.  The caller adds across batches and finalises: mean = sum / n,
+ * std = sqrt(sumsq / n - mean^2).  Refusals as above. */
+int WorldMi355ModulationSpectrumStats(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
+                                      const double* mean, double* sum, double* sumsq, int64_t* n_frames);
+/* mean: DEVICE double[n_utt][dim], the column means of x per utterance (zeros for an utterance of zero frames, NaN for
+ * a column with a non-finite value), summed in a fixed order that depends on the utterance's length alone. */
+int WorldMi355ColumnMeans(WorldMi355Batch* b, const double* x, int dim, double* mean);
+/* The output frames one wave of the postfilter handles; longer utterances are cut into such segments, which does not
+ * change a bit of the result. */
+int WorldMi355MspfSegmentFrames(void);
 /* The 12-byte HTK header of addhtkheader.pl:60-75 (host only, native byte order). */
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]);
@@ -331,7 +383,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel").  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
