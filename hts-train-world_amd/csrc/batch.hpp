@@ -313,5 +313,17 @@ int check_mspf_stats(const double* d_x, int dim, const WorldMi355MspfOption* opt
 int launch_mspf_stats(Batch& b, hipStream_t st, const double* d_x, int dim, const WorldMi355MspfOption& opt,
                       const double* d_mean, double* d_sum, double* d_sumsq, int64_t* n_frames);
 int mspf_segment_frames();
+int check_interpolate_gaps(const float* d_x, int dim, double ignore_value, const float* d_out);
+int launch_interpolate_gaps(Batch& b, hipStream_t st, const float* d_x, int dim, double ignore_value, float* d_out,
+                            float* d_voiced, int* d_status);
+int check_compose_ffo(int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
+                      const double* const* const* windows, const int* const* window_sizes, const float* d_out);
+int launch_compose_ffo(Batch& b, hipStream_t st, int n_streams, const float* const* d_data, const int* dims,
+                       const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                       const float* const* d_msd, float* d_out);
+int check_column_moments(const float* d_x, int64_t ld, int width, const double* ignore_value, const int64_t* d_count,
+                         const double* d_mean, const double* d_m2);
+int launch_column_moments(Batch& b, hipStream_t st, const float* d_x, int64_t ld, int width, const double* ignore_value,
+                          int64_t* d_count, double* d_mean, double* d_m2);
 
 }  // namespace wm

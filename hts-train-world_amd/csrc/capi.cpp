@@ -395,6 +395,28 @@ int WorldMi355ModulationSpectrumStats(WorldMi355Batch* b, const double* x, int d
   OnDevice dev_(b->b.ctx[0]);
   return launch_mspf_stats(b->b, b->b.ctx->stream, x, dim, *opt, mean, sum, sumsq, n_frames);
 }
+int WorldMi355InterpolateGaps(WorldMi355Batch* b, const float* x, int dim, double ignore_value, float* out, float* voiced,
+                               int* status) {
+  if (const int rc = check_interpolate_gaps(x, dim, ignore_value, out)) return rc;   // refused before any device call
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_interpolate_gaps(b->b, b->b.ctx->stream, x, dim, ignore_value, out, voiced, status);
+}
+int WorldMi355ComposeFfo(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
+                         const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                         const float* const* msd, float* out) {
+  if (const int rc = check_compose_ffo(n_streams, streams, dims, n_windows, windows, window_sizes, out)) return rc;
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_compose_ffo(b->b, b->b.ctx->stream, n_streams, streams, dims, n_windows, windows, window_sizes, msd, out);
+}
+int WorldMi355ColumnMoments(WorldMi355Batch* b, const float* x, int64_t ld, int width, const double* ignore_value,
+                            int64_t* count, double* mean, double* m2) {
+  if (const int rc = check_column_moments(x, ld, width, ignore_value, count, mean, m2)) return rc;
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_column_moments(b->b, b->b.ctx->stream, x, ld, width, ignore_value, count, mean, m2);
+}
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
   const int32_t a = n_frames, fs100 = (int32_t)(10000000.0 * frame_shift_samples / sampling_rate);

@@ -599,10 +599,29 @@ struct CmpMeta {
   const float* data[kCmpMaxStreams];
 };
 
+// One value of the composed row: window wi of stream s at dim j of `frame`, whose utterance covers frames lo .. hi.
+// cmp_compose_kernel and ffo_compose_kernel (ffo.hip) both take their values from here.
+__device__ __forceinline__ float cmp_window_value(const CmpMeta& m, int s, int wi, int j, int64_t frame, int64_t lo,
+                                                  int64_t hi) {
+#pragma clang fp contract(off)
+  const int dim = m.dim[s];
+  const int size = m.wsize[s][wi], nlr = (size - 1) / 2;
+  const float* src = m.data[s];
+  bool boundary = false;
+  double acc = 0.0;
+  for (int k = 0; k < size; ++k) {
+    int64_t l = frame + (k - nlr);
+    l = l < lo ? lo : (l > hi ? hi : l);
+    const double v = (double)src[l * dim + j];
+    if (((m.chk[s][wi] >> k) & 1u) && v == -1.0e+10) boundary = true;
+    acc += m.w[s][wi][k] * v;
+  }
+  return boundary ? -1.0e+10f : (float)acc;
+}
+
 __global__ __launch_bounds__(256) void cmp_compose_kernel(CmpMeta m, const int* __restrict__ frame_utt,
                                                           const int64_t* __restrict__ f_off, int64_t total_frames,
                                                           float* __restrict__ out) {
-#pragma clang fp contract(off)
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total_frames * m.total_cols) return;
   const int64_t frame = idx / m.total_cols;
@@ -614,26 +633,14 @@ __global__ __launch_bounds__(256) void cmp_compose_kernel(CmpMeta m, const int* 
   const int dim = m.dim[s];
   const int c = col - m.col0[s];
   const int wi = c / dim, j = c - wi * dim;
-  const int size = m.wsize[s][wi], nlr = (size - 1) / 2;
   const int u = frame_utt[frame];
-  const int64_t lo = f_off[u], hi = f_off[u + 1] - 1;
-  const float* src = m.data[s];
-  bool boundary = false;
-  double acc = 0.0;
-  for (int k = 0; k < size; ++k) {
-    int64_t l = frame + (k - nlr);
-    l = l < lo ? lo : (l > hi ? hi : l);
-    const double v = (double)src[l * dim + j];
-    if (((m.chk[s][wi] >> k) & 1u) && v == -1.0e+10) boundary = true;
-    acc += m.w[s][wi][k] * v;
-  }
-  out[idx] = boundary ? -1.0e+10f : (float)acc;
+  out[idx] = cmp_window_value(m, s, wi, j, frame, f_off[u], f_off[u + 1] - 1);
 }
 
-int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
-                       const double* const* const* windows, const int* const* window_sizes, float* d_out) {
+// the streams' windows into m; col0 and total_cols are the `cmp` row's (ComposeCmp's and ComposeFfo's limits)
+static int cmp_fill_meta(CmpMeta& m, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
+                         const double* const* const* windows, const int* const* window_sizes) {
   if (n_streams < 1 || n_streams > kCmpMaxStreams) return WM_ERR_BAD_ARG;
-  CmpMeta m;
   memset(&m, 0, sizeof(m));
   m.n_streams = n_streams;
   int col = 0;
@@ -656,7 +663,14 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
     col += dims[s] * n_windows[s];
   }
   m.total_cols = col;
-  const int64_t n = b.total_f * col;
+  return WM_OK;
+}
+
+int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
+                       const double* const* const* windows, const int* const* window_sizes, float* d_out) {
+  CmpMeta m;
+  if (const int rc = cmp_fill_meta(m, n_streams, d_data, dims, n_windows, windows, window_sizes)) return rc;
+  const int64_t n = b.total_f * m.total_cols;
   if (n <= 0) return WM_OK;
   TimedScope ts_(b.ctx, b.ctx->stream, "cmp_compose_kernel");
   hipLaunchKernelGGL(cmp_compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, m,
@@ -680,3 +694,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "mcpf.hip"
 // ---- the branch gen_wave takes instead with USEMSPF: postfiltering_mspf and make_mspf's sums (the same arrangement) ---
 #include "mspf.hip"
+// ---- the two stages after `cmp`: gap interpolation, `ffo` rows and per-utterance column moments (the same arrangement) -
+#include "ffo.hip"

@@ -32,6 +32,12 @@ model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is th
 postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
 `mspf-stats` write (make_mspf, :3133-3221).
 
+The way out goes on after `cmp` (the reference's `analysis` target is `features cmp ffo stats`, data/Makefile.in:117):
+ffo_files() / `ffo` writes the frame-by-frame training targets (:325-412: interpolate.pl on the msd stream, its voicing
+flag, window.pl, merge), stats_files() / `stats` the variances gen_param_files() reads and the GV of the corpus
+(:414-459), gv_data_files() / `gv-data` the per-utterance variance vectors of GV training (make_data_gv,
+scripts/Training.pl:1402-1491).
+
 There is no CPU path: without a HIP device the library call fails.
 """
 from __future__ import annotations
@@ -411,6 +417,250 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
     return done
 
 
+# ---- training targets, their variances and the GV data (data/Makefile.in:325-459, Training.pl:1402-1491) -------------
+def _streams_arg(streams):
+    return [(int(d), [read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws],
+             bool(m)) for d, ws, m in streams]
+
+
+def _size_is(path, size):
+    try:
+        return os.path.getsize(str(path)) == size
+    except OSError:
+        return False
+
+
+def _stream_frames(jobs, dims, n_paths, what):
+    """Frames per job from the first stream file's size; every stream file of a job must hold as many rows."""
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != n_paths or size % (4 * dims[0]):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not %s" % (j[0], size, dims[0], what))
+        frames.append(size // (4 * dims[0]))
+        for path, dim in zip(j[1:len(dims)], dims[1:]):
+            other = os.path.getsize(path)
+            if other != 4 * dim * frames[-1]:
+                raise ValueError("%s has %g frames, %s has %d" % (path, other / (4.0 * dim), j[0], frames[-1]))
+    return frames
+
+
+def ffo_files(jobs, streams, unvoiced_value=-1.0e10, ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8,
+              resume=False):
+    """The recipe's `ffo` stage (data/Makefile.in:325-412) for a file list: the frame-by-frame training targets.
+
+    jobs:    [(stream_file_0, ..., stream_file_k, ffo_out)] -- float32 files [T][dim_s] in the row's order (mgc, lf0,
+             bap, vib); ffo_out: float32 [T][row width], the row of ffo_layout (no header)
+    streams: [(dim_s, [window files or coefficient lists], msd)], the triple gen_param_files takes
+    A stream with msd is interpolated across the frames that hold unvoiced_value (interpolate.pl), flagged (`sopr
+    -magic -1.0E+10 -m 0 -a 1 -MAGIC 0`, from its column 0) and windowed; the others are windowed (:373-408).  An
+    utterance whose msd stream has a column without a valid value is reported on stderr and its ffo is not written:
+    interpolate.pl dies there and the Makefile's `-s` tests skip the utterance.  Frame counts must agree across an
+    utterance's files.  Rank-sharded by frame count; with resume, utterances whose ffo file is complete are skipped.
+    Returns the frames composed."""
+    import torch
+    jobs = list(jobs)
+    streams = _streams_arg(streams)
+    ns = len(streams)
+    width = ffo_layout(streams)[1]
+    frames = _stream_frames(jobs, [d for d, _, _ in streams], ns + 1, "%d stream files and one output path" % ns)
+    todo = [i for i in range(len(jobs)) if frames[i] > 0 and not (resume and _size_is(jobs[i][ns], 4 * width * frames[i]))]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    if not mine:
+        return 0
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    done = 0
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+            dev, bad = [], np.zeros(len(group), dtype=np.int32)
+            for s_, (dim, wins, msd) in enumerate(streams):
+                parts = list(pool.map(lambda i: _f32(jobs[i][s_], dim), group))
+                x = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda()
+                if msd:
+                    x, voiced, status = b.interpolate_gaps(x, unvoiced_value)
+                    bad |= status.cpu().numpy()
+                    dev.append((x, wins, voiced))
+                else:
+                    dev.append((x, wins, None))
+            out = b.compose_ffo(dev).cpu().numpy()
+            fo = b.frame_offsets
+            for k, i in enumerate(group):
+                if bad[k]:
+                    print("warning: %s: a column of an msd stream holds no valid value, %s is not written" % (
+                        jobs[i][0], jobs[i][ns]), file=sys.stderr)
+                    continue
+                writes.append(pool.submit(np.ascontiguousarray(out[fo[k]:fo[k + 1]]).tofile, jobs[i][ns]))
+            done += int(b.total_frames)
+            b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return done
+
+
+def stats_files(ffo_paths, streams, out_dir, names=("mgc", "lf0", "bap", "vib"), ctx=None,
+                max_batch_frames=MAX_BATCH_FRAMES, io_threads=8):
+    """The recipe's `stats` stage (data/Makefile.in:414-459) over a list of ffo files.
+
+    ffo_paths: float32 files [T][row width] in the layout of `streams` (ffo_layout), what ffo_files writes
+    Writes out_dir/ffo.var: one float32 row, the variance of every ffo column over all frames of all files (`cat ffo/* |
+    vstat -d -o 2`, :440), the row gen_param_files takes as var_path; <name>.var per stream: its mean columns of that
+    row (:441-443), names in the streams' order; gv.var: the variance across utterances of the per-utterance variances
+    (:446-449), cut to the static columns of every stream in order (:454-456).
+    Variances divide by n: the reading of `vstat -o 2` that the modulation-spectrum statistics took.  SPTK is not
+    available to this project's tests, so the divisor is unconfirmed.  The reference guards its `stats` target so that
+    it runs only without WORLD or STRAIGHT (:416) and its row leaves out `vib`; here the layout is taken from `streams`.
+    The moments come per utterance from the device (count, mean, sum of squared deviations: never sum x^2) and are
+    pooled on the host in path order (world.pool_moments).  Rank-sharded by frame count: each rank pools its shard --
+    the moments, and a second triple over its per-utterance variances with count 1 each -- the triples are gathered
+    and merged in rank order, and rank 0 writes; several ranks need an initialised process group.  Returns the frames
+    counted."""
+    import torch
+    paths = [str(p) for p in ffo_paths]
+    streams = _streams_arg(streams)
+    layout, width = ffo_layout(streams)
+    if len(names) < len(streams):
+        raise ValueError("stats_files: %d streams but %d names" % (len(streams), len(names)))
+    frames = []
+    for p in paths:
+        size = os.path.getsize(p)
+        if size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32" % (p, size, width))
+        frames.append(size // (4 * width))
+    some = [i for i in range(len(paths)) if frames[i] > 0]            # a batch holds no utterance without frames
+    mine = sorted(some[k] for k in _my_share([frames[i] for i in some]))
+    rank, world = _rank_world()
+    at = {i: k for k, i in enumerate(mine)}
+    cnt = np.zeros((len(mine), width), dtype=np.int64)
+    mean, m2 = np.zeros((len(mine), width)), np.zeros((len(mine), width))
+    if mine:
+        own_ctx = ctx is None
+        ctx = ctx or _own_context()
+        with ThreadPoolExecutor(io_threads) as pool:
+            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+                rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(paths[i], width), group)))).cuda()
+                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+                c_, m_, s_ = (t.cpu().numpy() for t in b.column_moments(rows))
+                b.close()
+                sel = [at[i] for i in group]
+                cnt[sel], mean[sel], m2[sel] = c_, m_, s_
+        if own_ctx:
+            ctx.close()
+    corpus = W.pool_moments(cnt, mean, m2)                            # over frames
+    gv = W.pool_moments(np.ones_like(cnt), m2 / np.maximum(cnt, 1), np.zeros_like(m2))     # over utterances
+    if world > 1:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("stats_files with WORLD_SIZE > 1 needs torch.distributed to be initialised: the ranks' "
+                               "moments have to be merged")
+        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+        packed = torch.from_numpy(np.stack([a.astype(np.float64) for a in corpus + gv])).to(dev)    # counts < 2^53
+        parts = [torch.empty_like(packed) for _ in range(world)]
+        dist.all_gather(parts, packed)
+        parts = np.stack([p.cpu().numpy() for p in parts])            # [rank][6][width]
+        corpus = W.pool_moments(parts[:, 0].astype(np.int64), parts[:, 1], parts[:, 2])
+        gv = W.pool_moments(parts[:, 3].astype(np.int64), parts[:, 4], parts[:, 5])
+    n = int(corpus[0].max()) if width else 0
+    if rank == 0 and n > 0:
+        os.makedirs(str(out_dir), exist_ok=True)
+        var = (corpus[2] / corpus[0]).astype(np.float32)
+        var.tofile(os.path.join(str(out_dir), "ffo.var"))
+        gvar = (gv[2] / gv[0]).astype(np.float32)
+        for name, (_, c0, cols) in zip(names, layout):
+            var[c0:c0 + cols].tofile(os.path.join(str(out_dir), "%s.var" % name))
+        np.concatenate([gvar[c0:c0 + dim] for (_, c0, _), (dim, _, _) in zip(layout, streams)]).tofile(
+            os.path.join(str(out_dir), "gv.var"))
+    return n
+
+
+def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoiced_value=-1.0e10, ctx=None,
+                  max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """`make_data_gv` (scripts/Training.pl:1402-1491) for a file list: the per-utterance variance vectors that GV
+    training reads (gv/data/<base>.cmp).
+
+    jobs:     [(stream_file_0, ..., stream_file_k, label_file or None, cmp_out)] -- the streams' FEATURE files, float32
+              [T][dim_s]
+    streams:  [(dim_s, windows, msd)]: the triple of ffo_files; the windows are not used
+    sampling_rate, frame_shift: addhtkheader.pl's SAMPFREQ and FRAMESHIFT (samples); a frame is frame_shift /
+              sampling_rate seconds
+    silences: label names to drop ($nosilgv, :1422-1440); the rows kept are mspf_label_rows' (both ends inclusive)
+    Per utterance the variance (dividing by n, see stats_files) of every column of every stream; in a stream with msd,
+    values equal to unvoiced_value are dropped.  The script's `grep -v` drops single values and so shifts the columns of
+    a two-column stream when only one of them carries the value; here every column is counted on its own.  The output
+    is one HTK vector: htk_header(1, sampling_rate, frame_shift, 4 * sum dim, 9) and the float32 row (:1453).  An
+    utterance with a column without values or a variance that is not finite is reported on stderr and not written
+    (:1454-1458).  Rank-sharded by frame count; with resume, utterances whose file is complete are not computed again.
+    Returns the list of written (or, with resume, complete) paths of this rank in job order: the script's scp."""
+    import torch
+    jobs = [tuple(j) for j in jobs]
+    streams = _streams_arg([(d, ws if ws else [[1.0]], m) for d, ws, m in streams])
+    ns = len(streams)
+    dims = [d for d, _, _ in streams]
+    silences = tuple(silences)
+    shift_s = float(frame_shift) / float(sampling_rate)
+    frames = _stream_frames(jobs, dims, ns + 2, "%d stream files, a label and one output path" % ns)
+    size_out = 12 + 4 * sum(dims)
+    have = [resume and _size_is(j[ns + 1], size_out) for j in jobs]
+    todo = [i for i in range(len(jobs)) if not have[i]]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    written = {i for i in range(len(jobs)) if have[i] and _rank_world()[0] == 0}
+
+    def skip(i, why):
+        print("warning: %s: %s, %s is not written" % (jobs[i][0], why, jobs[i][ns + 1]), file=sys.stderr)
+
+    for i in [i for i in mine if frames[i] == 0]:
+        skip(i, "no frames")
+    mine = [i for i in mine if frames[i] > 0]
+    if mine:
+        own_ctx = ctx is None
+        ctx = ctx or _own_context()
+        with ThreadPoolExecutor(io_threads) as pool:
+            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+                keep = []
+                for i in group:
+                    if silences and jobs[i][ns]:
+                        with open(jobs[i][ns]) as f:
+                            keep.append(mspf_label_rows(f.readlines(), shift_s, frames[i], silences))
+                    else:
+                        keep.append(np.arange(frames[i], dtype=np.int64))
+                left = [k for k in range(len(group)) if len(keep[k]) > 0]
+                for k in range(len(group)):
+                    if len(keep[k]) == 0:
+                        skip(group[k], "no frames outside the silences")
+                if not left:
+                    continue
+                off = np.concatenate([[0], np.cumsum([frames[i] for i in group])])
+                index = torch.from_numpy(np.concatenate([keep[k] + off[k] for k in left])).cuda()
+                b = W.WorldBatch(ctx, W.default_params(sampling_rate, 5.0), f0_lengths=[len(keep[k]) for k in left])
+                var, cnt = [], []
+                for s_, (dim, _, msd) in enumerate(streams):
+                    parts = list(pool.map(lambda i: _f32(jobs[i][s_], dim), group))
+                    x = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda()[index].contiguous()
+                    c_, _, s2 = b.column_moments(x, ignore_value=unvoiced_value if msd else None)
+                    cnt.append(c_.cpu().numpy())
+                    var.append(s2.cpu().numpy() / np.maximum(cnt[-1], 1))
+                b.close()
+                cnt, var = np.concatenate(cnt, axis=1), np.concatenate(var, axis=1).astype(np.float32)
+                for r, k in enumerate(left):
+                    i = group[k]
+                    if (cnt[r] == 0).any():
+                        skip(i, "a column without values")
+                    elif not np.isfinite(var[r]).all():
+                        skip(i, "a variance that is not finite")
+                    else:
+                        with open(jobs[i][ns + 1], "wb") as f:
+                            f.write(W.htk_header(1, sampling_rate, frame_shift, 4 * sum(dims), 9))
+                            f.write(var[r].tobytes())
+                        written.add(i)
+        if own_ctx:
+            ctx.close()
+    return [jobs[i][ns + 1] for i in sorted(written)]
+
+
 # ---- mel-cepstral postfilter (scripts/Training.pl:2642-2687 postfiltering_mcp) ----------------------------------------
 def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
                      io_threads=8, resume=False):
@@ -776,7 +1026,50 @@ def main(argv=None):
             p.add_argument("--nat-stats", required=True, help="directory of the natural parameters' statistics")
             p.add_argument("--emphasis", type=float, default=1.0, help="mspfe")
             p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
+    stream_help = "one per stream in the row's order: dimension, 1 if the stream has a voicing column, window files"
+    p = sub.add_parser("ffo", help="the recipe's ffo stage: frame-by-frame training targets from the stream files")
+    p.add_argument("--scp", required=True, help="job list: one feature file per stream, then the ffo file to write")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help=stream_help)
+    p.add_argument("--unvoiced-value", type=float, default=-1.0e10, help="what an unvoiced frame of an msd stream holds")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose ffo file is already complete")
+    p = sub.add_parser("stats", help="the recipe's stats stage: ffo.var, <name>.var and gv.var of a list of ffo files")
+    p.add_argument("--scp", required=True, help="one ffo file per line")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help=stream_help)
+    p.add_argument("--out-dir", required=True)
+    p.add_argument("--name", action="append", default=[], help="a stream's name, in order (default: mgc lf0 bap vib)")
+    p = sub.add_parser("gv-data", help="make_data_gv: the per-utterance variance vectors of GV training")
+    p.add_argument("--scp", required=True, help="job list: one feature file per stream, the label file ('-' for none), "
+                   "then the cmp file to write")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help=stream_help + " (the windows may be left empty)")
+    p.add_argument("--sampling-rate", type=int, required=True)
+    p.add_argument("--frame-shift", type=int, required=True, help="samples per frame")
+    p.add_argument("--silence", action="append", default=[], help="a label name to drop (may be repeated)")
+    p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
+    p.add_argument("--resume", action="store_true", help="skip utterances whose cmp file is already complete")
     a = ap.parse_args(argv)
+    if a.cmd == "ffo":
+        n = ffo_files(_read_scp(a.scp, len(a.stream) + 1), a.stream, a.unvoiced_value, resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "stats":
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                # torchrun: the ranks' moments are gathered
+            import torch
+            import torch.distributed as dist
+            torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+            if not dist.is_initialized():
+                dist.init_process_group(os.environ.get("WM_BACKEND", "nccl"))
+        n = stats_files([r[0] for r in _read_scp(a.scp, 1)], a.stream, a.out_dir, tuple(a.name) or ("mgc", "lf0", "bap", "vib"))
+        print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "gv-data":
+        jobs = [r[:-2] + (None if r[-2] == "-" else r[-2], r[-1]) for r in _read_scp(a.scp, len(a.stream) + 2)]
+        done = gv_data_files(jobs, a.stream, a.sampling_rate, a.frame_shift, a.silence, a.unvoiced_value, resume=a.resume)
+        for path in done:
+            print(path)
+        return 0
     if a.cmd == "mspf-stats":
         jobs = [(f, None if lab == "-" else lab) for f, lab in _read_scp(a.scp, 2)]
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:                # torchrun: the ranks' sums are all-reduced

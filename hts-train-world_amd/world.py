@@ -130,6 +130,9 @@ def load_library():
     L.WorldMi355ColumnMeans.argtypes = [vp, vp, C.c_int, vp]
     L.WorldMi355MspfSegmentFrames.argtypes = []
     L.WorldMi355ComposeCmp.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.WorldMi355InterpolateGaps.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp]
+    L.WorldMi355ComposeFfo.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.WorldMi355ColumnMoments.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(C.c_double), vp, vp, vp]
     L.WorldMi355DefaultMlpgOption.restype = None
     L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
     L.WorldMi355ParameterGeneration.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp,
@@ -548,6 +551,92 @@ class WorldBatch:
                                                    C.c_void_p(out.data_ptr())), "ComposeCmp")
         return out
 
+    def _f32_rows(self, x, where, contiguous=True):
+        import torch
+        if (x.dim() != 2 or x.shape[0] != self.total_frames or x.shape[1] < 1 or x.dtype != torch.float32
+                or not x.is_cuda or x.stride(1) != 1 or (contiguous and not x.is_contiguous())):
+            raise ValueError(f"{where}: x must be a {'contiguous ' if contiguous else ''}float32 cuda tensor "
+                             f"[{self.total_frames}][dim], got {x.dtype} {tuple(x.shape)}")
+        return int(x.shape[1])
+
+    def interpolate_gaps(self, x, ignore_value=-1e10):
+        """data/scripts/interpolate.pl per utterance and column: x float32 cuda [total_frames][dim]; a value equal to
+        float32(ignore_value) is a gap (-1e10 the scripts', 0 the analysis CLI's unvoiced lf0, 1e-8 Extract.py's).
+        Returns (out float32 [total_frames][dim]: gaps between valid frames on the line through them, leading and
+        trailing gaps at the nearest valid value, with the script's bits; voiced float32 [total_frames]: 1 where column
+        0 is valid, else 0; status int32 [n_utt]: bit 1 a column without a valid value, which is zeros in out)."""
+        import torch
+        dim = self._f32_rows(x, "interpolate_gaps")
+        if not np.isfinite(float(ignore_value)):
+            raise ValueError(f"interpolate_gaps: ignore_value must be finite, got {ignore_value}")
+        out = torch.empty_like(x)
+        voiced = torch.empty(self.total_frames, dtype=torch.float32, device="cuda")
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _check(load_library().WorldMi355InterpolateGaps(self.handle, ptr(x), dim, float(ignore_value), ptr(out),
+                                                        ptr(voiced), ptr(status)), "InterpolateGaps")
+        return out, voiced, status
+
+    def compose_ffo(self, streams):
+        """An `ffo` row (data/Makefile.in:373-408, recipe.ffo_layout): streams is a list of (float32 cuda tensor
+        [total_frames][dim], list of window coefficient lists, msd float32 cuda [total_frames] or None).  A stream with
+        msd gets that value as one column in front of its windows; the windows are compose_cmp's.  Returns float32
+        [total_frames][row width]."""
+        import torch
+        n = len(streams)
+        if n < 1:
+            raise ValueError("compose_ffo: no streams")
+        dp = C.POINTER(C.c_double)
+        keep, wptrs, sptrs = [], (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
+        for s, (t, wins, msd) in enumerate(streams):
+            self._f32_rows(t, "compose_ffo")
+            if len(wins) < 1 or any(len(w) < 1 for w in wins):
+                raise ValueError("compose_ffo: a stream needs at least one window, a window at least one coefficient")
+            if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and msd.is_contiguous()
+                                        and tuple(msd.shape) == (self.total_frames,)):
+                raise ValueError(f"compose_ffo: msd must be a contiguous float32 cuda tensor [{self.total_frames}]")
+            arrs = [(C.c_double * len(w))(*w) for w in wins]
+            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
+            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
+            keep += [arrs, pa, sz]
+            wptrs[s] = C.cast(pa, C.POINTER(dp))
+            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        data = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t, _, _ in streams])
+        msds = (C.c_void_p * n)(*[C.c_void_p(None if m is None else m.data_ptr()) for _, _, m in streams])
+        dims = (C.c_int * n)(*[int(t.shape[1]) for t, _, _ in streams])
+        nwin = (C.c_int * n)(*[len(w) for _, w, _ in streams])
+        cols = sum(int(t.shape[1]) * len(w) + (0 if m is None else 1) for t, w, m in streams)
+        out = torch.empty(self.total_frames, cols, dtype=torch.float32, device="cuda")
+        _check(load_library().WorldMi355ComposeFfo(self.handle, n, data, dims, nwin, wptrs, sptrs, msds,
+                                                   C.c_void_p(out.data_ptr())), "ComposeFfo")
+        return out
+
+    def column_moments(self, x, width=None, ignore_value=None):
+        """Per-utterance moments of the first `width` columns (all of them by default) of x, float32 cuda
+        [total_frames][...]: a column view of a wider matrix is taken as it is, by its row stride.  With ignore_value, a
+        value equal to float32(ignore_value) is left out of its own column.  Returns (count int64, mean float64, m2
+        float64), all cuda [n_utt][width]: the kept values, their mean, and the sum of (x - mean)^2 around it in double
+        (two passes); a count of 0 gives mean 0 and m2 0.  The bits do not depend on the batch around an utterance."""
+        import torch
+        cols = self._f32_rows(x, "column_moments", contiguous=False)
+        width = cols if width is None else int(width)
+        if width < 1 or width > cols:
+            raise ValueError(f"column_moments: width must be in 1 .. {cols}, got {width}")
+        ld = int(x.stride(0)) if self.total_frames > 1 else max(int(x.stride(0)), width)
+        if ld < width:
+            raise ValueError(f"column_moments: the row stride {ld} is smaller than width {width}")
+        ig = None
+        if ignore_value is not None:
+            if not np.isfinite(float(ignore_value)):
+                raise ValueError(f"column_moments: ignore_value must be finite, got {ignore_value}")
+            ig = C.byref(C.c_double(float(ignore_value)))
+        count = torch.empty(self.n_utt, width, dtype=torch.int64, device="cuda")
+        mean, m2 = self._new(self.n_utt, width), self._new(self.n_utt, width)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _check(load_library().WorldMi355ColumnMoments(self.handle, ptr(x), ld, width, ig, ptr(count), ptr(mean),
+                                                      ptr(m2)), "ColumnMoments")
+        return count, mean, m2
+
     def parameter_generation(self, streams, var_per_frame=False, edge=0, input_type=0, unvoiced_value=-1e10):
         """SPTK's mlpg per stream, as gen_param runs it (scripts/Training.pl:2755-2810): the static trajectory c that
         solves (W' P W) c = W' P mean.  streams: list of (mean, var, windows, msd_or_None).  mean: float32 cuda
@@ -636,6 +725,31 @@ def mspf_finalize(sum, sumsq, n):
     batches and ranks): (mean, std) with std the population standard deviation sqrt(E[m^2] - E[m]^2)."""
     mean = sum / n
     return mean, (sumsq / n - mean * mean).clip(0) ** 0.5
+
+
+def pool_moments(count, mean, m2):
+    """(n, mean, M2) of the union of parts given by their own: count, mean, m2 are arrays [parts][width] (numpy or
+    tensors) -- column_moments' rows, or triples pooled earlier (another rank's), stacked.  Chan's merge in float64 on
+    the host, in index order: n = sum n_u, mean = sum n_u m_u / n, M2 = sum M2_u + sum n_u (m_u - mean)^2.  A part with
+    count 0 contributes nothing; n = 0 gives mean 0 and M2 0.  The variance of the union is M2 / n."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    cnt, mu, ss = host(count), np.asarray(host(mean), dtype=np.float64), np.asarray(host(m2), dtype=np.float64)
+    if cnt.ndim != 2 or mu.shape != cnt.shape or ss.shape != cnt.shape:
+        raise ValueError(f"pool_moments: count, mean and m2 must share one shape [parts][width], got {cnt.shape}, "
+                         f"{mu.shape}, {ss.shape}")
+    if (cnt < 0).any() or (cnt != np.floor(cnt)).any():
+        raise ValueError("pool_moments: counts must be whole numbers >= 0")
+    nf = cnt.astype(np.float64)
+    width = cnt.shape[1]
+    n, s1, tot = np.zeros(width, dtype=np.int64), np.zeros(width), np.zeros(width)
+    for u in range(cnt.shape[0]):
+        n += cnt[u].astype(np.int64)
+        s1 += nf[u] * np.where(nf[u] > 0, mu[u], 0.0)
+    pooled = np.where(n > 0, s1 / np.maximum(n, 1), 0.0)
+    for u in range(cnt.shape[0]):
+        d = np.where(nf[u] > 0, mu[u] - pooled, 0.0)
+        tot += np.where(nf[u] > 0, ss[u], 0.0) + nf[u] * (d * d)
+    return n, pooled, tot
 
 
 def mspf_segment_frames() -> int:

@@ -355,6 +355,41 @@ int WorldMi355ColumnMeans(WorldMi355Batch* b, const double* x, int dim, double* 
 /* The output frames one wave of the postfilter handles; longer utterances are cut into such segments, which does not
  * change a bit of the result. */
 int WorldMi355MspfSegmentFrames(void);
+/* ---- The stages after `cmp`: the recipe's `ffo` and `stats` targets (data/Makefile.in:325-459) and the data of GV
+ * training (make_data_gv, scripts/Training.pl:1402-1491) rest on the three calls below.
+ *
+ * Gap interpolation, data/scripts/interpolate.pl:68-105.  x, out: DEVICE float32 [total_frames][dim], out != x.  A value
+ * is a gap when it equals (float)ignore_value: -1e10 (exact in float32) is the script's own comparison; 0 and 1e-8 are
+ * what this fork's analysis CLI and Extract.py leave in unvoiced frames.  Per utterance and column: a gap between the
+ * valid frames lo < t < hi becomes (float)(a + step (t - lo)), a = (double)x[lo], step = ((double)x[hi] - a) / (hi - lo),
+ * in double with the product and the sum rounded separately, which gives the script's bits; a leading gap takes the
+ * first valid value, a trailing gap the last; valid frames are copied.  NaN is a valid value and propagates.
+ * voiced: NULL, or DEVICE float32 [total_frames]: 1.0 where column 0 of x is valid, else 0.0 (`sopr -magic -1.0E+10
+ * -m 0 -a 1 -MAGIC 0`, Makefile.in:347/:381).  status: NULL, or DEVICE int[n_utt]: bit 1 a column of the utterance holds
+ * no valid value (the script dies with "no valid value"); that column is zeros in out, nothing else is affected.  An
+ * utterance never reads another's frames; a result depends on its own utterance and column alone.  A NULL x or out,
+ * dim < 1, out == x, a non-finite ignore_value: WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's
+ * stream; a batch of zero frames returns WM_OK. */
+int WorldMi355InterpolateGaps(WorldMi355Batch* b, const float* x, int dim, double ignore_value, float* out, float* voiced,
+                              int* status);
+/* An `ffo` row (Makefile.in:373-408): WorldMi355ComposeCmp's arguments and results, and msd: NULL, or per stream NULL
+ * or DEVICE float32 [total_frames], which becomes ONE column in front of that stream's windows:
+ *   out[frame] = [stream 0: msd, if any | window 0 (dim) | window 1 | ...][stream 1: ...]...
+ * Limits as ComposeCmp; a limit exceeded or a NULL required pointer: WM_ERR_BAD_ARG before any device call. */
+int WorldMi355ComposeFfo(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
+                         const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                         const float* const* msd, float* out);
+/* Per-utterance column moments.  x: DEVICE float32, row t of the batch at x + t * ld, ld >= width: a column view of a
+ * wider matrix works as it is.  ignore_value: HOST pointer or NULL; when given, a value equal to (float)*ignore_value is
+ * left out of its own column (make_data_gv's `grep -v '1e+10'`, :1448, counted per column).  count, mean, m2: DEVICE
+ * [n_utt][width]: the number of kept values, their mean, and the sum of (x - mean)^2 around that computed mean, both in
+ * double -- two passes, not sum x^2.  A count of 0 gives mean 0 and m2 0.  Summed in a fixed order that depends on the
+ * utterance's length alone (WorldMi355ColumnMeans' order): the same bits whatever the batch around the utterance, no
+ * atomics.  width is taken 64 columns per block and has no limit of its own.  A NULL x, count, mean or m2, width < 1,
+ * ld < width, a non-finite *ignore_value: WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's stream;
+ * a batch of zero frames returns WM_OK. */
+int WorldMi355ColumnMoments(WorldMi355Batch* b, const float* x, int64_t ld, int width, const double* ignore_value,
+                            int64_t* count, double* mean, double* m2);
 /* The 12-byte HTK header of addhtkheader.pl:60-75 (host only, native byte order). */
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]);
@@ -383,7 +418,8 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
+ * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel").  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
