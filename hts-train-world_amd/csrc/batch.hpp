@@ -241,7 +241,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
@@ -298,6 +298,17 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
                 const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
                 const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
                 const WorldMi355MlpgOption& opt, float* const* out, int* d_status);
+int check_trj(int n_streams, const float* const* pred, const float* const* obs, int64_t ld, const float* const* var,
+              const float* const* gv_var, const int* dims, const int* n_windows, const double* const* const* windows,
+              const int* const* window_sizes, const float* const* msd_pred, const float* const* msd_obs,
+              const float* const* msd_var, const WorldMi355TrajectoryOption* opt, const double* cost,
+              float* const* grad_pred, float* const* grad_msd, int64_t ld_grad);
+int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred, const float* const* obs, int64_t ld,
+               const float* const* var, const float* const* gv_var, const int* dims, const int* n_windows,
+               const double* const* const* windows, const int* const* window_sizes, const float* const* msd_pred,
+               const float* const* msd_obs, const float* const* msd_var, const WorldMi355TrajectoryOption& opt,
+               double* cost, float* const* c, float* const* grad_pred, float* const* grad_msd, int64_t ld_grad,
+               double* grad_var, int* d_status);
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);

@@ -353,6 +353,28 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
   return launch_mlpg(b->b, b->b.ctx->stream, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows,
                      window_sizes, msd, *opt, out, status);
 }
+void WorldMi355DefaultTrajectoryOption(WorldMi355TrajectoryOption* o) {         // DNNDefine.py:248-249
+  if (!o) return;
+  o->edge = 0;
+  o->msd_weight = 1.0;
+  o->gv_weight = 1.0e-6;
+}
+int WorldMi355TrajectoryCost(WorldMi355Batch* b, int n_streams, const float* const* pred, const float* const* obs,
+                             int64_t ld, const float* const* var, const float* const* gv_var, const int* dims,
+                             const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                             const float* const* msd_pred, const float* const* msd_obs, const float* const* msd_var,
+                             const WorldMi355TrajectoryOption* opt, double* cost, float* const* c,
+                             float* const* grad_pred, float* const* grad_msd, int64_t ld_grad, double* grad_var,
+                             int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_trj(n_streams, pred, obs, ld, var, gv_var, dims, n_windows, windows, window_sizes, msd_pred,
+                               msd_obs, msd_var, opt, cost, grad_pred, grad_msd, ld_grad))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_trj(b->b, b->b.ctx->stream, n_streams, pred, obs, ld, var, gv_var, dims, n_windows, windows,
+                    window_sizes, msd_pred, msd_obs, msd_var, *opt, cost, c, grad_pred, grad_msd, ld_grad, grad_var,
+                    status);
+}
 void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* o) {                     // SPTK's alpha and order, the recipe's beta and IMPLEN
   if (!o) return;
   o->alpha = 0.35;

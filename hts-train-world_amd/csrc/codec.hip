@@ -696,3 +696,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "mspf.hip"
 // ---- the two stages after `cmp`: gap interpolation, `ffo` rows and per-utterance column moments (the same arrangement) -
 #include "ffo.hip"
+// ---- the criterion of trajectory training on the same banded factor: DNNDefine.trajectory_cost (the same arrangement) -
+#include "trj.hip"

@@ -32,6 +32,10 @@ model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is th
 postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
 `mspf-stats` write (make_mspf, :3133-3221).
 
+trajectory_files() / `trj-eval` stands where gen_param_files() stands when the model was trained by trajectory training
+($TRJGV, scripts/Training.pl:930-940): the outputs and the cost of DNNDefine.trajectory_cost; the loss itself, for a
+torch model, is training.TrajectoryLoss.
+
 The way out goes on after `cmp` (the reference's `analysis` target is `features cmp ffo stats`, data/Makefile.in:117):
 ffo_files() / `ffo` writes the frame-by-frame training targets (:325-412: interpolate.pl on the msd stream, its voicing
 flag, window.pl, merge), stats_files() / `stats` the variances gen_param_files() reads and the GV of the corpus
@@ -415,6 +419,92 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
     if own_ctx:
         ctx.close()
     return done
+
+
+# ---- trajectory training's criterion and outputs (scripts/Training.pl:930-940, DNNDefine.trajectory_cost) --------------
+def trajectory_rows(streams):
+    """float32 values per row of what trajectory_files writes: per stream its voicing column, when it has one, then dim."""
+    return sum(int(d) + (1 if m else 0) for d, _, m in streams)
+
+
+def trajectory_files(jobs, streams, var_path, gv_path, msd_weight=1.0, gv_weight=1.0e-6, ctx=None,
+                     max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """What DNNSynthesis.py does with a model trained by trajectory training ($TRJGV), for a file list: the rows of
+    DNNDefine.trajectory_cost's final_outputs and, where the targets are given, the cost of every utterance.
+
+    jobs:     [(pred_ffo, obs_ffo or None, out or None)] -- pred_ffo: float32 rows of the model's output in the ffo
+              layout; obs_ffo: the targets in the same layout (ffo_files writes them); out: float32 [T][sum_s (msd_s +
+              dim_s)], per stream the predicted voicing column, when it has one, then the trajectory c
+    streams:  [(dim_s, [window files or coefficient lists, the static window first], msd)] as gen_param_files takes them
+    var_path: one float32 row in the ffo layout (ffo.var or the trained variances); gv_path: gv.var, one float32 row
+              over the static columns of all streams in order
+    With obs_ffo the rows and the cost come from WorldBatch.trajectory_cost; without it the trajectories are
+    parameter_generation's (edge 0, no voicing mask) and no cost is evaluated.  Returns one entry per job: the cost
+    trj + msd_weight msd + gv_weight gv, or None (no targets; skipped by resume; another rank's; a flagged utterance,
+    which is reported on stderr and whose flagged columns are zeros).  Rank-sharded by frame count."""
+    import torch
+    from . import training
+    jobs = [tuple(j) for j in jobs]
+    streams = _streams_arg(streams)
+    layout, width = ffo_layout(streams)
+    out_cols = trajectory_rows(streams)
+    var = np.fromfile(var_path, dtype=np.float32)
+    if var.size != width:
+        raise ValueError("%s has %d values, an ffo row has %d" % (var_path, var.size, width))
+    need_gv = any(j[1] is not None for j in jobs)
+    if need_gv:
+        gv = np.fromfile(gv_path, dtype=np.float32)
+        if gv.size != sum(d for d, _, _ in streams):
+            raise ValueError("%s has %d values, the streams have %d static columns" % (gv_path, gv.size, sum(d for d, _, _ in streams)))
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 3 or size % (4 * width):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not (pred, obs, out)" % (j[0], size, width))
+        if j[1] is not None and os.path.getsize(j[1]) != size:
+            raise ValueError("%s and %s differ in size" % (j[0], j[1]))
+        frames.append(size // (4 * width))
+    todo = [i for i in range(len(jobs))
+            if not (resume and jobs[i][2] is not None and _size_is(jobs[i][2], 4 * frames[i] * out_cols))]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    dvar = torch.from_numpy(var).cuda()
+    dgv = torch.from_numpy(gv).cuda() if need_gv else None
+    costs = [None] * len(jobs)
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for with_obs in (True, False):
+            part = [i for i in mine if (jobs[i][1] is not None) == with_obs]
+            for group in _batches(sorted(part, key=lambda i: -frames[i]), frames, max_batch_frames):
+                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+                load = lambda col: torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][col], width), group)))).cuda()
+                pred = load(0)
+                if with_obs:
+                    cost, c, _, _, status = b.trajectory_cost(training.stream_views(pred, load(1), streams), dvar, dgv,
+                                                              msd_weight, gv_weight, want_grad_pred=False,
+                                                              want_grad_var=False)
+                    total = (cost[:, 0] + msd_weight * cost[:, 1] + gv_weight * cost[:, 2]).cpu().numpy()
+                else:
+                    c, status = b.parameter_generation([(pred[:, c0:c0 + n], dvar[c0:c0 + n], wins, None)
+                                                        for (_, c0, n), (_, wins, _) in zip(layout, streams)], edge=0)
+                status = status.cpu().numpy()
+                for k in np.nonzero(status)[0]:
+                    print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
+                          file=sys.stderr)
+                host = training.final_outputs(b, pred, c, streams).cpu().numpy()
+                fo = b.frame_offsets
+                for k, i in enumerate(group):
+                    if with_obs and status[k] == 0:
+                        costs[i] = float(total[k])
+                    if jobs[i][2] is not None:
+                        writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][2]))
+                b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return costs
 
 
 # ---- training targets, their variances and the GV data (data/Makefile.in:325-459, Training.pl:1402-1491) -------------
@@ -1001,6 +1091,17 @@ def main(argv=None):
     p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
     p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
     p.add_argument("--resume", action="store_true", help="skip utterances whose stream files are already complete")
+    p = sub.add_parser("trj-eval", help="trajectory training's outputs and cost (DNNDefine.trajectory_cost) of a list of "
+                       "ffo files")
+    p.add_argument("--scp", required=True, help="job list: the model's ffo rows, the target ffo rows ('-' for none: no "
+                   "cost), the file to write ('-' for none)")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help="one per stream in the row's order: dimension, 1 if a voicing column precedes it, window files")
+    p.add_argument("--var", required=True, help="one float32 row of variances in the ffo layout")
+    p.add_argument("--gv-var", required=True, help="gv.var: one float32 row over the static columns of all streams")
+    p.add_argument("--msd-weight", type=float, default=1.0)
+    p.add_argument("--gv-weight", type=float, default=1.0e-6)
+    p.add_argument("--resume", action="store_true", help="skip utterances whose output file is already complete")
     p = sub.add_parser("postfilter", help="postfiltering_mcp: formant emphasis on a list of mgc files")
     p.add_argument("--scp", required=True, help="job list: the mgc file, then the p_mgc file to write")
     p.add_argument("--order", type=int, required=True, help="order of the mel-cepstra: a row holds order + 1 float32")
@@ -1089,6 +1190,13 @@ def main(argv=None):
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)
         print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "trj-eval":
+        jobs = [(p_, None if o_ == "-" else o_, None if w_ == "-" else w_) for p_, o_, w_ in _read_scp(a.scp, 3)]
+        costs = trajectory_files(jobs, a.stream, a.var, a.gv_var, a.msd_weight, a.gv_weight, resume=a.resume)
+        for j, cost in zip(jobs, costs):
+            if cost is not None:
+                print("Evaluation: cost = %e (%s)" % (cost, j[0]))
         return 0
     if a.cmd == "gen-param":
         n = gen_param_files(_read_scp(a.scp, 1 + len(a.stream)), a.stream, a.var, a.edge, a.unvoiced_value,

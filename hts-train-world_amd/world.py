@@ -50,6 +50,11 @@ class MlpgOption(C.Structure):
                 ("unvoiced_value", C.c_double)]
 
 
+class TrajectoryOption(C.Structure):
+    """include/world_mi355.h: WorldMi355TrajectoryOption (the trajectory training criterion, DNNDefine.trajectory_cost)."""
+    _fields_ = [("edge", C.c_int), ("msd_weight", C.c_double), ("gv_weight", C.c_double)]
+
+
 class McpfOption(C.Structure):
     """include/world_mi355.h: WorldMi355McpfOption (the recipe's mel-cepstral postfilter, postfiltering_mcp)."""
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("order", C.c_int), ("length", C.c_int)]
@@ -137,6 +142,10 @@ def load_library():
     L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
     L.WorldMi355ParameterGeneration.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp,
                                                 C.POINTER(MlpgOption), vp, vp]
+    L.WorldMi355DefaultTrajectoryOption.restype = None
+    L.WorldMi355DefaultTrajectoryOption.argtypes = [C.POINTER(TrajectoryOption)]
+    L.WorldMi355TrajectoryCost.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           C.POINTER(TrajectoryOption), vp, vp, vp, vp, C.c_int64, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -707,6 +716,100 @@ class WorldBatch:
             wptrs, sptrs, vpn(*[ptr(t) for t in msds]), C.byref(o), vpn(*[ptr(t) for t in outs]),
             C.c_void_p(status.data_ptr())), "ParameterGeneration")
         return outs, status
+
+    def trajectory_cost(self, streams, var, gv_var, msd_weight=1.0, gv_weight=1.0e-6, want_c=True, want_grad_pred=True,
+                        want_grad_var=True):
+        """The recipe's trajectory training criterion with its gradients (DNNDefine.trajectory_cost,
+        data/scripts/DNNDefine.py:240-399), every utterance of the batch at once.  streams: list of (pred, obs, windows,
+        msd): pred and obs float32 cuda [total_frames][len(windows) * dim] laid as parameter_generation's mean -- tensors
+        of their own or column views of `ffo`-layout matrices (a model's output, the targets); of obs only the static
+        window is read.  msd: None, or (pred, obs) voicing columns, float32 cuda [total_frames].  var: float32 cuda, ONE
+        row in the `ffo` layout of these streams (per stream its voicing column's variance, when it has one, then
+        len(windows) * dim); gv_var: float32 cuda, one row over the static columns of all streams in order (gv.var).
+        Returns (cost float64 [n_utt][3]: trj, msd, gv -- an utterance's cost is trj + msd_weight msd + gv_weight gv;
+        c: per stream float32 [total_frames][dim]; grad_pred: float32 [total_frames][width] in the `ffo` layout, the
+        gradient of each utterance's cost in its own rows; grad_var: float64 [n_utt][width], per utterance; status int32
+        [n_utt]: bit 1 a non-finite pred or obs or a variance that is not positive and finite, bit 2 a matrix that is
+        not positive definite -- such an utterance has costs 0 and gradients 0).  An output that is not wanted is
+        None and is not computed."""
+        import torch
+        n, tf = len(streams), self.total_frames
+        for pred, obs, wins, msd in streams:
+            for t in (pred, obs):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == tf and len(wins) >= 1
+                        and t.shape[1] % len(wins) == 0 and t.shape == pred.shape):
+                    raise ValueError("trajectory_cost: pred and obs must be float32 cuda [total_frames][n_windows * dim]")
+            for t in msd or ():
+                if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (tf,)):
+                    raise ValueError("trajectory_cost: a voicing column must be float32 cuda [total_frames]")
+            if msd is not None and len(msd) != 2:
+                raise ValueError("trajectory_cost: msd is None or (pred column, obs column)")
+        dims = [int(p.shape[1]) // len(w) for p, _, w, _ in streams]
+        at, layout = 0, []                                             # (voicing column or None, first column, columns)
+        for p, _, _, msd in streams:
+            layout.append((at if msd is not None else None, at + (msd is not None), int(p.shape[1])))
+            at = layout[-1][1] + layout[-1][2]
+        width = at
+        if not (var.is_cuda and var.dtype == torch.float32 and tuple(var.shape) == (width,)):
+            raise ValueError(f"trajectory_cost: var must be float32 cuda [{width}], got {tuple(var.shape)}")
+        if not (gv_var.is_cuda and gv_var.dtype == torch.float32 and tuple(gv_var.shape) == (sum(dims),)):
+            raise ValueError(f"trajectory_cost: gv_var must be float32 cuda [{sum(dims)}], got {tuple(gv_var.shape)}")
+        var, gv_var = var.contiguous(), gv_var.contiguous()
+        # one row stride for pred, obs and the voicing columns: as given when they share one, else packed side by side
+        rows = [t for p, o, _, _ in streams for t in (p, o)]
+        cols = [t for _, _, _, msd in streams if msd is not None for t in msd]
+        keep = [rows, cols, var, gv_var]
+        if not (tf > 1 and len({int(t.stride(0)) for t in rows + cols}) == 1 and all(t.stride(1) == 1 for t in rows)):
+            mat = torch.cat(rows + [c[:, None] for c in cols], dim=1)
+            keep.append(mat)
+            at, r2, c2 = 0, [], []
+            for t in rows:
+                r2.append(mat[:, at:at + t.shape[1]])
+                at += int(t.shape[1])
+            for _ in cols:
+                c2.append(mat[:, at])
+                at += 1
+            rows, cols, ld = r2, c2, int(mat.shape[1])
+        else:
+            ld = int(rows[0].stride(0))
+        cols = iter(cols)
+        msds = [(next(cols), next(cols)) if msd is not None else None for _, _, _, msd in streams]
+        dp = C.POINTER(C.c_double)
+        vpn = C.c_void_p * n
+        wptrs, sptrs = (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
+        for s, (_, _, wins, _) in enumerate(streams):
+            arrs = [(C.c_double * len(w))(*w) for w in wins]
+            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
+            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
+            keep += [arrs, pa, sz]
+            wptrs[s] = C.cast(pa, C.POINTER(dp))
+            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        cost = torch.zeros(self.n_utt, 3, dtype=torch.float64, device="cuda")      # a batch of zero frames launches nothing
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        c = [torch.empty(tf, d, dtype=torch.float32, device="cuda") for d in dims] if want_c else None
+        grad_pred = torch.zeros(tf, width, dtype=torch.float32, device="cuda") if want_grad_pred else None
+        grad_var = torch.zeros(self.n_utt, width, dtype=torch.float64, device="cuda") if want_grad_var else None
+        o = TrajectoryOption()
+        load_library().WorldMi355DefaultTrajectoryOption(C.byref(o))
+        o.msd_weight, o.gv_weight = float(msd_weight), float(gv_weight)
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        esz, at = 4, 0
+        gv_ptrs = []
+        for d in dims:
+            gv_ptrs.append(C.c_void_p(gv_var.data_ptr() + esz * at))
+            at += d
+        col = lambda t, k: None if t is None or k is None else C.c_void_p(t.data_ptr() + esz * k)
+        _check(load_library().WorldMi355TrajectoryCost(
+            self.handle, n, vpn(*[ptr(t) for t in rows[0::2]]), vpn(*[ptr(t) for t in rows[1::2]]), ld,
+            vpn(*[col(var, c0) for _, c0, _ in layout]), vpn(*gv_ptrs), (C.c_int * n)(*dims),
+            (C.c_int * n)(*[len(w) for _, _, w, _ in streams]), wptrs, sptrs,
+            vpn(*[ptr(m and m[0]) for m in msds]), vpn(*[ptr(m and m[1]) for m in msds]),
+            vpn(*[col(var, mc) for mc, _, _ in layout]), C.byref(o), ptr(cost),
+            None if c is None else vpn(*[ptr(t) for t in c]),
+            None if grad_pred is None else vpn(*[col(grad_pred, c0) for _, c0, _ in layout]),
+            None if grad_pred is None else vpn(*[col(grad_pred, mc) for mc, _, _ in layout]), width, ptr(grad_var),
+            ptr(status)), "TrajectoryCost")
+        return cost, c, grad_pred, grad_var, status
 
     def split_frames(self, a):
         return [a[self.frame_offsets[u]:self.frame_offsets[u + 1]] for u in range(self.n_utt)]

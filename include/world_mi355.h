@@ -273,6 +273,49 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
                                   const double* const* const* windows, const int* const* window_sizes,
                                   const float* const* msd, const WorldMi355MlpgOption* opt, float* const* out,
                                   int* status);
+/* ---- Trajectory training criterion with gradients: DNNDefine.trajectory_cost (data/scripts/DNNDefine.py:240-399) as
+ * DNNTraining.py -w win drives it (scripts/Training.pl:930-940), for a whole batch of utterances.  Rows are in the `ffo`
+ * layout (per stream an optional voicing column, then [window 0: dim | window 1: dim | ...]); per column (utterance,
+ * stream, dimension) of T frames with the stream's windows, W_i as ParameterGeneration's W at edge 0 for window i alone:
+ *   A = sum_i p_i W_i' W_i,  c = A^-1 sum_i p_i W_i' mu_i,  e = o - c  (o the observed static),  p_i = 1 / var_i,
+ *   trj = (D T ln 2pi - sum_d ln det A_d + sum_d e_d' A_d e_d) / (2 D T),
+ *   msd = (M T ln 2pi + T sum_m ln var_m + sum_m sum_t (pred_m - obs_m)^2 / var_m) / (2 M T)     (0 when M = 0),
+ *   gv  = (D ln 2pi + sum_d ln gv_var_d + sum_d (pv_d - ov_d)^2 / gv_var_d) / (2 D),  pv, ov the variances over t of c, o,
+ *   utterance cost = trj + msd_weight msd + gv_weight gv,
+ * D the sum of dims, M the number of streams with a voicing column.  A is banded: the factor, ln det A, the band of
+ * A^-1 that the variance gradient needs and both solves cost O(T) per column, in double (float32 in).  Utterances never
+ * exchange data: an utterance's bits do not depend on the batch around it. */
+typedef struct {
+  int edge;               /* 0: taps beyond the utterance dropped, the reference's window matrix; nothing else is accepted */
+  double msd_weight;      /* default 1 */
+  double gv_weight;       /* default 1e-6 */
+} WorldMi355TrajectoryOption;
+void WorldMi355DefaultTrajectoryOption(WorldMi355TrajectoryOption* opt);   /* 0, 1, 1e-6 */
+/* pred[s], obs[s]: DEVICE, the stream's window 0 of row t at pred[s] + t * ld (n_windows[s] * dims[s] floats), as
+ *   ParameterGeneration's mean; of obs only the static window is read.  var[s]: DEVICE, ONE row of
+ *   n_windows[s] * dims[s] variances.  gv_var[s]: DEVICE, dims[s] variances of the per-utterance variance.
+ * dims, n_windows, windows, window_sizes: HOST, as ComposeCmp; window sizes 1, 3 or 5.
+ * msd_pred, msd_obs, msd_var: NULL (no stream has a voicing column), or per stream NULL or DEVICE: the voicing column
+ *   of row t at msd_pred[s] + t * ld, msd_obs[s] + t * ld, and its one variance at msd_var[s].
+ * cost: DEVICE double [n_utt][3]: trj, msd, gv.
+ * c: NULL, or per stream DEVICE float32 [total_frames][dims[s]], contiguous.
+ * grad_pred: NULL, or per stream DEVICE: the gradient of the utterance's cost with respect to pred, at
+ *   grad_pred[s] + t * ld_grad; grad_msd: NULL, or per stream NULL or DEVICE, the voicing column's, same stride.
+ * grad_var: NULL, or DEVICE double [n_utt][width], the gradient of each utterance's cost with respect to the variance
+ *   row in the `ffo` layout of the streams as given (width = sum_s [voicing column] + n_windows[s] * dims[s]).
+ * status: NULL, or DEVICE int[n_utt], a bit mask: 1 a non-finite pred or obs, or a variance (gv_var and the voicing
+ *   column's included) that is not positive and finite; 2 a pivot <= 0 (no static window).  A flagged utterance has
+ *   costs 0 and gradients 0, and c is zeros in the flagged columns; other utterances keep their bits.
+ * A count out of range (1-4 streams, 1-4 windows, dims >= 1), a NULL required pointer, ld (ld_grad with grad_pred
+ * or grad_msd) smaller than a stream's row, edge != 0, a window size even or above 5: WM_ERR_BAD_ARG before any device call.
+ * Asynchronous on the context's stream; a batch of zero frames returns WM_OK.  Timed as "trj_kernel". */
+int WorldMi355TrajectoryCost(WorldMi355Batch* b, int n_streams, const float* const* pred, const float* const* obs,
+                             int64_t ld, const float* const* var, const float* const* gv_var, const int* dims,
+                             const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                             const float* const* msd_pred, const float* const* msd_obs, const float* const* msd_var,
+                             const WorldMi355TrajectoryOption* opt, double* cost, float* const* c,
+                             float* const* grad_pred, float* const* grad_msd, int64_t ld_grad, double* grad_var,
+                             int* status);
 /* ---- Mel-cepstral postfilter: the recipe's formant emphasis, postfiltering_mcp (scripts/Training.pl:2642-2687), which
  * gen_wave (:2813-2845) runs on every generated `.mgc` before mgc2sp -- the stage between
  * WorldMi355ParameterGeneration and WorldMi355MelCepstrumToSpectrum.  For one frame c[0 .. order] at warp alpha and
@@ -419,7 +462,8 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
  * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
- * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
+ * column kernels and trj_reduce_kernel as one record).  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
