@@ -241,7 +241,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
@@ -309,6 +309,10 @@ int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred
                const float* const* msd_obs, const float* const* msd_var, const WorldMi355TrajectoryOption& opt,
                double* cost, float* const* c, float* const* grad_pred, float* const* grad_msd, int64_t ld_grad,
                double* grad_var, int* d_status);
+int check_dnn(int n_utt, const WorldMi355AcousticModel* m, const float* x, int64_t ld_x, const int* spkr, const float* out,
+              int64_t ld_out, const float* obs, int64_t ld_obs, const double* cost);
+int launch_dnn(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const float* x, int64_t ld_x, const int* spkr,
+               float* out, int64_t ld_out, const float* obs, int64_t ld_obs, double* cost, int* d_status);
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);

@@ -375,6 +375,15 @@ int WorldMi355TrajectoryCost(WorldMi355Batch* b, int n_streams, const float* con
                     window_sizes, msd_pred, msd_obs, msd_var, *opt, cost, c, grad_pred, grad_msd, ld_grad, grad_var,
                     status);
 }
+int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const float* x, int64_t ld_x,
+                                   const int* spkr, float* out, int64_t ld_out, const float* obs, int64_t ld_obs,
+                                   double* cost, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_dnn(b->b.n_utt, m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_dnn(b->b, b->b.ctx->stream, *m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, status);
+}
 void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* o) {                     // SPTK's alpha and order, the recipe's beta and IMPLEN
   if (!o) return;
   o->alpha = 0.35;

@@ -698,3 +698,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "ffo.hip"
 // ---- the criterion of trajectory training on the same banded factor: DNNDefine.trajectory_cost (the same arrangement) -
 #include "trj.hip"
+// ---- the network between `ffi` and `ffo`: DNNDefine.inference and the frame-level cost (the same arrangement) -
+#include "dnn.hip"

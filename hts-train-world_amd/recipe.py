@@ -36,6 +36,10 @@ trajectory_files() / `trj-eval` stands where gen_param_files() stands when the m
 ($TRJGV, scripts/Training.pl:930-940): the outputs and the cost of DNNDefine.trajectory_cost; the loss itself, for a
 torch model, is training.TrajectoryLoss.
 
+forward_files() / `dnn-forward` is the step in front of both (scripts/Training.pl:877, 906, 964, 993: DNNSynthesis.py
+frame by frame): the acoustic model's outputs for a list of `.ffi` files, the speaker's variance row and, where the
+targets are paired, the cost.
+
 The way out goes on after `cmp` (the reference's `analysis` target is `features cmp ffo stats`, data/Makefile.in:117):
 ffo_files() / `ffo` writes the frame-by-frame training targets (:325-412: interpolate.pl on the msd stream, its voicing
 flag, window.pl, merge), stats_files() / `stats` the variances gen_param_files() reads and the GV of the corpus
@@ -499,6 +503,88 @@ def trajectory_files(jobs, streams, var_path, gv_path, msd_weight=1.0, gv_weight
                         costs[i] = float(total[k])
                     if jobs[i][2] is not None:
                         writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][2]))
+                b.close()
+        for w_ in writes:
+            w_.result()
+    if own_ctx:
+        ctx.close()
+    return costs
+
+
+def read_forward_scp(path):
+    """The scp of Training.pl:1691-1722 as DNNDataIO.get_filenames reads it: a line is `ffi` or `ffi ffo`."""
+    jobs = []
+    with open(path) as f:
+        for ln in f:
+            if not ln.strip():
+                continue
+            if " " not in ln.rstrip("\n").rstrip():
+                jobs.append((ln.strip(), None))
+            else:
+                a, b_ = ln.split(" ", 1)
+                jobs.append((a.strip(), b_.strip()))
+    return jobs
+
+
+def forward_files(jobs, model_path, out_dir, spkr=None, extension="ffo", ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
+                  io_threads=8, max_chunk_frames=0, report=print):
+    """What DNNSynthesis.py does frame by frame (scripts/Training.pl:877, 906, 964, 993), for a file list: the model's
+    outputs for every `.ffi`, the speaker's variance row beside them and, where the targets are paired, the cost.
+
+    jobs:       [(ffi, ffo or None)] (read_forward_scp) -- ffi: float32 rows of the model's n_inputs; ffo: the targets
+    model_path: the `.npz` training.AcousticModel.save writes
+    spkr:       None: the last speaker, as the script (DNNSynthesis.py:139); or one index for every file
+    Writes <out_dir>/<base>.<extension> (the means in the ffo layout: what gen_param_files and trajectory_files read)
+    and <out_dir>/<base>.var (DNNSynthesis.py:202).  For every pair the cost is reported as `Evaluation: cost = %e (ffi)`:
+    the script's line (DNNSynthesis.py:233), whose parenthesis holds the elapsed time, with the file's name there instead,
+    since one run covers many files (as `trj-eval` does).
+    Returns one entry per job: the cost, or None (no targets; another rank's; a flagged utterance, which is reported on
+    stderr and whose rows are zeros).  Rank-sharded by frame count."""
+    import torch
+    from . import training
+    jobs = [tuple(j) if not isinstance(j, (str, os.PathLike)) else (j, None) for j in jobs]
+    model = training.AcousticModel.load(model_path)
+    n_in, n_out = model.n_inputs, model.n_outputs
+    s_id = model.n_spkrs - 1 if spkr is None else int(spkr)
+    if not 0 <= s_id < model.n_spkrs:
+        raise ValueError("speaker %d: the model has %d" % (s_id, model.n_spkrs))
+    frames = []
+    for j in jobs:
+        size = os.path.getsize(j[0])
+        if len(j) != 2 or size % (4 * n_in):
+            raise ValueError("%s: %d bytes are no rows of %d float32, or not (ffi, ffo)" % (j[0], size, n_in))
+        frames.append(size // (4 * n_in))
+        if j[1] is not None and os.path.getsize(j[1]) != 4 * n_out * frames[-1]:
+            raise ValueError("%s does not hold %d rows of %d float32, as %s asks" % (j[1], frames[-1], n_out, j[0]))
+    mine = [i for i in _my_share(frames) if frames[i] > 0]
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    model = model.cuda()
+    var_row = model.variance.variances[s_id].detach().to(torch.float32).cpu().numpy()
+    os.makedirs(str(out_dir), exist_ok=True)
+    costs = [None] * len(jobs)
+    with ThreadPoolExecutor(io_threads) as pool:
+        writes = []
+        for with_obs in (True, False):
+            part = [i for i in mine if (jobs[i][1] is not None) == with_obs]
+            for group in _batches(sorted(part, key=lambda i: -frames[i]), frames, max_batch_frames):
+                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+                load = lambda col, w: torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][col], w), group)))).cuda()
+                out, cost, status = model.infer(b, load(0, n_in), [s_id] * len(group), load(1, n_out) if with_obs else None,
+                                                max_chunk_frames)
+                host, status = out.cpu().numpy(), status.cpu().numpy()
+                cost = cost.cpu().numpy() if cost is not None else None
+                fo = b.frame_offsets
+                for k, i in enumerate(group):
+                    base = os.path.join(str(out_dir), os.path.splitext(os.path.basename(jobs[i][0]))[0])
+                    if status[k]:
+                        print("warning: %s: status %d, its rows are zeros" % (jobs[i][0], int(status[k])), file=sys.stderr)
+                    elif with_obs:
+                        costs[i] = float(cost[k])
+                        report("    Evaluation: cost = %e (%s)" % (costs[i], jobs[i][0]))
+                    writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile,
+                                              base + "." + extension if extension else base))
+                    writes.append(pool.submit(var_row.tofile, base + ".var"))
                 b.close()
         for w_ in writes:
             w_.result()
@@ -1102,6 +1188,13 @@ def main(argv=None):
     p.add_argument("--msd-weight", type=float, default=1.0)
     p.add_argument("--gv-weight", type=float, default=1.0e-6)
     p.add_argument("--resume", action="store_true", help="skip utterances whose output file is already complete")
+    p = sub.add_parser("dnn-forward", help="DNNSynthesis.py frame by frame: the acoustic model's outputs for a list of ffi "
+                       "files")
+    p.add_argument("--scp", required=True, help="one `ffi` or one `ffi ffo` pair per line (with targets: the cost)")
+    p.add_argument("--model", required=True, help="the .npz of training.AcousticModel.save")
+    p.add_argument("--out-dir", required=True, help="<base>.<extension> and <base>.var are written here")
+    p.add_argument("--extension", default="ffo")
+    p.add_argument("--spkr", type=int, default=None, help="speaker index (default: the last, as DNNSynthesis.py)")
     p = sub.add_parser("postfilter", help="postfiltering_mcp: formant emphasis on a list of mgc files")
     p.add_argument("--scp", required=True, help="job list: the mgc file, then the p_mgc file to write")
     p.add_argument("--order", type=int, required=True, help="order of the mel-cepstra: a row holds order + 1 float32")
@@ -1190,6 +1283,9 @@ def main(argv=None):
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)
         print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "dnn-forward":
+        forward_files(read_forward_scp(a.scp), a.model, a.out_dir, a.spkr, a.extension)
         return 0
     if a.cmd == "trj-eval":
         jobs = [(p_, None if o_ == "-" else o_, None if w_ == "-" else w_) for p_, o_, w_ in _read_scp(a.scp, 3)]

@@ -5,13 +5,19 @@ DNNDefine.trajectory_cost, data/scripts/DNNDefine.py:240-399), on whole batches 
 
 pred is the model's output in the `ffo` layout, var the trained variance row, obs the `ffo` targets and gv_var the
 content of gv.var.  The cost and both gradients come from one call of WorldBatch.trajectory_cost (csrc/trj.hip): nothing
-here computes them in torch.  The network, its optimiser, checkpoints and the data reader are the caller's."""
+here computes them in torch.
+
+AcousticModel is the recipe's network itself (DNNDefine.inference, data/scripts/DNNDefine.py:113-191) under the
+reference's parameter names: a plain torch forward for training with autograd, infer() for the forward pass of whole
+batches on the library's own kernel (csrc/dnn.hip), and save() / load() of one `.npz` -- the interchange format, since
+TF checkpoints cannot be read here.  Dropout, the optimiser, checkpoints and the data reader are the caller's."""
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from .recipe import ffo_layout
+from .world import ACTIVATIONS
 
 
 def stream_views(pred, obs, layout):
@@ -80,3 +86,119 @@ class TrajectoryLoss(torch.autograd.Function):
         if ctx.grad_var is not None:
             gv = (ctx.grad_var * g[:, None]).sum(0).to(torch.float32)
         return None, gp, gv, None, None, None, None, None, None
+
+
+def frame_cost(pred, obs, var):
+    """DNNDefine.cost (DNNDefine.py:231-237) in torch: 0.5 (ln 2 pi + mean ln var + mean (obs - pred)^2 / var)."""
+    import math
+    return 0.5 * (math.log(2.0 * math.pi) + torch.log(var).mean() + ((obs - pred) ** 2 / var).mean())
+
+
+def _activate(name, v):
+    return {"linear": lambda t: t, "sigmoid": torch.sigmoid, "tanh": torch.tanh, "relu": torch.relu}[name](v)
+
+
+def _truncated_normal(shape, std):
+    # tf.truncated_normal_initializer: values beyond two standard deviations are drawn again
+    return torch.nn.init.trunc_normal_(torch.empty(*shape), 0.0, std, -2.0 * std, 2.0 * std)
+
+
+class _Layer(torch.nn.Module):
+    def __init__(self, fan_in, fan_out, n_spkrs, sat):
+        super().__init__()
+        self.si_weights = torch.nn.Parameter(_truncated_normal((fan_in, fan_out), 1.0 / fan_in ** 0.5))
+        self.si_biases = torch.nn.Parameter(torch.zeros(fan_out))
+        if sat:
+            self.sd_weights = torch.nn.Parameter(_truncated_normal((n_spkrs, fan_out), 1.0 / n_spkrs ** 0.5))
+
+
+class _Variance(torch.nn.Module):
+    def __init__(self, n_spkrs, n_outputs):
+        super().__init__()
+        self.variances = torch.nn.Parameter(torch.ones(n_spkrs, n_outputs))
+
+
+class AcousticModel(torch.nn.Module):
+    """DNNDefine.inference: n_inputs -> units[0] -> ... -> n_outputs.  Parameters, as the reference names them:
+    hidden{i}.si_weights [fan_in][units[i]], hidden{i}.si_biases, hidden{i}.sd_weights [n_spkrs][units[i]] (SAT mode:
+    by default when there is more than one speaker), output.si_weights, output.si_biases, variance.variances
+    [n_spkrs][n_outputs]; initialised as DNNDefine.py:135-183 does (truncated normal of deviation 1 / sqrt(fan_in), for
+    the speaker rows 1 / sqrt(n_spkrs); biases 0; variances 1)."""
+
+    def __init__(self, n_inputs, units, n_outputs, n_spkrs=1, hidden_activation="sigmoid", output_activation="linear",
+                 sat=None):
+        super().__init__()
+        units = [int(n) for n in units]
+        if hidden_activation not in ACTIVATIONS or output_activation not in ACTIVATIONS:
+            raise ValueError("an activation is one of %s" % (ACTIVATIONS,))
+        if n_inputs < 1 or n_outputs < 1 or n_spkrs < 1 or any(n < 1 for n in units) or len(units) > 8:
+            raise ValueError("AcousticModel: at most 8 hidden layers; every width and n_spkrs at least 1")
+        self.n_inputs, self.units, self.n_outputs, self.n_spkrs = int(n_inputs), units, int(n_outputs), int(n_spkrs)
+        self.hidden_activation, self.output_activation = hidden_activation, output_activation
+        self.sat = n_spkrs > 1 if sat is None else bool(sat)
+        fan = [self.n_inputs] + units
+        for i, n in enumerate(units):
+            setattr(self, "hidden%d" % i, _Layer(fan[i], n, self.n_spkrs, self.sat))
+        self.output = _Layer(fan[-1], self.n_outputs, self.n_spkrs, False)
+        self.variance = _Variance(self.n_spkrs, self.n_outputs)
+
+    def hidden(self, i):
+        return getattr(self, "hidden%d" % i)
+
+    def forward(self, x, spkr=None):
+        """x: [rows][n_inputs]; spkr: None (the last speaker, DNNSynthesis.py:139), one index, or one index per row.
+        Returns the outputs [rows][n_outputs]; no dropout (the caller's, between the layers of its training step)."""
+        if spkr is None:
+            spkr = self.n_spkrs - 1
+        h = x
+        for i in range(len(self.units)):
+            L = self.hidden(i)
+            z = h @ L.si_weights + L.si_biases
+            if self.sat:
+                z = z + L.sd_weights[spkr]
+            h = _activate(self.hidden_activation, z)
+        return _activate(self.output_activation, h @ self.output.si_weights + self.output.si_biases)
+
+    def kernel_args(self):
+        """What WorldBatch.acoustic_model_forward takes: the module's own parameters, float32, not copied when they
+        already are."""
+        f = lambda t: t.detach().to(torch.float32)
+        layers = [self.hidden(i) for i in range(len(self.units))]
+        return {"weights": [f(L.si_weights) for L in layers] + [f(self.output.si_weights)],
+                "biases": [f(L.si_biases) for L in layers] + [f(self.output.si_biases)],
+                "spkr_weights": [f(L.sd_weights) for L in layers] if self.sat else None,
+                "variances": f(self.variance.variances), "n_spkrs": self.n_spkrs,
+                "hidden_activation": self.hidden_activation, "output_activation": self.output_activation}
+
+    def infer(self, batch, x, spkr=None, obs=None, max_chunk_frames=0):
+        """The forward pass of a WorldBatch on the library's kernel: (out, cost or None, status), see
+        WorldBatch.acoustic_model_forward.  spkr: None or one index per utterance."""
+        return batch.acoustic_model_forward(self, x, spkr, obs, max_chunk_frames)
+
+    def save(self, path):
+        """One `.npz`: float32 arrays under the parameters' names, and the two activation names."""
+        import numpy as np
+        arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.state_dict().items()}
+        arrays["hidden_activation"] = np.array(self.hidden_activation)
+        arrays["output_activation"] = np.array(self.output_activation)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            arrays = {k: z[k] for k in z.files}
+        n = 0
+        while "hidden%d.si_weights" % n in arrays:
+            n += 1
+        for k in ("output.si_weights", "output.si_biases", "variance.variances", "hidden_activation", "output_activation"):
+            if k not in arrays:
+                raise ValueError("%s: no %s" % (path, k))
+        units = [int(arrays["hidden%d.si_weights" % i].shape[1]) for i in range(n)]
+        wo, var = arrays["output.si_weights"], arrays["variance.variances"]
+        n_in = int(arrays["hidden0.si_weights"].shape[0]) if n else int(wo.shape[0])
+        m = cls(n_in, units, int(wo.shape[1]), int(var.shape[0]), str(arrays.pop("hidden_activation")),
+                str(arrays.pop("output_activation")), sat="hidden0.sd_weights" in arrays)
+        m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in arrays.items()})
+        return m

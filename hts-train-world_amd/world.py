@@ -55,6 +55,17 @@ class TrajectoryOption(C.Structure):
     _fields_ = [("edge", C.c_int), ("msd_weight", C.c_double), ("gv_weight", C.c_double)]
 
 
+class AcousticModelDesc(C.Structure):
+    """include/world_mi355.h: WorldMi355AcousticModel (the acoustic model's forward pass, DNNDefine.inference)."""
+    _fields_ = [("n_layers", C.c_int), ("n_inputs", C.c_int), ("n_outputs", C.c_int), ("n_spkrs", C.c_int),
+                ("hidden_activation", C.c_int), ("output_activation", C.c_int), ("units", C.POINTER(C.c_int)),
+                ("weights", C.POINTER(C.c_void_p)), ("biases", C.POINTER(C.c_void_p)),
+                ("spkr_weights", C.POINTER(C.c_void_p)), ("variances", C.c_void_p), ("max_chunk_frames", C.c_int64)]
+
+
+ACTIVATIONS = ("linear", "sigmoid", "tanh", "relu")      # Config.pm.in:228: the codes 0 .. 3
+
+
 class McpfOption(C.Structure):
     """include/world_mi355.h: WorldMi355McpfOption (the recipe's mel-cepstral postfilter, postfiltering_mcp)."""
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("order", C.c_int), ("length", C.c_int)]
@@ -146,6 +157,8 @@ def load_library():
     L.WorldMi355DefaultTrajectoryOption.argtypes = [C.POINTER(TrajectoryOption)]
     L.WorldMi355TrajectoryCost.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                            C.POINTER(TrajectoryOption), vp, vp, vp, vp, C.c_int64, vp, vp]
+    L.WorldMi355AcousticModelForward.argtypes = [vp, C.POINTER(AcousticModelDesc), vp, C.c_int64, vp, vp, C.c_int64, vp,
+                                                 C.c_int64, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -810,6 +823,86 @@ class WorldBatch:
             None if grad_pred is None else vpn(*[col(grad_pred, mc) for mc, _, _ in layout]), width, ptr(grad_var),
             ptr(status)), "TrajectoryCost")
         return cost, c, grad_pred, grad_var, status
+
+    def acoustic_model_forward(self, model, x, spkr=None, obs=None, max_chunk_frames=0):
+        """The forward pass of the recipe's acoustic model (DNNDefine.inference as DNNSynthesis.py runs it) and, with
+        targets, its frame-level cost (DNNDefine.cost), every utterance of the batch at once.  model: a mapping (or an
+        object whose kernel_args() returns one, such as training.AcousticModel) with "weights" (n_layers + 1 float32
+        cuda tensors [fan_in][fan_out], the last the output layer's), "biases" ([fan_out] each), "spkr_weights" (None,
+        or n_layers tensors [n_spkrs][units]), "variances" (None, or [n_spkrs][n_outputs]), "hidden_activation",
+        "output_activation" (a name of ACTIVATIONS or its code) and "n_spkrs".  x: float32 cuda
+        [total_frames][n_inputs], obs: None or float32 cuda [total_frames][n_outputs]; either may be a column view of a
+        wider matrix (its row stride is passed, nothing is copied).  spkr: None (n_spkrs - 1 for all), or one index per
+        utterance.  Returns (out float32 [total_frames][n_outputs], cost float64 [n_utt] or None without obs, status
+        int32 [n_utt]: bit 1 a non-finite x or obs, bit 2 a non-finite output or, with a cost, a variance that is not
+        positive and finite -- such an utterance has zero rows and cost 0)."""
+        import torch
+        m = model.kernel_args() if hasattr(model, "kernel_args") else model
+        tf = self.total_frames
+        code = lambda a: ACTIVATIONS.index(a) if isinstance(a, str) else int(a)
+        keep = []
+
+        def dev(t, shape, what):
+            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)):
+                raise ValueError(f"acoustic_model_forward: {what} must be float32 cuda {list(shape)}, got {tuple(t.shape)}")
+            t = t.detach().contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        def rows(t, width, what):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (tf, width)):
+                raise ValueError(f"acoustic_model_forward: {what} must be float32 cuda [{tf}][{width}]")
+            if tf > 0 and (t.stride(1) != 1 or (tf > 1 and t.stride(0) < width)):
+                t = t.contiguous()
+            keep.append(t)
+            return t, int(t.stride(0)) if tf > 1 else width
+
+        weights, biases = list(m["weights"]), list(m["biases"])
+        n_layers = len(weights) - 1
+        if n_layers < 0 or len(biases) != n_layers + 1 or weights[-1].dim() != 2 or any(w.dim() != 2 for w in weights):
+            raise ValueError("acoustic_model_forward: weights and biases are n_layers + 1 matrices and vectors")
+        n_in, n_out, n_spkrs = int(weights[0].shape[0]), int(weights[-1].shape[1]), int(m.get("n_spkrs", 1))
+        units = [int(w.shape[1]) for w in weights[:-1]]
+        fan = [n_in] + units
+        vpn = C.c_void_p * (n_layers + 1)
+        d = AcousticModelDesc()
+        d.n_layers, d.n_inputs, d.n_outputs, d.n_spkrs = n_layers, n_in, n_out, n_spkrs
+        d.hidden_activation, d.output_activation = code(m["hidden_activation"]), code(m["output_activation"])
+        ua = (C.c_int * max(n_layers, 1))(*units)
+        wa = vpn(*[dev(w, (fan[i], (units + [n_out])[i]), f"weights[{i}]") for i, w in enumerate(weights)])
+        ba = vpn(*[dev(t, ((units + [n_out])[i],), f"biases[{i}]") for i, t in enumerate(biases)])
+        keep += [ua, wa, ba]
+        d.units, d.weights, d.biases = ua, wa, ba
+        sd = m.get("spkr_weights")
+        if sd is not None:
+            if len(sd) != n_layers:
+                raise ValueError("acoustic_model_forward: spkr_weights has one matrix per hidden layer")
+            sa = (C.c_void_p * max(n_layers, 1))(*[dev(t, (n_spkrs, units[i]), f"spkr_weights[{i}]") for i, t in enumerate(sd)])
+            keep.append(sa)
+            d.spkr_weights = sa
+        var = m.get("variances")
+        if var is not None:
+            d.variances = dev(var, (n_spkrs, n_out), "variances")
+        d.max_chunk_frames = int(max_chunk_frames)
+        x, ld_x = rows(x, n_in, "x")
+        ld_obs = 0
+        if obs is not None:
+            if var is None:
+                raise ValueError("acoustic_model_forward: a cost needs the model's variances")
+            obs, ld_obs = rows(obs, n_out, "obs")
+        sp = None
+        if spkr is not None:
+            sp = np.ascontiguousarray(spkr, dtype=np.int32)
+            if sp.shape != (self.n_utt,):
+                raise ValueError(f"acoustic_model_forward: spkr has one index per utterance ({self.n_utt})")
+        out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda")
+        cost = torch.zeros(self.n_utt, dtype=torch.float64, device="cuda") if obs is not None else None
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        _check(load_library().WorldMi355AcousticModelForward(
+            self.handle, C.byref(d), ptr(x), ld_x, None if sp is None else sp.ctypes.data_as(C.c_void_p), ptr(out), n_out,
+            ptr(obs), ld_obs, ptr(cost), ptr(status)), "AcousticModelForward")
+        return out, cost, status
 
     def split_frames(self, a):
         return [a[self.frame_offsets[u]:self.frame_offsets[u + 1]] for u in range(self.n_utt)]

@@ -316,6 +316,40 @@ int WorldMi355TrajectoryCost(WorldMi355Batch* b, int n_streams, const float* con
                              const WorldMi355TrajectoryOption* opt, double* cost, float* const* c,
                              float* const* grad_pred, float* const* grad_msd, int64_t ld_grad, double* grad_var,
                              int* status);
+/* ---- Acoustic model forward pass: DNNDefine.inference (data/scripts/DNNDefine.py:113-191) as DNNSynthesis.py:129-229
+ * runs it (keep_prob 1), with the frame-level DNNDefine.cost (:231-237), for a whole batch of utterances: `.ffi` rows in,
+ * `ffo`-layout means out.  Per frame of utterance u with speaker s(u), float32, every addition rounded in this order:
+ *   h_{i+1} = act_h((h_i W_i + b_i) + sd_i[s(u)])   (the speaker row only with spkr_weights),   out = act_o(h_L W_o + b_o);
+ * a product h W is a k-ordered fmaf chain from zero (the exact-f32 matrix instruction).  With n_layers = 0 the inputs
+ * feed the output layer.  Cost per utterance of T frames, D = n_outputs, var = variances[s(u)], in double:
+ *   cost = (ln 2pi + (1 / D) sum_d ln var_d + (1 / (T D)) sum_t sum_d (obs - out)^2 / var_d) / 2.
+ * A row's result depends on that row of x and on the model alone: not on the chunking, not on the batch around it. */
+typedef struct {
+  int n_layers, n_inputs, n_outputs, n_spkrs;    /* n_layers 0 .. 8; n_spkrs >= 1 */
+  int hidden_activation, output_activation;      /* 0 linear, 1 sigmoid, 2 tanh, 3 relu (Config.pm.in:228) */
+  const int* units;                              /* HOST [n_layers] */
+  const float* const* weights;                   /* HOST array of n_layers + 1 DEVICE pointers, [fan_in][fan_out] */
+  const float* const* biases;                    /* likewise, [fan_out] */
+  const float* const* spkr_weights;              /* NULL (SD), or n_layers DEVICE pointers [n_spkrs][units[i]] */
+  const float* variances;                        /* DEVICE [n_spkrs][n_outputs], or NULL when no cost is asked */
+  int64_t max_chunk_frames;                      /* frames that go through the layers together; 0: 65 536; at most 2^20 */
+} WorldMi355AcousticModel;
+/* x: DEVICE, row t at x + t * ld_x (n_inputs floats).  spkr: HOST [n_utt], or NULL: n_spkrs - 1 for every utterance
+ *   (DNNSynthesis.py:139).  out: DEVICE, row t at out + t * ld_out (n_outputs floats).  obs: DEVICE, the targets, row t
+ *   at obs + t * ld_obs; read only with cost.  cost: NULL, or DEVICE double [n_utt].
+ * status: NULL, or DEVICE int[n_utt], a bit mask: 1 a non-finite value in the utterance's rows of x (of obs too when a
+ *   cost is asked); 2 a non-finite output of finite inputs, or, when a cost is asked, a variance of its speaker that is
+ *   not positive and finite.  A flagged utterance has zero rows in out and cost 0; other utterances keep their bits.
+ * A NULL required pointer, a count out of range (n_layers outside 0 .. 8, a unit count, n_inputs, n_outputs or n_spkrs
+ * below 1, max_chunk_frames below 0), an activation code outside 0 .. 3, a speaker index outside [0, n_spkrs), a leading
+ * dimension smaller than its row, cost without obs or without variances, a layer so wide that a chunk's 128 x 128 tiles
+ * exceed 2^31 - 1: WM_ERR_BAD_ARG before any device call.
+ * The hidden activations live in the batch's workspace (two [chunk][max units] float32 buffers, kept between calls).
+ * Asynchronous on the context's stream; a batch of zero frames returns WM_OK.  Timed as "dnn_layer_kernel" (the input
+ * check and all layers of a call as one record) and "dnn_cost_kernel". */
+int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const float* x, int64_t ld_x,
+                                   const int* spkr, float* out, int64_t ld_out, const float* obs, int64_t ld_obs,
+                                   double* cost, int* status);
 /* ---- Mel-cepstral postfilter: the recipe's formant emphasis, postfiltering_mcp (scripts/Training.pl:2642-2687), which
  * gen_wave (:2813-2845) runs on every generated `.mgc` before mgc2sp -- the stage between
  * WorldMi355ParameterGeneration and WorldMi355MelCepstrumToSpectrum.  For one frame c[0 .. order] at warp alpha and
@@ -463,7 +497,8 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
  * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
  * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
- * column kernels and trj_reduce_kernel as one record).  Enable clears earlier records; Query synchronises the stream and
+ * column kernels and trj_reduce_kernel as one record, "dnn_layer_kernel": all layers of a call as one record,
+ * "dnn_cost_kernel").  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
