@@ -313,6 +313,18 @@ int check_dnn(int n_utt, const WorldMi355AcousticModel* m, const float* x, int64
               int64_t ld_out, const float* obs, int64_t ld_obs, const double* cost);
 int launch_dnn(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const float* x, int64_t ld_x, const int* spkr,
                float* out, int64_t ld_out, const float* obs, int64_t ld_obs, double* cost, int* d_status);
+int check_dnn_train_forward(int n_utt, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop, const float* x,
+                            int64_t ld_x, const int* spkr, const float* out, int64_t ld_out, const float* obs, int64_t ld_obs,
+                            const double* cost, const float* grad_out, int64_t ld_grad, const double* grad_var);
+int launch_dnn_train_forward(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const WorldMi355Dropout* drop,
+                             const float* x, int64_t ld_x, const int* spkr, float* out, int64_t ld_out, const float* obs,
+                             int64_t ld_obs, double* cost, float* grad_out, int64_t ld_grad, double* grad_var, int* d_status);
+int check_dnn_backward(int n_utt, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop, const float* x,
+                       int64_t ld_x, const int* spkr, const float* grad_out, int64_t ld_grad, float* const* grad_weights,
+                       float* const* grad_biases, float* const* grad_spkr_weights);
+int launch_dnn_backward(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const WorldMi355Dropout* drop,
+                        const float* x, int64_t ld_x, const int* spkr, const float* G, int64_t ld_g, float* const* gW,
+                        float* const* gB, float* const* gS, int* d_status);
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);

@@ -384,6 +384,30 @@ int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticM
   OnDevice dev_(b->b.ctx[0]);
   return launch_dnn(b->b, b->b.ctx->stream, *m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, status);
 }
+int WorldMi355AcousticModelTrainForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
+                                        const float* x, int64_t ld_x, const int* spkr, float* out, int64_t ld_out,
+                                        const float* obs, int64_t ld_obs, double* cost, float* grad_out, int64_t ld_grad,
+                                        double* grad_var, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_dnn_train_forward(b->b.n_utt, m, drop, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, grad_out,
+                                             ld_grad, grad_var))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_dnn_train_forward(b->b, b->b.ctx->stream, *m, drop, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, grad_out,
+                                  ld_grad, grad_var, status);
+}
+int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
+                                    const float* x, int64_t ld_x, const int* spkr, const float* grad_out, int64_t ld_grad,
+                                    float* const* grad_weights, float* const* grad_biases, float* const* grad_spkr_weights,
+                                    int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_dnn_backward(b->b.n_utt, m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
+                                        grad_spkr_weights))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_dnn_backward(b->b, b->b.ctx->stream, *m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
+                             grad_spkr_weights, status);
+}
 void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* o) {                     // SPTK's alpha and order, the recipe's beta and IMPLEN
   if (!o) return;
   o->alpha = 0.35;

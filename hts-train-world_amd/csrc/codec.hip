@@ -700,3 +700,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "trj.hip"
 // ---- the network between `ffi` and `ffo`: DNNDefine.inference and the frame-level cost (the same arrangement) -
 #include "dnn.hip"
+// ---- its training pass: dropout, the backward pass and the cost gradients of DNNTraining.py (the same arrangement) -
+#include "dnn_train.hip"

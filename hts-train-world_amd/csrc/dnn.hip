@@ -297,6 +297,7 @@ struct DnnWs : StageWs {
                                     // been read or staged (as mspf.hip's h_tab and synthesis.hip's order rely on)
   int64_t cap = 0, cap_utt = 0;     // floats per buffer; utterances
   int n_buf = 0;
+  bool train = false;               // a DnnTrainWs (dnn_train.hip): this struct with the training pass's buffers behind it
 };
 
 static void dnn_launch_layer(int act, const DnnLayer& L, hipStream_t st) {

@@ -36,6 +36,8 @@ trajectory_files() / `trj-eval` stands where gen_param_files() stands when the m
 ($TRJGV, scripts/Training.pl:930-940): the outputs and the cost of DNNDefine.trajectory_cost; the loss itself, for a
 torch model, is training.TrajectoryLoss.
 
+train_files() / `dnn-train` is DNNTraining.py (SD and SAT; frame by frame, or with --stream trajectory training) on the
+library's training pass.
 forward_files() / `dnn-forward` is the step in front of both (scripts/Training.pl:877, 906, 964, 993: DNNSynthesis.py
 frame by frame): the acoustic model's outputs for a list of `.ffi` files, the speaker's variance row and, where the
 targets are paired, the cost.
@@ -591,6 +593,221 @@ def forward_files(jobs, model_path, out_dir, spkr=None, extension="ffo", ctx=Non
     if own_ctx:
         ctx.close()
     return costs
+
+
+# ---- the training loop: DNNTraining.py frame by frame, SD and SAT (scripts/Training.pl:850-870) ------------------------
+OPTIMIZERS = ("sgd", "momentum", "adagrad", "adadelta", "adam", "rmsprop")     # DNNDefine.get_optimizer (DNNDefine.py:65-80)
+
+
+def make_optimizer(model, name, learning_rate):
+    """DNNDefine.training's three groups (DNNDefine.py:194-213): the si_ parameters at learning_rate, the sd_ parameters
+    at learning_rate, the variances at 0.01 learning_rate -- as torch.optim's optimiser of that name with TF 1.x's
+    default hyper-parameters (momentum 0.9; Adagrad's accumulator 0.1; Adadelta rho 0.95, eps 1e-8; Adam 0.9, 0.999,
+    1e-8; RMSprop decay 0.9, eps 1e-10).  torch adds Adam's and RMSprop's eps outside the square root, TF inside it for
+    RMSprop and to a rescaled root for Adam; and TF 1.x starts RMSprop's mean-square slot at ones, torch at zeros, so
+    RMSprop's first steps are much larger here (the first about 1 / sqrt(0.1) times the rate, against about the gradient
+    times the rate in TF).  The trajectories are not TF's."""
+    import torch
+    named = list(model.named_parameters())
+    pick = lambda key: [p for k, p in named if k.split(".")[-1].startswith(key)]
+    groups = [{"params": pick("si_"), "lr": learning_rate}, {"params": pick("sd_"), "lr": learning_rate},
+              {"params": pick("variance"), "lr": 0.01 * learning_rate}]
+    groups = [g for g in groups if g["params"]]
+    name = name.lower()
+    if name == "sgd":
+        return torch.optim.SGD(groups, lr=learning_rate)
+    if name == "momentum":
+        return torch.optim.SGD(groups, lr=learning_rate, momentum=0.9)
+    if name == "adagrad":
+        return torch.optim.Adagrad(groups, lr=learning_rate, initial_accumulator_value=0.1, eps=0.0)
+    if name == "adadelta":
+        return torch.optim.Adadelta(groups, lr=learning_rate, rho=0.95, eps=1e-8)
+    if name == "adam":
+        return torch.optim.Adam(groups, lr=learning_rate, betas=(0.9, 0.999), eps=1e-8)
+    if name == "rmsprop":
+        return torch.optim.RMSprop(groups, lr=learning_rate, alpha=0.9, eps=1e-10)
+    raise ValueError("an optimiser is one of %s" % (OPTIMIZERS,))
+
+
+def minibatches(frame_spkr, batch_size, n_steps, seed, start=0):
+    """The frame-by-frame minibatches of steps start .. start + n_steps - 1: every epoch a permutation of the frames by
+    numpy.random.default_rng(seed) (the epochs draw from one generator), cut into batch_size frames (an epoch's tail
+    shorter than that is dropped, as the reader's queue leaves it).  Yields (rows, lengths, spkrs): the frames' indices
+    grouped into one pseudo-utterance per speaker present, speakers ascending and the draw's order kept within one."""
+    frame_spkr = np.asarray(frame_spkr)
+    for rows in _draws(len(frame_spkr), batch_size, n_steps, seed, start, "frames"):
+        rows = rows[np.argsort(frame_spkr[rows], kind="stable")]
+        spkrs, lengths = np.unique(frame_spkr[rows], return_counts=True)
+        yield rows, [int(v) for v in lengths], [int(v) for v in spkrs]
+
+
+def utterance_minibatches(file_spkr, batch_size, n_steps, seed, start=0):
+    """Trajectory training's minibatches: batch_size files of the same seeded permutations.  Yields (files, spkrs): the
+    files' indices ordered by speaker (the draw's order kept within one) and the speaker of each."""
+    file_spkr = np.asarray(file_spkr)
+    for files in _draws(len(file_spkr), batch_size, n_steps, seed, start, "files"):
+        files = files[np.argsort(file_spkr[files], kind="stable")]
+        yield files, [int(v) for v in file_spkr[files]]
+
+
+def _draws(n, batch_size, n_steps, seed, start, what):
+    if batch_size < 1 or n < batch_size:
+        raise ValueError("%d %s do not fill a minibatch of %d" % (n, what, batch_size))
+    rng = np.random.default_rng(seed)
+    done = 0
+    while done < start + n_steps:
+        perm = rng.permutation(n)
+        for at in range(0, n - batch_size + 1, batch_size):
+            if done == start + n_steps:
+                return
+            if done >= start:
+                yield perm[at:at + batch_size]
+            done += 1
+
+
+def _train_cost(model, b, x, obs, lengths, spkrs, keep_prob, seed, step):
+    """The minibatch's cost (a float64 scalar with autograd history): the mean over its frames of DNNDefine.cost, from
+    the library's training pass (training.AcousticModel.train_outputs and training.FrameLoss) on the WorldBatch `b` of
+    the pseudo-utterances, which must live until the cost's backward() has run."""
+    import torch
+    from . import training
+    out = model.train_outputs(b, x, spkrs, keep_prob, seed, step)
+    cost = training.FrameLoss.apply(b, out, model.variance.variances, obs, spkrs)
+    w = torch.as_tensor(lengths, dtype=torch.float64, device=cost.device)
+    return (cost * (w / w.sum())).sum()
+
+
+def _train_cost_trajectory(model, b, parts, x, obs, spkrs, layout, gv_var, msd_weight, gv_weight, keep_prob, seed, step):
+    """Trajectory training's cost of a minibatch of utterances ordered by speaker (DNNDefine.trajectory_cost: the mean
+    over the utterances): one training forward on the WorldBatch `b` of all of them, then training.TrajectoryLoss per
+    speaker present, with that speaker's variance row and GV variances, on parts = [(speaker, WorldBatch of its
+    utterances, first row, end row)].  Every batch must live until the cost's backward() has run."""
+    from . import training
+    out = model.train_outputs(b, x, spkrs, keep_prob, seed, step)
+    total = 0.0
+    for s, sub, r0, r1 in parts:
+        total = total + training.TrajectoryLoss.apply(sub, out[r0:r1], model.variance.variances[s], obs[r0:r1], gv_var[s],
+                                                      layout, msd_weight, gv_weight).sum()
+    return total / len(spkrs)
+
+
+def _variance_rows(variance_dir, name, n_spkrs, width):
+    """DNNTraining.py:116-139: <dir>/<name> in SD mode, <dir>/<speaker index>/<name> per speaker in SAT mode."""
+    rows = [_f32(os.path.join(str(variance_dir), name) if n_spkrs == 1 else
+                 os.path.join(str(variance_dir), str(s), name)).reshape(-1) for s in range(n_spkrs)]
+    if any(r.shape != (width,) for r in rows):
+        raise ValueError("%s: %s does not hold %d float32" % (variance_dir, name, width))
+    return np.stack(rows)
+
+
+def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, variance_dir=None, hidden_activation="sigmoid",
+                output_activation="linear", keep_prob=0.5, optimizer="adam", learning_rate=0.001, batch_size=256,
+                n_epochs=100, n_steps=None, seed=0, log_interval=100, save_interval=0, restore=None, streams=None,
+                msd_weight=1.0, gv_weight=1.0e-6, ctx=None, device="cuda", report=print):
+    """What DNNTraining.py does in SD and SAT mode: trains the acoustic model on a file list and saves it.
+
+    jobs:         [(ffi, ffo)] or [(ffi, ffo, speaker index)]: float32 rows of n_inputs and of n_outputs
+    model_path:   the `.npz` to write (training.AcousticModel.save, with the step count): every save_interval steps
+                  (0: never) and at the end
+    units:        the hidden layers' widths; n_spkrs > 1 is SAT mode
+    variance_dir: None (variances and GV variances 1), or DNNTraining.py -z: the directory of ffo.var and gv.var (SAT:
+                  <dir>/<speaker index>/ffo.var and gv.var)
+    streams:      None: frame by frame, DNNDefine.cost on minibatches of batch_size frames (minibatches); or DNNTraining.py
+                  -w, trajectory training: [(dim, windows, msd)] in the row's order as trajectory_files takes it,
+                  DNNDefine.trajectory_cost (training.TrajectoryLoss, with msd_weight and gv_weight) on minibatches of
+                  batch_size utterances (utterance_minibatches).  The GV variances stay at gv.var: the library returns no
+                  gradient with respect to them, and the `.npz` does not hold them
+    restore:      None, or the `.npz` to continue from: the steps, the minibatch draws and the dropout offsets go on from
+                  its step count.  The optimiser's own state (momentum, Adam's moments ...) is not in the file and begins anew
+    A step runs the library's training forward and backward with dropout (seed, offset = the step number) and one step of
+    make_optimizer's optimiser.  n_steps: None for n_epochs * frames // batch_size, in trajectory mode n_epochs * files //
+    batch_size (DNNTraining.py:180-187).  Every log_interval steps `Step %7d: cost = %e` is reported (DNNTraining.py:369).
+    Returns the reported (step, cost) pairs.  ADAPT mode is not offered.  The whole corpus is held on the device."""
+    import torch
+    from . import training
+    jobs = [tuple(j) + (0,) * (3 - len(j)) for j in jobs]
+    frames = []
+    for ffi, ffo, s in jobs:
+        size = os.path.getsize(ffi)
+        if size % (4 * n_inputs) or os.path.getsize(ffo) != size // (4 * n_inputs) * 4 * n_outputs:
+            raise ValueError("%s, %s: not as many rows of %d and %d float32" % (ffi, ffo, n_inputs, n_outputs))
+        if not 0 <= int(s) < n_spkrs:
+            raise ValueError("%s: speaker %d of %d" % (ffi, s, n_spkrs))
+        frames.append(size // (4 * n_inputs))
+    layout = n_static = None
+    if streams is not None:
+        layout = _streams_arg(streams)
+        n_static = sum(d for d, _, _ in layout)
+        if ffo_layout(layout)[1] != n_outputs:
+            raise ValueError("the streams make rows of %d columns, not %d" % (ffo_layout(layout)[1], n_outputs))
+    if n_steps is None:
+        n_steps = n_epochs * (sum(frames) if layout is None else len(jobs)) // batch_size
+    torch.manual_seed(seed)                                        # the initialisation's draws
+    start = 0
+    if restore is not None:
+        model = training.AcousticModel.load(restore)
+        if (model.n_inputs, model.units, model.n_outputs, model.n_spkrs) != (n_inputs, [int(n) for n in units], n_outputs, n_spkrs):
+            raise ValueError("%s holds another net" % restore)
+        start = model.step
+    else:
+        model = training.AcousticModel(n_inputs, units, n_outputs, n_spkrs, hidden_activation, output_activation)
+        if variance_dir is not None:                               # DNNTraining.py:116-127
+            with torch.no_grad():
+                model.variance.variances.copy_(torch.from_numpy(_variance_rows(variance_dir, "ffo.var", n_spkrs, n_outputs)))
+    gv_var = None
+    if layout is not None:                                         # DNNTraining.py:129-139
+        gv_var = torch.from_numpy(_variance_rows(variance_dir, "gv.var", n_spkrs, n_static) if variance_dir is not None
+                                  else np.ones((n_spkrs, n_static), dtype=np.float32)).to(device)
+    model = model.to(device)
+    own_ctx = ctx is None and device != "cpu"
+    if own_ctx:
+        ctx = _own_context()
+    x = torch.from_numpy(np.concatenate([_f32(j[0], n_inputs) for j in jobs])).to(device)
+    obs = torch.from_numpy(np.concatenate([_f32(j[1], n_outputs) for j in jobs])).to(device)
+    file_spkr = [int(j[2]) for j in jobs]
+    f_off = np.concatenate([[0], np.cumsum(frames)])
+    opt = make_optimizer(model, optimizer, learning_rate)
+    batch = (lambda lengths: W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)) if ctx is not None \
+        else (lambda lengths: None)
+    draws = minibatches(np.repeat(file_spkr, frames), batch_size, n_steps, seed, start) if layout is None \
+        else utterance_minibatches(file_spkr, batch_size, n_steps, seed, start)
+    log = []
+    for step, draw in enumerate(draws, start):
+        opt.zero_grad(set_to_none=True)
+        live = []
+        try:
+            if layout is None:
+                rows, lengths, spkrs = draw
+                idx = torch.from_numpy(rows).to(device)
+                live.append(batch(lengths))
+                cost = _train_cost(model, live[0], x[idx], obs[idx], lengths, spkrs, keep_prob, seed, step)
+            else:
+                files, spkrs = draw
+                lengths = [frames[i] for i in files]
+                idx = torch.from_numpy(np.concatenate([np.arange(f_off[i], f_off[i + 1]) for i in files])).to(device)
+                live.append(batch(lengths))
+                parts, off = [], np.concatenate([[0], np.cumsum(lengths)])
+                for s in sorted(set(spkrs)):
+                    k0, k1 = spkrs.index(s), len(spkrs) - spkrs[::-1].index(s)
+                    live.append(batch(lengths[k0:k1]))
+                    parts.append((s, live[-1], int(off[k0]), int(off[k1])))
+                cost = _train_cost_trajectory(model, live[0], parts, x[idx], obs[idx], spkrs, layout, gv_var, msd_weight,
+                                              gv_weight, keep_prob, seed, step)
+            cost.backward()
+        finally:
+            for b in live:
+                if b is not None:
+                    b.close()
+        opt.step()
+        if log_interval > 0 and ((step - start) % log_interval == 0 or step == start + n_steps - 1):
+            log.append((step, float(cost.detach())))
+            report("Step %7d: cost = %e" % log[-1])
+        if save_interval > 0 and (step + 1 - start) % save_interval == 0 and step + 1 < start + n_steps:
+            model.save(model_path, step + 1)
+    model.save(model_path, start + n_steps)
+    if own_ctx:
+        ctx.close()
+    return log
 
 
 # ---- training targets, their variances and the GV data (data/Makefile.in:325-459, Training.pl:1402-1491) -------------
@@ -1195,6 +1412,33 @@ def main(argv=None):
     p.add_argument("--out-dir", required=True, help="<base>.<extension> and <base>.var are written here")
     p.add_argument("--extension", default="ffo")
     p.add_argument("--spkr", type=int, default=None, help="speaker index (default: the last, as DNNSynthesis.py)")
+    p = sub.add_parser("dnn-train", help="DNNTraining.py (SD and SAT; frame by frame or trajectory training): trains the acoustic model on a list "
+                       "of ffi / ffo pairs")
+    p.add_argument("--scp", required=True, help="one `ffi ffo` pair per line, or `ffi ffo speaker-index`")
+    p.add_argument("--model", required=True, help="the .npz to write")
+    p.add_argument("--inputs", type=int, required=True, help="float32 values per ffi row")
+    p.add_argument("--outputs", type=int, required=True, help="float32 values per ffo row")
+    p.add_argument("--units", type=int, nargs="*", default=[], help="the hidden layers' widths")
+    p.add_argument("--spkrs", type=int, default=1, help="number of speakers (more than one: SAT mode)")
+    p.add_argument("--variance-dir", default=None, help="the directory of ffo.var (SAT: <dir>/<speaker index>/ffo.var)")
+    p.add_argument("--hidden-activation", default="sigmoid", choices=W.ACTIVATIONS)
+    p.add_argument("--output-activation", default="linear", choices=W.ACTIVATIONS)
+    p.add_argument("--keep-prob", type=float, default=0.5)
+    p.add_argument("--optimizer", default="adam", choices=OPTIMIZERS)
+    p.add_argument("--learning-rate", type=float, default=0.001)
+    p.add_argument("--batch-size", type=int, default=256)
+    p.add_argument("--epochs", type=int, default=100)
+    p.add_argument("--steps", type=int, default=None, help="instead of --epochs")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--log-interval", type=int, default=100)
+    p.add_argument("--save-interval", type=int, default=0)
+    p.add_argument("--restore", default=None, help="a .npz to continue from: steps, draws and dropout offsets go on from "
+                   "its step count")
+    p.add_argument("--stream", action="append", default=None, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help="trajectory training (DNNTraining.py -w): one per stream in the row's order; minibatches are then "
+                   "--batch-size utterances, and gv.var is read beside ffo.var")
+    p.add_argument("--msd-weight", type=float, default=1.0)
+    p.add_argument("--gv-weight", type=float, default=1.0e-6)
     p = sub.add_parser("postfilter", help="postfiltering_mcp: formant emphasis on a list of mgc files")
     p.add_argument("--scp", required=True, help="job list: the mgc file, then the p_mgc file to write")
     p.add_argument("--order", type=int, required=True, help="order of the mel-cepstra: a row holds order + 1 float32")
@@ -1283,6 +1527,17 @@ def main(argv=None):
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)
         print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "dnn-train":
+        rows = []
+        with open(a.scp) as f:
+            for ln in f:
+                w = ln.split()
+                if w:
+                    rows.append((w[0], w[1]) + ((int(w[2]),) if len(w) > 2 else ()))
+        train_files(rows, a.model, a.inputs, a.units, a.outputs, a.spkrs, a.variance_dir, a.hidden_activation,
+                    a.output_activation, a.keep_prob, a.optimizer, a.learning_rate, a.batch_size, a.epochs, a.steps, a.seed,
+                    a.log_interval, a.save_interval, a.restore, a.stream, a.msd_weight, a.gv_weight)
         return 0
     if a.cmd == "dnn-forward":
         forward_files(read_forward_scp(a.scp), a.model, a.out_dir, a.spkr, a.extension)

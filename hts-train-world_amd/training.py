@@ -8,9 +8,16 @@ content of gv.var.  The cost and both gradients come from one call of WorldBatch
 here computes them in torch.
 
 AcousticModel is the recipe's network itself (DNNDefine.inference, data/scripts/DNNDefine.py:113-191) under the
-reference's parameter names: a plain torch forward for training with autograd, infer() for the forward pass of whole
-batches on the library's own kernel (csrc/dnn.hip), and save() / load() of one `.npz` -- the interchange format, since
-TF checkpoints cannot be read here.  Dropout, the optimiser, checkpoints and the data reader are the caller's."""
+reference's parameter names: a plain torch forward with autograd, infer() for the forward pass of whole batches on the
+library's own kernel (csrc/dnn.hip), train_outputs() for the training pass on the library's kernels (csrc/dnn_train.hip:
+the forward pass with TF 1.x dropout, and as its autograd backward the library's backward pass through the network), and
+save() / load() of one `.npz` -- the interchange format, since TF checkpoints cannot be read here.
+
+    out = model.train_outputs(batch, x, spkr, keep_prob=0.5, seed=seed, offset=step)
+    loss = (FrameLoss.apply(batch, out, model.variance.variances, obs, spkr) * weights).sum()
+
+FrameLoss is DNNDefine.cost per utterance with both gradients from the library; TrajectoryLoss takes the same `out`.
+The training loop itself (minibatches, the optimisers' groups, checkpoints) is recipe.train_files."""
 from __future__ import annotations
 
 import torch
@@ -94,6 +101,76 @@ def frame_cost(pred, obs, var):
     return 0.5 * (math.log(2.0 * math.pi) + torch.log(var).mean() + ((obs - pred) ** 2 / var).mean())
 
 
+class FrameLoss(torch.autograd.Function):
+    """Per-utterance frame-level cost [n_utt] (float64) of a WorldBatch `b` (DNNDefine.cost, DNNDefine.py:231-237).
+    pred: float32 cuda [total_frames][D]; variances: float32 cuda [n_spkrs][D] (either may require grad); obs: float32
+    cuda [total_frames][D]; spkr: None (the last speaker) or one index per utterance.  The cost and both gradients come
+    from one WorldBatch.acoustic_model_train_forward call on a one-layer linear net with the identity as its weights
+    (pred 1 + 0 is pred, bit for bit): nothing here computes them in torch.  Weights T_u / sum T on the result give the
+    reference's mean over a minibatch.  A non-zero status raises, unless skip_flagged: a flagged utterance then costs 0
+    and sends no gradient."""
+
+    @staticmethod
+    def forward(ctx, b, pred, variances, obs, spkr=None, skip_flagged=False):
+        n_spkrs, D = int(variances.shape[0]), int(variances.shape[1])
+        eye = {"weights": [torch.eye(D, dtype=torch.float32, device=pred.device)],
+               "biases": [torch.zeros(D, dtype=torch.float32, device=pred.device)], "spkr_weights": None,
+               "variances": variances.detach(), "n_spkrs": n_spkrs, "hidden_activation": 0, "output_activation": 0}
+        _, cost, status, grad_pred, grad_var = b.acoustic_model_train_forward(eye, pred.detach(), spkr, obs, want_grads=True)
+        flagged = torch.nonzero(status).reshape(-1).tolist()
+        if flagged and not skip_flagged:
+            raise RuntimeError("FrameLoss: utterances %s are flagged (status %s): bit 1 a non-finite input, bit 2 a variance "
+                               "that is not positive and finite" % (flagged, [int(status[u]) for u in flagged]))
+        ctx.grad_pred, ctx.grad_var = grad_pred, grad_var          # intermediates, not differentiable themselves
+        ctx.offsets = torch.as_tensor(b.frame_offsets, device=pred.device)
+        ctx.spk = [n_spkrs - 1] * b.n_utt if spkr is None else [int(v) for v in spkr]
+        ctx.n_spkrs = n_spkrs
+        return cost
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gp = gv = None
+        if ctx.needs_input_grad[1]:
+            per_frame = torch.repeat_interleave(g, ctx.offsets[1:] - ctx.offsets[:-1])
+            gp = ctx.grad_pred * per_frame[:, None].to(torch.float32)
+        if ctx.needs_input_grad[2]:
+            # a speaker's utterances are added one by one in the batch's order, in double, and rounded once: a scatter
+            # with atomic additions would leave the order, and so the bits, to chance
+            w = ctx.grad_var * g[:, None]
+            gv = torch.zeros(ctx.n_spkrs, w.shape[1], dtype=torch.float64, device=g.device)
+            for u, s in enumerate(ctx.spk):
+                gv[s] += w[u]
+            gv = gv.to(torch.float32)
+        return None, gp, gv, None, None, None
+
+
+class _TrainOutputs(torch.autograd.Function):
+    """AcousticModel.train_outputs: forward WorldBatch.acoustic_model_train_forward, backward
+    WorldBatch.acoustic_model_backward with the same (keep_prob, seed, offset).  params: the module's parameters in
+    AcousticModel.train_parameters' order, so that autograd hands their gradients back."""
+
+    @staticmethod
+    def forward(ctx, model, b, x, spkr, keep_prob, seed, offset, max_chunk_frames, *params):
+        out, _, status = b.acoustic_model_train_forward(model, x, spkr, None, keep_prob, seed, offset, False, max_chunk_frames)
+        flagged = torch.nonzero(status).reshape(-1).tolist()
+        if flagged:
+            raise RuntimeError("train_outputs: utterances %s are flagged (status %s): bit 1 a non-finite input, bit 2 a "
+                               "non-finite output" % (flagged, [int(status[u]) for u in flagged]))
+        ctx.call = (model, b, x, spkr, keep_prob, seed, offset, max_chunk_frames)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        model, b, x, spkr, keep_prob, seed, offset, max_chunk_frames = ctx.call
+        grads = b.acoustic_model_backward(model, x, spkr, g.contiguous(), keep_prob, seed, offset, max_chunk_frames)
+        flagged = torch.nonzero(grads["status"]).reshape(-1).tolist()
+        if flagged:
+            raise RuntimeError("train_outputs: the backward pass flagged utterances %s: a non-finite gradient" % (flagged,))
+        return (None,) * 8 + tuple(grads[name].to(p.dtype) for name, p in model.train_parameters())
+
+
 def _activate(name, v):
     return {"linear": lambda t: t, "sigmoid": torch.sigmoid, "tanh": torch.tanh, "relu": torch.relu}[name](v)
 
@@ -175,10 +252,26 @@ class AcousticModel(torch.nn.Module):
         WorldBatch.acoustic_model_forward.  spkr: None or one index per utterance."""
         return batch.acoustic_model_forward(self, x, spkr, obs, max_chunk_frames)
 
-    def save(self, path):
-        """One `.npz`: float32 arrays under the parameters' names, and the two activation names."""
+    def train_parameters(self):
+        """[(name, parameter)] of the network (not the variances), the reference's names, in a fixed order."""
+        keep = [(k, p) for k, p in self.named_parameters() if not k.startswith("variance.")]
+        return keep
+
+    def train_outputs(self, batch, x, spkr=None, keep_prob=1.0, seed=0, offset=0, max_chunk_frames=0):
+        """The training forward of a WorldBatch on the library's kernels, differentiable with respect to the module's
+        parameters (not to x): out float32 [total_frames][n_outputs].  keep_prob, seed, offset: the dropout of the hidden
+        layers, see WorldBatch.acoustic_model_train_forward; offset is the caller's step counter.  The result feeds
+        FrameLoss or TrajectoryLoss.  A flagged utterance raises."""
+        return _TrainOutputs.apply(self, batch, x, spkr, float(keep_prob), int(seed), int(offset), int(max_chunk_frames),
+                                   *[p for _, p in self.train_parameters()])
+
+    def save(self, path, step=None):
+        """One `.npz`: float32 arrays under the parameters' names, and the two activation names; with `step`, the number
+        of training steps behind the parameters (load() leaves it in the module's `step`, 0 without one)."""
         import numpy as np
         arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.state_dict().items()}
+        if step is not None:
+            arrays["step"] = np.array(int(step), dtype=np.int64)
         arrays["hidden_activation"] = np.array(self.hidden_activation)
         arrays["output_activation"] = np.array(self.output_activation)
         with open(path, "wb") as f:
@@ -189,6 +282,7 @@ class AcousticModel(torch.nn.Module):
         import numpy as np
         with np.load(path, allow_pickle=False) as z:
             arrays = {k: z[k] for k in z.files}
+        step = int(arrays.pop("step", 0))
         n = 0
         while "hidden%d.si_weights" % n in arrays:
             n += 1
@@ -201,4 +295,5 @@ class AcousticModel(torch.nn.Module):
         m = cls(n_in, units, int(wo.shape[1]), int(var.shape[0]), str(arrays.pop("hidden_activation")),
                 str(arrays.pop("output_activation")), sat="hidden0.sd_weights" in arrays)
         m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in arrays.items()})
+        m.step = step
         return m

@@ -63,6 +63,11 @@ class AcousticModelDesc(C.Structure):
                 ("spkr_weights", C.POINTER(C.c_void_p)), ("variances", C.c_void_p), ("max_chunk_frames", C.c_int64)]
 
 
+class Dropout(C.Structure):
+    """include/world_mi355.h: WorldMi355Dropout (the acoustic model's training pass)."""
+    _fields_ = [("keep_prob", C.c_float), ("seed", C.c_uint64), ("offset", C.c_uint32)]
+
+
 ACTIVATIONS = ("linear", "sigmoid", "tanh", "relu")      # Config.pm.in:228: the codes 0 .. 3
 
 
@@ -159,6 +164,10 @@ def load_library():
                                            C.POINTER(TrajectoryOption), vp, vp, vp, vp, C.c_int64, vp, vp]
     L.WorldMi355AcousticModelForward.argtypes = [vp, C.POINTER(AcousticModelDesc), vp, C.c_int64, vp, vp, C.c_int64, vp,
                                                  C.c_int64, vp, vp]
+    L.WorldMi355AcousticModelTrainForward.argtypes = [vp, C.POINTER(AcousticModelDesc), C.POINTER(Dropout), vp, C.c_int64, vp,
+                                                      vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]
+    L.WorldMi355AcousticModelBackward.argtypes = [vp, C.POINTER(AcousticModelDesc), C.POINTER(Dropout), vp, C.c_int64, vp,
+                                                  vp, C.c_int64, vp, vp, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -824,18 +833,9 @@ class WorldBatch:
             ptr(status)), "TrajectoryCost")
         return cost, c, grad_pred, grad_var, status
 
-    def acoustic_model_forward(self, model, x, spkr=None, obs=None, max_chunk_frames=0):
-        """The forward pass of the recipe's acoustic model (DNNDefine.inference as DNNSynthesis.py runs it) and, with
-        targets, its frame-level cost (DNNDefine.cost), every utterance of the batch at once.  model: a mapping (or an
-        object whose kernel_args() returns one, such as training.AcousticModel) with "weights" (n_layers + 1 float32
-        cuda tensors [fan_in][fan_out], the last the output layer's), "biases" ([fan_out] each), "spkr_weights" (None,
-        or n_layers tensors [n_spkrs][units]), "variances" (None, or [n_spkrs][n_outputs]), "hidden_activation",
-        "output_activation" (a name of ACTIVATIONS or its code) and "n_spkrs".  x: float32 cuda
-        [total_frames][n_inputs], obs: None or float32 cuda [total_frames][n_outputs]; either may be a column view of a
-        wider matrix (its row stride is passed, nothing is copied).  spkr: None (n_spkrs - 1 for all), or one index per
-        utterance.  Returns (out float32 [total_frames][n_outputs], cost float64 [n_utt] or None without obs, status
-        int32 [n_utt]: bit 1 a non-finite x or obs, bit 2 a non-finite output or, with a cost, a variance that is not
-        positive and finite -- such an utterance has zero rows and cost 0)."""
+    def _acoustic_model_args(self, who, model, x, spkr, obs, max_chunk_frames):
+        """What the three acoustic-model calls share: (descriptor, what it points to, the row-argument checker, x, ld_x,
+        obs, ld_obs, spkr array, (n_in, units, n_out, n_spkrs, sat))."""
         import torch
         m = model.kernel_args() if hasattr(model, "kernel_args") else model
         tf = self.total_frames
@@ -844,14 +844,14 @@ class WorldBatch:
 
         def dev(t, shape, what):
             if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)):
-                raise ValueError(f"acoustic_model_forward: {what} must be float32 cuda {list(shape)}, got {tuple(t.shape)}")
+                raise ValueError(f"{who}: {what} must be float32 cuda {list(shape)}, got {tuple(t.shape)}")
             t = t.detach().contiguous()
             keep.append(t)
             return t.data_ptr()
 
         def rows(t, width, what):
             if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (tf, width)):
-                raise ValueError(f"acoustic_model_forward: {what} must be float32 cuda [{tf}][{width}]")
+                raise ValueError(f"{who}: {what} must be float32 cuda [{tf}][{width}]")
             if tf > 0 and (t.stride(1) != 1 or (tf > 1 and t.stride(0) < width)):
                 t = t.contiguous()
             keep.append(t)
@@ -860,7 +860,7 @@ class WorldBatch:
         weights, biases = list(m["weights"]), list(m["biases"])
         n_layers = len(weights) - 1
         if n_layers < 0 or len(biases) != n_layers + 1 or weights[-1].dim() != 2 or any(w.dim() != 2 for w in weights):
-            raise ValueError("acoustic_model_forward: weights and biases are n_layers + 1 matrices and vectors")
+            raise ValueError(f"{who}: weights and biases are n_layers + 1 matrices and vectors")
         n_in, n_out, n_spkrs = int(weights[0].shape[0]), int(weights[-1].shape[1]), int(m.get("n_spkrs", 1))
         units = [int(w.shape[1]) for w in weights[:-1]]
         fan = [n_in] + units
@@ -876,7 +876,7 @@ class WorldBatch:
         sd = m.get("spkr_weights")
         if sd is not None:
             if len(sd) != n_layers:
-                raise ValueError("acoustic_model_forward: spkr_weights has one matrix per hidden layer")
+                raise ValueError(f"{who}: spkr_weights has one matrix per hidden layer")
             sa = (C.c_void_p * max(n_layers, 1))(*[dev(t, (n_spkrs, units[i]), f"spkr_weights[{i}]") for i, t in enumerate(sd)])
             keep.append(sa)
             d.spkr_weights = sa
@@ -888,13 +888,31 @@ class WorldBatch:
         ld_obs = 0
         if obs is not None:
             if var is None:
-                raise ValueError("acoustic_model_forward: a cost needs the model's variances")
+                raise ValueError(f"{who}: a cost needs the model's variances")
             obs, ld_obs = rows(obs, n_out, "obs")
         sp = None
         if spkr is not None:
             sp = np.ascontiguousarray(spkr, dtype=np.int32)
             if sp.shape != (self.n_utt,):
-                raise ValueError(f"acoustic_model_forward: spkr has one index per utterance ({self.n_utt})")
+                raise ValueError(f"{who}: spkr has one index per utterance ({self.n_utt})")
+        return d, keep, rows, x, ld_x, obs, ld_obs, sp, (n_in, units, n_out, n_spkrs, sd is not None)
+
+    def acoustic_model_forward(self, model, x, spkr=None, obs=None, max_chunk_frames=0):
+        """The forward pass of the recipe's acoustic model (DNNDefine.inference as DNNSynthesis.py runs it) and, with
+        targets, its frame-level cost (DNNDefine.cost), every utterance of the batch at once.  model: a mapping (or an
+        object whose kernel_args() returns one, such as training.AcousticModel) with "weights" (n_layers + 1 float32
+        cuda tensors [fan_in][fan_out], the last the output layer's), "biases" ([fan_out] each), "spkr_weights" (None,
+        or n_layers tensors [n_spkrs][units]), "variances" (None, or [n_spkrs][n_outputs]), "hidden_activation",
+        "output_activation" (a name of ACTIVATIONS or its code) and "n_spkrs".  x: float32 cuda
+        [total_frames][n_inputs], obs: None or float32 cuda [total_frames][n_outputs]; either may be a column view of a
+        wider matrix (its row stride is passed, nothing is copied).  spkr: None (n_spkrs - 1 for all), or one index per
+        utterance.  Returns (out float32 [total_frames][n_outputs], cost float64 [n_utt] or None without obs, status
+        int32 [n_utt]: bit 1 a non-finite x or obs, bit 2 a non-finite output or, with a cost, a variance that is not
+        positive and finite -- such an utterance has zero rows and cost 0)."""
+        import torch
+        d, keep, _, x, ld_x, obs, ld_obs, sp, (_, _, n_out, _, _) = self._acoustic_model_args(
+            "acoustic_model_forward", model, x, spkr, obs, max_chunk_frames)
+        tf = self.total_frames
         out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda")
         cost = torch.zeros(self.n_utt, dtype=torch.float64, device="cuda") if obs is not None else None
         status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
@@ -903,6 +921,68 @@ class WorldBatch:
             self.handle, C.byref(d), ptr(x), ld_x, None if sp is None else sp.ctypes.data_as(C.c_void_p), ptr(out), n_out,
             ptr(obs), ld_obs, ptr(cost), ptr(status)), "AcousticModelForward")
         return out, cost, status
+
+    def acoustic_model_train_forward(self, model, x, spkr=None, obs=None, keep_prob=1.0, seed=0, offset=0, want_grads=False,
+                                     max_chunk_frames=0):
+        """acoustic_model_forward with dropout between the hidden layers (TF 1.x tf.nn.dropout; the mask is Philox4x32-10
+        of (seed, offset, layer, batch row, unit), see include/world_mi355.h) and, with want_grads, the gradients of the
+        frame-level cost.  Returns (out, cost or None, status), and with want_grads (obs is then required)
+        (out, cost, status, grad_out float32 [total_frames][n_outputs], grad_var float64 [n_utt][n_outputs]): the
+        gradients of every utterance's own cost.  With keep_prob 1 out equals acoustic_model_forward's bit for bit."""
+        import torch
+        d, keep, _, x, ld_x, obs, ld_obs, sp, (_, _, n_out, _, _) = self._acoustic_model_args(
+            "acoustic_model_train_forward", model, x, spkr, obs, max_chunk_frames)
+        if want_grads and obs is None:
+            raise ValueError("acoustic_model_train_forward: the cost gradients need obs")
+        tf = self.total_frames
+        drop = Dropout(float(keep_prob), int(seed) & 0xffffffffffffffff, int(offset) & 0xffffffff)
+        out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda")
+        cost = torch.zeros(self.n_utt, dtype=torch.float64, device="cuda") if obs is not None else None
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        grad_out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda") if want_grads else None
+        grad_var = torch.zeros(self.n_utt, n_out, dtype=torch.float64, device="cuda") if want_grads else None
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        _check(load_library().WorldMi355AcousticModelTrainForward(
+            self.handle, C.byref(d), C.byref(drop), ptr(x), ld_x, None if sp is None else sp.ctypes.data_as(C.c_void_p),
+            ptr(out), n_out, ptr(obs), ld_obs, ptr(cost), ptr(grad_out), n_out, ptr(grad_var), ptr(status)),
+            "AcousticModelTrainForward")
+        if want_grads:
+            return out, cost, status, grad_out, grad_var
+        return out, cost, status
+
+    def acoustic_model_backward(self, model, x, spkr, grad_out, keep_prob=1.0, seed=0, offset=0, max_chunk_frames=0):
+        """The backward pass of the training forward with the same (keep_prob, seed, offset): the gradients of
+        sum(out * grad_out) with respect to the model's parameters, as a dict keyed by the reference's parameter names
+        (hidden{i}.si_weights, hidden{i}.si_biases, hidden{i}.sd_weights in SAT mode, output.si_weights,
+        output.si_biases; float32 cuda, shaped as the parameters), and under "status" the int32 [n_utt] mask: bit 1 a
+        non-finite x or grad_out, bit 2 a non-finite output -- such an utterance adds exact zeros.  grad_out: float32 cuda
+        [total_frames][n_outputs], or a column view."""
+        import torch
+        d, keep, rows, x, ld_x, _, _, sp, (n_in, units, n_out, n_spkrs, sat) = self._acoustic_model_args(
+            "acoustic_model_backward", model, x, spkr, None, max_chunk_frames)
+        g, ld_g = rows(grad_out, n_out, "grad_out")
+        drop = Dropout(float(keep_prob), int(seed) & 0xffffffffffffffff, int(offset) & 0xffffffff)
+        n_layers = len(units)
+        fan, wid = [n_in] + units, units + [n_out]
+        names = ["hidden%d" % i for i in range(n_layers)] + ["output"]
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device="cuda")
+        gw = [z(fan[i], wid[i]) for i in range(n_layers + 1)]
+        gb = [z(wid[i]) for i in range(n_layers + 1)]
+        gs = [z(n_spkrs, units[i]) for i in range(n_layers)] if sat else None
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        wa, ba = arr(gw), arr(gb)
+        sa = arr(gs) if sat else None
+        _check(load_library().WorldMi355AcousticModelBackward(
+            self.handle, C.byref(d), C.byref(drop), C.c_void_p(x.data_ptr()), ld_x,
+            None if sp is None else sp.ctypes.data_as(C.c_void_p), C.c_void_p(g.data_ptr()), ld_g, wa, ba, sa,
+            C.c_void_p(status.data_ptr())), "AcousticModelBackward")
+        res = {"status": status}
+        for i, k in enumerate(names):
+            res[k + ".si_weights"], res[k + ".si_biases"] = gw[i], gb[i]
+            if sat and i < n_layers:
+                res[k + ".sd_weights"] = gs[i]
+        return res
 
     def split_frames(self, a):
         return [a[self.frame_offsets[u]:self.frame_offsets[u + 1]] for u in range(self.n_utt)]

@@ -350,6 +350,49 @@ typedef struct {
 int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const float* x, int64_t ld_x,
                                    const int* spkr, float* out, int64_t ld_out, const float* obs, int64_t ld_obs,
                                    double* cost, int* status);
+/* ---- Acoustic model training pass: DNNTraining.py's step on the network above -- the forward pass with dropout
+ * (DNNDefine.inference at keep_prob < 1, TF 1.x tf.nn.dropout), the gradients of the frame-level cost, and the backward
+ * pass through the network.  Hidden layer i, batch row t (0 .. total_frames - 1), unit n:
+ *   mask m = 1 iff (float)(w >> 8) * 2^-24 < keep_prob, w word n & 3 of Philox4x32-10 (multipliers 0xD2511F53,
+ *   0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) at counter (t, n >> 2, i, offset), key (seed & 0xffffffff,
+ *   seed >> 32): a function of (seed, offset, i, t, n) alone;
+ *   a_i = act_h((h_{i-1} W_i + b_i) + sd_i[s(u)]),  h_i = m ? fl(a_i / keep_prob) : 0  (h_i = a_i at keep_prob 1),
+ *   out = act_o(h_{L-1} W_o + b_o): no dropout on the outputs.  With keep_prob 1 out equals AcousticModelForward's bits.
+ * Backward from G = dloss/dout:  dz_o = G act_o'(out),  dh_{i-1} = dz_i W_i',  da_i = m ? fl(dh_i / keep_prob) : 0,
+ *   dz_i = da_i act_h'(a_i)  (the derivative from the float32 a: a (1 - a), 1 - a^2, [a > 0], 1),
+ *   dW_i[k][n] = sum_t h_{i-1}[t][k] dz_i[t][n]: one k-ordered float32 fmaf chain over the batch's rows in order,
+ *   db_i = sum_t dz_i,  dsd_i[s] = the same over the rows of speaker s: both in double, utterance by utterance in a fixed
+ *   order that depends on the lengths alone, rounded once.  No result depends on max_chunk_frames.
+ * Cost gradients per utterance of T frames (D = n_outputs, var = variances[s(u)]), in double:
+ *   grad_out[t][d] = (out - obs) / (var_d T D)  (rounded to float32),
+ *   grad_var[u][d] = (1 / var_d - (1 / T) sum_t (obs - out)^2 / var_d^2) / (2 D). */
+typedef struct {
+  float keep_prob;        /* 0 < keep_prob <= 1 */
+  uint64_t seed;
+  uint32_t offset;        /* the caller's step counter */
+} WorldMi355Dropout;
+/* AcousticModelForward's arguments, and: drop: HOST, NULL for keep_prob 1.  grad_out: NULL, or DEVICE float32, row t at
+ *   grad_out + t * ld_grad.  grad_var: NULL, or DEVICE double [n_utt][n_outputs].  Either asks for obs and variances, as a
+ *   cost does.  status as AcousticModelForward's; a flagged utterance has zero rows in out and grad_out, a zero row in
+ *   grad_var and cost 0.  Refusals as AcousticModelForward's, and: keep_prob outside (0, 1] or not finite, ld_grad smaller
+ *   than a row.  Timed as "dnn_layer_kernel" and "dnn_cost_kernel". */
+int WorldMi355AcousticModelTrainForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
+                                        const float* x, int64_t ld_x, const int* spkr, float* out, int64_t ld_out,
+                                        const float* obs, int64_t ld_obs, double* cost, float* grad_out, int64_t ld_grad,
+                                        double* grad_var, int* status);
+/* The backward pass: the forward pass is computed again from x with the same mask.  grad_out: DEVICE, G, row t at
+ *   grad_out + t * ld_grad.  grad_weights, grad_biases: NULL, or HOST arrays of n_layers + 1 DEVICE pointers shaped as
+ *   the model's; grad_spkr_weights: NULL, or n_layers DEVICE pointers [n_spkrs][units[i]] (refused without
+ *   spkr_weights).  The gradients are overwritten.  status: NULL, or DEVICE int[n_utt]: 1 a non-finite value in the
+ *   utterance's rows of x or of G; 2 a non-finite output of finite inputs.  A flagged utterance adds exact zeros to every
+ *   gradient; the others' contributions keep their bits.  Refusals as above, and a NULL entry in a given pointer array.
+ * A batch of zero frames returns WM_OK with zero gradients.  The workspace (per chunk row: two dz buffers and, per hidden
+ * layer, a_i and with keep_prob < 1 also h_i, each max(units, n_outputs) floats) is the forward pass's, grown.  Timed as
+ * "dnn_backward_kernel", one record per call. */
+int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
+                                    const float* x, int64_t ld_x, const int* spkr, const float* grad_out, int64_t ld_grad,
+                                    float* const* grad_weights, float* const* grad_biases, float* const* grad_spkr_weights,
+                                    int* status);
 /* ---- Mel-cepstral postfilter: the recipe's formant emphasis, postfiltering_mcp (scripts/Training.pl:2642-2687), which
  * gen_wave (:2813-2845) runs on every generated `.mgc` before mgc2sp -- the stage between
  * WorldMi355ParameterGeneration and WorldMi355MelCepstrumToSpectrum.  For one frame c[0 .. order] at warp alpha and
