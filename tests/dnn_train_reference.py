@@ -129,16 +129,23 @@ def names_of(n_layers):
     return ["hidden%d" % i for i in range(n_layers)] + ["output"]
 
 
-def backward(params, fw, G, spkr_rows, hidden, output):
-    """(grads, bounds): dicts keyed by the reference's parameter names, float64, of sum(out * G)."""
+def backward(params, fw, G, spkr_rows, hidden, output, e_G=None):
+    """(grads, bounds): dicts keyed by the reference's parameter names, float64, of sum(out * G).  e_G: None -- G is
+    the float32 matrix that the float32 evaluation receives too, without error -- or the element-wise bound on the error
+    of the G that reaches the float32 evaluation: G is then taken in float64 as it is given (a whole training step,
+    tests/train_step_reference.py, where G comes from the forward pass's own outputs)."""
     ls = R.layers(params)
     L = len(ls) - 1
     names = names_of(L)
     p = fw["p"]
     rows = fw["x"].shape[0]
-    G = np.asarray(G, dtype=np.float32).astype(np.float64)
+    if e_G is None:
+        G = np.asarray(G, dtype=np.float32).astype(np.float64)
+        e_G = np.zeros_like(G)
+    else:
+        G, e_G = np.asarray(G, dtype=np.float64), np.broadcast_to(np.asarray(e_G, dtype=np.float64), np.shape(G))
     d, e_d = deriv(output, fw["out"], fw["e_out"])
-    dz, e_dz = _times(G, np.zeros_like(G), d, e_d)
+    dz, e_dz = _times(G, e_G, d, e_d)
     grads, bounds = {}, {}
     for i in range(L, -1, -1):
         W, _, sd = ls[i]
@@ -214,7 +221,8 @@ def _deriv_f32(name, a):
 
 def backward_f32(params, x, spkr_rows, hidden, output, p, ms, G):
     """Forward and backward in plain numpy float32 (whatever order its products sum in) with the masks given: what the
-    bound must cover.  Returns the gradients, float32, keyed as backward's."""
+    bound must cover.  G: the matrix, or a function of the float32 outputs that returns it (a criterion evaluated on
+    them).  Returns the gradients, float32, keyed as backward's."""
     f = np.float32
     p = f(p)
     ls = [(W.astype(f), b.astype(f), None if sd is None else sd.astype(f)) for W, b, sd in R.layers(params)]
@@ -234,7 +242,7 @@ def backward_f32(params, x, spkr_rows, hidden, output, p, ms, G):
         acts.append(a)
         h = np.where(ms[i], a / p, f(0.0)).astype(f) if p < 1 else a
         hs.append(h)
-    dz = np.asarray(G, dtype=f) * _deriv_f32(output, out)
+    dz = np.asarray(G(out) if callable(G) else G, dtype=f) * _deriv_f32(output, out)
     grads = {}
     for i in range(L, -1, -1):
         W, _, sd = ls[i]
@@ -278,15 +286,15 @@ CORPUS_LENGTHS = (33, 129, 257, 64)
 CORPUS_LR, CORPUS_STEPS, CORPUS_BATCH = 2.0, 20, 128      # SGD; the host test confirms that the cost falls at this rate
 
 
-def write_corpus(directory, n_spkrs=1):
-    """`.ffi` / `.ffo` files of CORPUS_LENGTHS frames: inputs as make_inputs draws them, targets a random net's outputs
+def write_corpus(directory, n_spkrs=1, lengths=CORPUS_LENGTHS):
+    """`.ffi` / `.ffo` files of `lengths` frames: inputs as make_inputs draws them, targets a random net's outputs
     (sigmoid hidden units, linear outputs) plus 0.1 normal noise.  Returns [(ffi, ffo, speaker index)]."""
     import os
     n_in, units, n_out = CORPUS_NET
     teacher = R.make_model(R.SEED + 700, n_in, units, n_out)
     rng = np.random.default_rng(R.SEED + 701)
     jobs = []
-    for k, T_ in enumerate(CORPUS_LENGTHS):
+    for k, T_ in enumerate(lengths):
         x = R.make_inputs(R.SEED + 710 + k, T_, n_in)
         out, _ = R.forward(teacher, x, np.zeros(T_, dtype=np.int64), "sigmoid", "linear")
         obs = (out + 0.1 * rng.standard_normal(out.shape)).astype(np.float32)

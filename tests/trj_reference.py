@@ -5,7 +5,9 @@ independently of each other and of the library, are what the library is held to.
 
 (a) dense():  trajectory_cost line by line in torch float64 on the CPU -- the dense W of mlpg_reference.window_matrix
     (edge 0), W' S W, its Cholesky factor, the FULL inverse by cholesky_solve against eye(T), the three costs exactly as
-    the reference composes them -- and torch autograd for the gradients with respect to pred and var.
+    the reference composes them -- and torch autograd for the gradients with respect to pred and var.  dense_terms()
+    is the same statement on float64 tensors as they are given, the three cost terms returned as tensors: what
+    tests/train_step_reference.py chains behind the network's forward pass.
 (b) banded(): a banded LDL' written out in np.longdouble gives ln det A, c and the band of A^-1 (backward recurrence);
     the cost terms and the ANALYTIC gradients of the issue are evaluated from them.  It also returns, per quantity, S:
     the sum of the magnitudes of the terms that were added to make it (in the quantity's own units).
@@ -44,14 +46,15 @@ def named(streams):
 
 
 # ---- (a) dense, float64, autograd ----------------------------------------------------------------------------------
-def dense(pred, obs, var, gv_var, streams, msd_weight=1.0, gv_weight=1.0e-6, want_cond=True):
+def dense_terms(p_, o_, v_, g_, streams, want_cond=False):
+    """trajectory_cost of one utterance on torch float64 tensors as they are given -- nothing is cast, detached or
+    differentiated here, so the tensors may carry autograd history (tests/train_step_reference.py chains the network
+    in front).  p_, o_: [T][width], v_: [width], g_: [sum dims].  Returns (trj, msd, gv, cs, conds): the three cost
+    terms as tensors, c per stream as numpy, the condition numbers (empty without want_cond)."""
     import torch
     streams = named(streams)
     lay, width = layout(streams)
-    T = pred.shape[0]
-    f64 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32).astype(np.float64))
-    p_, v_ = f64(pred).requires_grad_(True), f64(var).requires_grad_(True)
-    o_, g_ = f64(obs), f64(gv_var)
+    T = p_.shape[0]
     D = sum(d for d, _, _ in streams)
     Mn = sum(1 for _, _, m in streams if m)
     covdet = mahala = torch.zeros((), dtype=torch.float64)
@@ -85,6 +88,14 @@ def dense(pred, obs, var, gv_var, streams, msd_weight=1.0, gv_weight=1.0e-6, wan
     msd = (Mn * T * LN2PI + msd_covdet + msd_mahala) / (2.0 * Mn * T) if Mn else torch.zeros((), dtype=torch.float64)
     pv, ov = torch.cat(pvs), torch.cat(ovs)
     gv = (D * LN2PI + torch.log(g_).sum() + ((pv - ov) ** 2 / g_).sum()) / (2.0 * D)
+    return trj, msd, gv, cs, conds
+
+
+def dense(pred, obs, var, gv_var, streams, msd_weight=1.0, gv_weight=1.0e-6, want_cond=True):
+    import torch
+    f64 = lambda a: torch.tensor(np.asarray(a, dtype=np.float32).astype(np.float64))
+    p_, v_ = f64(pred).requires_grad_(True), f64(var).requires_grad_(True)
+    trj, msd, gv, cs, conds = dense_terms(p_, f64(obs), v_, f64(gv_var), streams, want_cond)
     total = trj + msd_weight * msd + gv_weight * gv
     total.backward()
     return {"cost": np.array([trj.item(), msd.item(), gv.item()]), "c": cs, "grad_pred": p_.grad.numpy(),
