@@ -325,6 +325,11 @@ int check_dnn_backward(int n_utt, const WorldMi355AcousticModel* m, const WorldM
 int launch_dnn_backward(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const WorldMi355Dropout* drop,
                         const float* x, int64_t ld_x, const int* spkr, const float* G, int64_t ld_g, float* const* gW,
                         float* const* gB, float* const* gS, int* d_status);
+int check_optimizer_step(const WorldMi355OptimizerOption* opt, int n_tensors, float* const* param, const float* const* grad,
+                         float* const* slot0, float* const* slot1, const int64_t* count, const float* rate);
+int launch_optimizer_step(Context& c, hipStream_t st, const WorldMi355OptimizerOption& opt, int n_tensors, float* const* param,
+                          const float* const* grad, float* const* slot0, float* const* slot1, const int64_t* count,
+                          const float* rate, int* d_status);
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);

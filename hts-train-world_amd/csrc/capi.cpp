@@ -408,6 +408,26 @@ int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355Acoustic
   return launch_dnn_backward(b->b, b->b.ctx->stream, *m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
                              grad_spkr_weights, status);
 }
+void WorldMi355DefaultOptimizerOption(int rule, WorldMi355OptimizerOption* o) {   // tf.train.*Optimizer's defaults (TF 1.x)
+  if (!o) return;
+  o->rule = rule;
+  o->momentum = rule == 1 ? 0.9f : 0.0f;
+  o->rho = rule == 3 ? 0.95f : 0.9f;
+  o->beta1 = 0.9f;
+  o->beta2 = 0.999f;
+  o->epsilon = rule == 5 ? 1e-10f : 1e-8f;
+  o->beta1_power = o->beta1;
+  o->beta2_power = o->beta2;
+}
+int WorldMi355OptimizerStep(WorldMi355Context* h, const WorldMi355OptimizerOption* opt, int n_tensors, float* const* param,
+                            const float* const* grad, float* const* slot0, float* const* slot1, const int64_t* count,
+                            const float* rate, int* status) {
+  if (!h) return WM_ERR_BAD_ARG;
+  if (const int rc = check_optimizer_step(opt, n_tensors, param, grad, slot0, slot1, count, rate))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(h->c);
+  return launch_optimizer_step(h->c, h->c.stream, *opt, n_tensors, param, grad, slot0, slot1, count, rate, status);
+}
 void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* o) {                     // SPTK's alpha and order, the recipe's beta and IMPLEN
   if (!o) return;
   o->alpha = 0.35;

@@ -702,3 +702,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "dnn.hip"
 // ---- its training pass: dropout, the backward pass and the cost gradients of DNNTraining.py (the same arrangement) -
 #include "dnn_train.hip"
+// ---- the step after it: tf.train.*'s update rules for every tensor of the model in one launch (the same arrangement) -
+#include "optim.hip"

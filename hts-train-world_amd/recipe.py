@@ -36,8 +36,9 @@ trajectory_files() / `trj-eval` stands where gen_param_files() stands when the m
 ($TRJGV, scripts/Training.pl:930-940): the outputs and the cost of DNNDefine.trajectory_cost; the loss itself, for a
 torch model, is training.TrajectoryLoss.
 
-train_files() / `dnn-train` is DNNTraining.py (SD and SAT; frame by frame, or with --stream trajectory training) on the
-library's training pass.
+train_files() / `dnn-train` is DNNTraining.py (SD, SAT and with --adapt ADAPT; frame by frame, or with --stream trajectory
+training) on the library's training pass; with --updates tf1 the step itself is the library's too (Tf1Optimizer: TF 1.x's
+update rules in one launch, the optimiser's state saved with the model).
 forward_files() / `dnn-forward` is the step in front of both (scripts/Training.pl:877, 906, 964, 993: DNNSynthesis.py
 frame by frame): the acoustic model's outputs for a list of `.ffi` files, the speaker's variance row and, where the
 targets are paired, the cost.
@@ -606,7 +607,7 @@ def make_optimizer(model, name, learning_rate):
     1e-8; RMSprop decay 0.9, eps 1e-10).  torch adds Adam's and RMSprop's eps outside the square root, TF inside it for
     RMSprop and to a rescaled root for Adam; and TF 1.x starts RMSprop's mean-square slot at ones, torch at zeros, so
     RMSprop's first steps are much larger here (the first about 1 / sqrt(0.1) times the rate, against about the gradient
-    times the rate in TF).  The trajectories are not TF's."""
+    times the rate in TF).  These trajectories are not TF's; Tf1Optimizer's follow TF's rules."""
     import torch
     named = list(model.named_parameters())
     pick = lambda key: [p for k, p in named if k.split(".")[-1].startswith(key)]
@@ -627,6 +628,125 @@ def make_optimizer(model, name, learning_rate):
     if name == "rmsprop":
         return torch.optim.RMSprop(groups, lr=learning_rate, alpha=0.9, eps=1e-10)
     raise ValueError("an optimiser is one of %s" % (OPTIMIZERS,))
+
+
+class Tf1Optimizer:
+    """make_optimizer's three groups (by the same test on the parameter's name) under TF 1.x's own update rules -- the
+    table in include/world_mi355.h, float32, every operation rounded on its own -- with the state tf.train.Saver keeps:
+    the slots per parameter and Adam's two beta powers.  The rates are (learning_rate, learning_rate, 0.01 learning_rate)
+    for the si_ parameters, the sd_ parameters and the variances; with adapt (DNNTraining.py's ADAPT mode, :297-303)
+    (0, learning_rate, 0.01 learning_rate): at rate 0 the slots move and the parameter keeps its bits.
+
+    ctx: the world.Context whose optimizer_step updates every tensor in one launch (the parameters are float32 cuda
+    tensors); or None: the same sequence of operations in torch float32 on the CPU, for parameters on the CPU -- the
+    loop's host path, as train_files(device="cpu") is.  step() reads every parameter's .grad and advances the powers."""
+
+    def __init__(self, model, name, learning_rate, ctx, adapt=False):
+        import torch
+        name = name.lower()
+        if name not in OPTIMIZERS:
+            raise ValueError("an optimiser is one of %s" % (OPTIMIZERS,))
+        self.name, self.rule, self.ctx = name, W.OPTIMIZER_RULES.index(name), ctx
+        rate_of = (("si_", 0.0 if adapt else learning_rate), ("sd_", learning_rate), ("variance", 0.01 * learning_rate))
+        self.names, self.params, self.rates = [], [], []
+        for key, rate in rate_of:
+            for k, p in model.named_parameters():
+                if k.split(".")[-1].startswith(key):
+                    self.names.append(k)
+                    self.params.append(p)
+                    self.rates.append(float(np.float32(rate)))
+        for p in self.params:
+            if p.dtype != torch.float32 or p.is_cuda != (ctx is not None) or not p.is_contiguous():
+                raise ValueError("Tf1Optimizer: float32 contiguous parameters, on the GPU with a context and on the CPU without")
+        self.slots = [[torch.full_like(p, v) for p in self.params] for v in W.OPTIMIZER_SLOT_INIT[self.rule]]
+        # TF 1.x's defaults in float32, as WorldMi355DefaultOptimizerOption sets them
+        f = np.float32
+        self.momentum, self.rho = f(0.9), f(0.95 if name == "adadelta" else 0.9)
+        self.beta1, self.beta2, self.epsilon = f(0.9), f(0.999), f(1e-10 if name == "rmsprop" else 1e-8)
+        self.beta1_power, self.beta2_power = self.beta1, self.beta2
+
+    def zero_grad(self, set_to_none=True):
+        for p in self.params:
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
+
+    def step(self):
+        import torch
+        grads = []
+        for k, p in zip(self.names, self.params):
+            if p.grad is None:
+                raise RuntimeError("Tf1Optimizer.step: %s has no gradient" % k)
+            grads.append(p.grad.to(torch.float32).contiguous())
+        with torch.no_grad():
+            if self.ctx is not None:
+                o = W.default_optimizer_option(self.rule, beta1_power=float(self.beta1_power), beta2_power=float(self.beta2_power))
+                self.ctx.optimizer_step(o, [p.data for p in self.params], grads, self.rates, *self.slots)
+            else:
+                for i, (p, g, r) in enumerate(zip(self.params, grads, self.rates)):
+                    self._host_update(p, g, r, [s[i] for s in self.slots])
+        self.beta1_power, self.beta2_power = self.beta1_power * self.beta1, self.beta2_power * self.beta2
+
+    def _host_update(self, p, g, r, slots):
+        """The table's operations one by one: torch's float32 CPU operations round each on its own, and no call here is
+        a fused one (no addcmul, no alpha=)."""
+        import torch
+        f = np.float32
+        c = lambda v: float(f(v))                     # a float32 value as the Python float torch casts back to it exactly
+        one = f(1.0)
+        if self.name == "sgd":
+            p.copy_(p - g * c(r))
+        elif self.name == "momentum":
+            a, = slots
+            a.copy_(a * c(self.momentum) + g)
+            p.copy_(p - a * c(r))
+        elif self.name == "adagrad":
+            a, = slots
+            a.copy_(a + g * g)
+            p.copy_(p - (g * c(r)) / torch.sqrt(a))
+        elif self.name == "adadelta":
+            a, b = slots
+            rho, eps = c(self.rho), c(self.epsilon)
+            a.copy_(a * rho + (g * g) * c(one - self.rho))
+            u = (torch.sqrt(b + eps) / torch.sqrt(a + eps)) * g
+            p.copy_(p - u * c(r))
+            b.copy_(b * rho + (u * u) * c(one - self.rho))
+        elif self.name == "adam":
+            m, v = slots
+            alpha = f(f(r) * np.sqrt(one - self.beta2_power)) / (one - self.beta1_power)
+            m.copy_(m + (g - m) * c(one - self.beta1))
+            v.copy_(v + (g * g - v) * c(one - self.beta2))
+            p.copy_(p - (m * c(alpha)) / (torch.sqrt(v) + c(self.epsilon)))
+        else:
+            s, = slots
+            s.copy_(s + (g * g - s) * c(one - self.rho))
+            p.copy_(p - (g * c(r)) / torch.sqrt(s + c(self.epsilon)))
+
+    def state_arrays(self):
+        """What AcousticModel.save(optimizer_state=...) writes: the rule's name, slot0/<parameter name> and
+        slot1/<parameter name> as float32 arrays, and the two beta powers."""
+        out = {"rule": np.array(self.name)}
+        for j, slot in enumerate(self.slots):
+            for k, t in zip(self.names, slot):
+                out["slot%d/%s" % (j, k)] = t.detach().cpu().numpy().copy()
+        out["beta1_power"] = np.array(self.beta1_power, dtype=np.float32)
+        out["beta2_power"] = np.array(self.beta2_power, dtype=np.float32)
+        return out
+
+    def load_state_arrays(self, state):
+        """Continue from state_arrays()' dictionary (AcousticModel.load leaves it in the module's optimizer_state)."""
+        import torch
+        if str(state.get("rule")) != self.name:
+            raise ValueError("the state is of optimiser %s, not %s" % (state.get("rule"), self.name))
+        with torch.no_grad():
+            for j, slot in enumerate(self.slots):
+                for k, t in zip(self.names, slot):
+                    v = state.get("slot%d/%s" % (j, k))
+                    if v is None or tuple(v.shape) != tuple(t.shape):
+                        raise ValueError("the state holds no slot%d of %s of shape %s" % (j, k, tuple(t.shape)))
+                    t.copy_(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)))
+        self.beta1_power, self.beta2_power = np.float32(state["beta1_power"]), np.float32(state["beta2_power"])
 
 
 def minibatches(frame_spkr, batch_size, n_steps, seed, start=0):
@@ -703,8 +823,8 @@ def _variance_rows(variance_dir, name, n_spkrs, width):
 def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, variance_dir=None, hidden_activation="sigmoid",
                 output_activation="linear", keep_prob=0.5, optimizer="adam", learning_rate=0.001, batch_size=256,
                 n_epochs=100, n_steps=None, seed=0, log_interval=100, save_interval=0, restore=None, streams=None,
-                msd_weight=1.0, gv_weight=1.0e-6, ctx=None, device="cuda", report=print):
-    """What DNNTraining.py does in SD and SAT mode: trains the acoustic model on a file list and saves it.
+                msd_weight=1.0, gv_weight=1.0e-6, ctx=None, device="cuda", report=print, updates="torch", adapt=False):
+    """What DNNTraining.py does in SD, SAT and ADAPT mode: trains the acoustic model on a file list and saves it.
 
     jobs:         [(ffi, ffo)] or [(ffi, ffo, speaker index)]: float32 rows of n_inputs and of n_outputs
     model_path:   the `.npz` to write (training.AcousticModel.save, with the step count): every save_interval steps
@@ -718,14 +838,27 @@ def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, varianc
                   batch_size utterances (utterance_minibatches).  The GV variances stay at gv.var: the library returns no
                   gradient with respect to them, and the `.npz` does not hold them
     restore:      None, or the `.npz` to continue from: the steps, the minibatch draws and the dropout offsets go on from
-                  its step count.  The optimiser's own state (momentum, Adam's moments ...) is not in the file and begins anew
+                  its step count.  With updates="tf1" the optimiser's own state (the slots, Adam's beta powers) goes on
+                  from the file's too, as with tf.train.Saver: a continued run is the run it continues, bit for bit.  A
+                  file without the state of this optimiser is reported in one line, and the state begins anew; with
+                  updates="torch" it always begins anew
+    updates:      "torch": one step of make_optimizer's optimiser (torch.optim's rules).  "tf1": one step of Tf1Optimizer
+                  (TF 1.x's rules; on the GPU one launch of the library's kernel), whose state every save writes
+    adapt:        DNNTraining.py's ADAPT mode (:102-107, 297-303, 323-328): needs `restore` with a SAT model of at least
+                  two speakers.  Before the first step every hidden layer's sd_weights[-1] becomes the float32 mean of the
+                  other speakers' rows; the si_ parameters then train at rate 0, the sd_ parameters at learning_rate, the
+                  variances at 0.01 learning_rate.  The jobs are the new (last) speaker's
     A step runs the library's training forward and backward with dropout (seed, offset = the step number) and one step of
-    make_optimizer's optimiser.  n_steps: None for n_epochs * frames // batch_size, in trajectory mode n_epochs * files //
+    the optimiser.  n_steps: None for n_epochs * frames // batch_size, in trajectory mode n_epochs * files //
     batch_size (DNNTraining.py:180-187).  Every log_interval steps `Step %7d: cost = %e` is reported (DNNTraining.py:369).
-    Returns the reported (step, cost) pairs.  ADAPT mode is not offered.  The whole corpus is held on the device."""
+    Returns the reported (step, cost) pairs.  The whole corpus is held on the device."""
     import torch
     from . import training
     jobs = [tuple(j) + (0,) * (3 - len(j)) for j in jobs]
+    if updates not in ("torch", "tf1"):
+        raise ValueError("updates is \"torch\" or \"tf1\"")
+    if adapt and (restore is None or n_spkrs < 2):
+        raise ValueError("adapt continues a SAT model of at least two speakers: give restore")
     frames = []
     for ffi, ffo, s in jobs:
         size = os.path.getsize(ffi)
@@ -749,6 +882,12 @@ def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, varianc
         if (model.n_inputs, model.units, model.n_outputs, model.n_spkrs) != (n_inputs, [int(n) for n in units], n_outputs, n_spkrs):
             raise ValueError("%s holds another net" % restore)
         start = model.step
+        if adapt:
+            if not model.sat:
+                raise ValueError("%s is no SAT model: nothing to adapt" % restore)
+            for i in range(len(model.units)):                          # DNNTraining.py:323-328
+                sd = model.hidden(i).sd_weights.detach().numpy()       # (the parameter's own memory)
+                sd[-1] = np.mean(sd[:-1], 0)
     else:
         model = training.AcousticModel(n_inputs, units, n_outputs, n_spkrs, hidden_activation, output_activation)
         if variance_dir is not None:                               # DNNTraining.py:116-127
@@ -766,7 +905,21 @@ def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, varianc
     obs = torch.from_numpy(np.concatenate([_f32(j[1], n_outputs) for j in jobs])).to(device)
     file_spkr = [int(j[2]) for j in jobs]
     f_off = np.concatenate([[0], np.cumsum(frames)])
-    opt = make_optimizer(model, optimizer, learning_rate)
+    if updates == "tf1":
+        opt = Tf1Optimizer(model, optimizer, learning_rate, ctx, adapt)
+        state = model.optimizer_state if restore is not None else None
+        if state is not None and str(state.get("rule")) == opt.name:
+            opt.load_state_arrays(state)
+        elif restore is not None:
+            report("%s holds no state of optimiser %s: its state begins anew" % (restore, opt.name))
+    else:
+        opt = make_optimizer(model, optimizer, learning_rate)
+        if adapt:
+            si = {id(p) for k, p in model.named_parameters() if k.split(".")[-1].startswith("si_")}
+            for g in opt.param_groups:
+                if g["params"] and id(g["params"][0]) in si:
+                    g["lr"] = 0.0
+    state_of = (lambda: opt.state_arrays()) if updates == "tf1" else (lambda: None)
     batch = (lambda lengths: W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)) if ctx is not None \
         else (lambda lengths: None)
     draws = minibatches(np.repeat(file_spkr, frames), batch_size, n_steps, seed, start) if layout is None \
@@ -803,8 +956,8 @@ def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, varianc
             log.append((step, float(cost.detach())))
             report("Step %7d: cost = %e" % log[-1])
         if save_interval > 0 and (step + 1 - start) % save_interval == 0 and step + 1 < start + n_steps:
-            model.save(model_path, step + 1)
-    model.save(model_path, start + n_steps)
+            model.save(model_path, step + 1, state_of())
+    model.save(model_path, start + n_steps, state_of())
     if own_ctx:
         ctx.close()
     return log
@@ -1433,7 +1586,11 @@ def main(argv=None):
     p.add_argument("--log-interval", type=int, default=100)
     p.add_argument("--save-interval", type=int, default=0)
     p.add_argument("--restore", default=None, help="a .npz to continue from: steps, draws and dropout offsets go on from "
-                   "its step count")
+                   "its step count; with --updates tf1 the optimiser's state too")
+    p.add_argument("--updates", default="torch", choices=("torch", "tf1"), help="torch: torch.optim's update rules; tf1: "
+                   "TF 1.x's own, in one launch of the library's kernel, with the optimiser's state saved in the .npz")
+    p.add_argument("--adapt", action="store_true", help="DNNTraining.py's ADAPT mode: needs --restore with a SAT model; the last "
+                   "speaker's sd_weights row starts at the mean of the others and the si_ parameters stay")
     p.add_argument("--stream", action="append", default=None, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
                    help="trajectory training (DNNTraining.py -w): one per stream in the row's order; minibatches are then "
                    "--batch-size utterances, and gv.var is read beside ffo.var")
@@ -1537,7 +1694,8 @@ def main(argv=None):
                     rows.append((w[0], w[1]) + ((int(w[2]),) if len(w) > 2 else ()))
         train_files(rows, a.model, a.inputs, a.units, a.outputs, a.spkrs, a.variance_dir, a.hidden_activation,
                     a.output_activation, a.keep_prob, a.optimizer, a.learning_rate, a.batch_size, a.epochs, a.steps, a.seed,
-                    a.log_interval, a.save_interval, a.restore, a.stream, a.msd_weight, a.gv_weight)
+                    a.log_interval, a.save_interval, a.restore, a.stream, a.msd_weight, a.gv_weight, updates=a.updates,
+                    adapt=a.adapt)
         return 0
     if a.cmd == "dnn-forward":
         forward_files(read_forward_scp(a.scp), a.model, a.out_dir, a.spkr, a.extension)

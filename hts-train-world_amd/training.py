@@ -265,13 +265,18 @@ class AcousticModel(torch.nn.Module):
         return _TrainOutputs.apply(self, batch, x, spkr, float(keep_prob), int(seed), int(offset), int(max_chunk_frames),
                                    *[p for _, p in self.train_parameters()])
 
-    def save(self, path, step=None):
+    def save(self, path, step=None, optimizer_state=None):
         """One `.npz`: float32 arrays under the parameters' names, and the two activation names; with `step`, the number
-        of training steps behind the parameters (load() leaves it in the module's `step`, 0 without one)."""
+        of training steps behind the parameters (load() leaves it in the module's `step`, 0 without one); with
+        optimizer_state (recipe.Tf1Optimizer.state_arrays: the rule's name, slot0/<parameter name>, slot1/<parameter
+        name>, beta1_power, beta2_power), those arrays under optimizer/<key> (load() leaves the dictionary in the module's
+        `optimizer_state`, None without one)."""
         import numpy as np
         arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in self.state_dict().items()}
         if step is not None:
             arrays["step"] = np.array(int(step), dtype=np.int64)
+        for k, v in (optimizer_state or {}).items():
+            arrays["optimizer/" + k] = np.asarray(v)
         arrays["hidden_activation"] = np.array(self.hidden_activation)
         arrays["output_activation"] = np.array(self.output_activation)
         with open(path, "wb") as f:
@@ -283,6 +288,7 @@ class AcousticModel(torch.nn.Module):
         with np.load(path, allow_pickle=False) as z:
             arrays = {k: z[k] for k in z.files}
         step = int(arrays.pop("step", 0))
+        state = {k[len("optimizer/"):]: arrays.pop(k) for k in [k for k in arrays if k.startswith("optimizer/")]}
         n = 0
         while "hidden%d.si_weights" % n in arrays:
             n += 1
@@ -296,4 +302,5 @@ class AcousticModel(torch.nn.Module):
                 str(arrays.pop("output_activation")), sat="hidden0.sd_weights" in arrays)
         m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in arrays.items()})
         m.step = step
+        m.optimizer_state = state or None
         return m

@@ -71,6 +71,27 @@ class Dropout(C.Structure):
 ACTIVATIONS = ("linear", "sigmoid", "tanh", "relu")      # Config.pm.in:228: the codes 0 .. 3
 
 
+class OptimizerOption(C.Structure):
+    """include/world_mi355.h: WorldMi355OptimizerOption (the update rules of TF 1.x's tf.train.* optimisers)."""
+    _fields_ = [("rule", C.c_int), ("momentum", C.c_float), ("rho", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("epsilon", C.c_float), ("beta1_power", C.c_float), ("beta2_power", C.c_float)]
+
+
+OPTIMIZER_RULES = ("sgd", "momentum", "adagrad", "adadelta", "adam", "rmsprop")      # the codes 0 .. 5
+OPTIMIZER_SLOTS = (0, 1, 1, 2, 2, 1)                     # the slots a rule keeps per parameter
+OPTIMIZER_SLOT_INIT = ((), (0.0,), (0.1,), (0.0, 0.0), (0.0, 0.0), (1.0,))      # TF 1.x's initial values
+
+
+def default_optimizer_option(rule, **over) -> OptimizerOption:
+    """TF 1.x's defaults of `rule` (a name or its code); the powers are the betas."""
+    o = OptimizerOption()
+    load_library().WorldMi355DefaultOptimizerOption(OPTIMIZER_RULES.index(rule) if isinstance(rule, str) else int(rule),
+                                                    C.byref(o))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
 class McpfOption(C.Structure):
     """include/world_mi355.h: WorldMi355McpfOption (the recipe's mel-cepstral postfilter, postfiltering_mcp)."""
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("order", C.c_int), ("length", C.c_int)]
@@ -168,6 +189,9 @@ def load_library():
                                                       vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, vp]
     L.WorldMi355AcousticModelBackward.argtypes = [vp, C.POINTER(AcousticModelDesc), C.POINTER(Dropout), vp, C.c_int64, vp,
                                                   vp, C.c_int64, vp, vp, vp, vp]
+    L.WorldMi355DefaultOptimizerOption.restype = None
+    L.WorldMi355DefaultOptimizerOption.argtypes = [C.c_int, C.POINTER(OptimizerOption)]
+    L.WorldMi355OptimizerStep.argtypes = [vp, C.POINTER(OptimizerOption), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -215,6 +239,35 @@ class Context:
         _check(load_library().WorldMi355TimingQuery(self.handle, kernel.encode(), C.byref(ms), C.byref(n)),
                "TimingQuery")
         return ms.value, n.value
+
+    def optimizer_step(self, option, params, grads, rates, slot0=None, slot1=None, want_status=False):
+        """One update of every tensor in ONE launch (csrc/optim.hip), by TF 1.x's rule option.rule (default_optimizer_option;
+        for adam the caller advances option.beta1_power and beta2_power after the call).  params, grads, slot0, slot1:
+        lists of float32 cuda contiguous tensors, a parameter's gradient and slots of its own number of elements (slot0:
+        every rule but sgd; slot1: adadelta and adam); rates: one float per tensor.  params and the slots are updated in
+        place.  Returns None, or with want_status an int32 cuda tensor [len(params)]: 1 where a gradient element of that
+        tensor is not finite.  Asynchronous on the context's stream."""
+        import torch
+        n = len(params)
+        need = OPTIMIZER_SLOTS[option.rule] if 0 <= option.rule < len(OPTIMIZER_SLOTS) else 0
+        lists = [params, grads] + [slot0, slot1][:need]
+        if any(l is None or len(l) != n for l in lists) or len(rates) != n:
+            raise ValueError("optimizer_step: %d parameters need as many gradients, rates and (%d) slots each" % (n, need))
+        for l in lists:
+            for t, p in zip(l, params):
+                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError("optimizer_step: every tensor must be float32, cuda and contiguous")
+                if t.numel() != p.numel() or t.device != p.device:
+                    raise ValueError("optimizer_step: a gradient or slot of %d elements for a parameter of %d"
+                                     % (t.numel(), p.numel()))
+        ptrs = [(C.c_void_p * n)(*[t.data_ptr() for t in l]) for l in lists] + [None] * (2 - need)
+        count = (C.c_int64 * n)(*[p.numel() for p in params])
+        rate = (C.c_float * n)(*[float(r) for r in rates])
+        status = torch.empty(n, dtype=torch.int32, device=params[0].device) if want_status and n else None
+        _check(load_library().WorldMi355OptimizerStep(self.handle, C.byref(option), n, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                                      count, rate, status.data_ptr() if status is not None else None),
+               "OptimizerStep")
+        return status
 
     def close(self):
         if self.handle:

@@ -393,6 +393,43 @@ int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355Acoustic
                                     const float* x, int64_t ld_x, const int* spkr, const float* grad_out, int64_t ld_grad,
                                     float* const* grad_weights, float* const* grad_biases, float* const* grad_spkr_weights,
                                     int* status);
+/* ---- The optimisers' update step: DNNDefine.get_optimizer (data/scripts/DNNDefine.py:65-80) names six tf.train.*
+ * optimisers of TF 1.x, which DNNDefine.training (:194-213) applies to three groups of tensors at three rates.  One call
+ * updates every tensor of every group in ONE launch.  rule: 0 sgd, 1 momentum, 2 adagrad, 3 adadelta, 4 adam, 5 rmsprop.
+ * With g the gradient, p the parameter, r the tensor's rate -- everything float32, every operation rounded on its own in
+ * the order written, nothing contracted into a fused multiply-add, division and square root correctly rounded,
+ * subnormals kept; 1 - rho and 1 - beta are float32 differences of the float32 fields:
+ *   rule                                 slots (initial value)  update
+ *   sgd                                  -                      p <- p - r g
+ *   momentum (momentum 0.9)              a (0)                  a <- a mu + g;  p <- p - a r
+ *   adagrad                              a (0.1)                a <- a + g g;  p <- p - (g r) / sqrt(a)
+ *   adadelta (rho 0.95, epsilon 1e-8)    a (0), b (0)           a <- a rho + (g g) (1 - rho);
+ *                                                               u = (sqrt(b + eps) / sqrt(a + eps)) g;  p <- p - u r;
+ *                                                               b <- b rho + (u u) (1 - rho)
+ *   adam (beta 0.9, 0.999, epsilon 1e-8) m (0), v (0)           alpha = r sqrt(1 - beta2_power) / (1 - beta1_power), on
+ *                                                               the host in float32;  m <- m + (g - m) (1 - beta1);
+ *                                                               v <- v + (g g - v) (1 - beta2);
+ *                                                               p <- p - (m alpha) / (sqrt(v) + eps)
+ *   rmsprop (rho 0.9, epsilon 1e-10)     s (1)                  s <- s + (g g - s) (1 - rho);
+ *                                                               p <- p - (g r) / sqrt(s + eps)
+ * The slots are the caller's, and so are their initial values (slot0: a, m, s; slot1: b, v).  beta1_power and beta2_power
+ * are TF's variables of that name: they start at beta1 and beta2, and the CALLER multiplies them by beta1 and beta2 after
+ * each step.  RMSprop is TF's at momentum 0, whose `momentum` slot holds the last update alone: it is not kept.  A rate of
+ * 0 is a rate: the slots move and p keeps its bits. */
+typedef struct { int rule; float momentum, rho, beta1, beta2, epsilon, beta1_power, beta2_power; } WorldMi355OptimizerOption;
+/* TF 1.x's defaults for `rule` (the table above); the powers are the betas. */
+void WorldMi355DefaultOptimizerOption(int rule, WorldMi355OptimizerOption* opt);
+/* param, grad, slot0, slot1: HOST arrays [n_tensors] of DEVICE float32 pointers, tensor k holding count[k] contiguous
+ * elements; count, rate: HOST [n_tensors].  slot0 is needed by every rule but sgd, slot1 by adadelta and adam; an array
+ * the rule does not need may be NULL and is not read.  Elements move 16 bytes at a time where all pointers of a tensor
+ * are 16-byte aligned, else one by one: the same bits either way.  status: NULL, or DEVICE int[n_tensors], zeroed by the
+ * call: 1 where a gradient element of the tensor is not finite; the update is applied as written all the same, as TF
+ * does.  n_tensors outside 1 .. 64, a rule outside 0 .. 5, a NULL required array or entry, a count below 1, a rate that
+ * is negative or not finite, a field of opt that is not finite, for adam a power outside (0, 1): WM_ERR_BAD_ARG before
+ * any device call.  A call of the context, not of a batch; asynchronous on the context's stream. */
+int WorldMi355OptimizerStep(WorldMi355Context* ctx, const WorldMi355OptimizerOption* opt, int n_tensors,
+                            float* const* param, const float* const* grad, float* const* slot0, float* const* slot1,
+                            const int64_t* count, const float* rate, int* status);
 /* ---- Mel-cepstral postfilter: the recipe's formant emphasis, postfiltering_mcp (scripts/Training.pl:2642-2687), which
  * gen_wave (:2813-2845) runs on every generated `.mgc` before mgc2sp -- the stage between
  * WorldMi355ParameterGeneration and WorldMi355MelCepstrumToSpectrum.  For one frame c[0 .. order] at warp alpha and
@@ -541,7 +578,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
  * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
  * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
  * column kernels and trj_reduce_kernel as one record, "dnn_layer_kernel": all layers of a call as one record,
- * "dnn_cost_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * "dnn_cost_kernel", "optimizer_step_kernel").  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
