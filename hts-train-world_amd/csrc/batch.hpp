@@ -241,7 +241,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn, ffi;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
 
   int64_t rng_bound_cheaptrick() const;
@@ -357,5 +357,15 @@ int check_column_moments(const float* d_x, int64_t ld, int width, const double* 
                          const double* d_mean, const double* d_m2);
 int launch_column_moments(Batch& b, hipStream_t st, const float* d_x, int64_t ld, int width, const double* ignore_value,
                           int64_t* d_count, double* d_mean, double* d_m2);
+struct LabelSet;                                    // a compiled question config and its device tables (ffi.hip)
+int label_set_create(Context& c, int n_features, const WorldMi355LabelFeature* f, LabelSet** out);
+void label_set_destroy(LabelSet* s);
+int label_set_count(const LabelSet* s);
+int check_label_features(const Batch& b, const LabelSet* set, const int* line_off, const int* start, const int* end,
+                         const int* state_index, const char* const* name, const int* state_level, const float* d_out,
+                         int64_t ld_out);
+int launch_label_features(Batch& b, hipStream_t st, const LabelSet& set, const int* line_off, const int* start,
+                          const int* end, const int* state_index, const char* const* name, const int* state_level,
+                          float* d_out, int64_t ld_out, int* d_status);
 
 }  // namespace wm

@@ -492,6 +492,34 @@ int WorldMi355ColumnMoments(WorldMi355Batch* b, const float* x, int64_t ld, int 
   OnDevice dev_(b->b.ctx[0]);
   return launch_column_moments(b->b, b->b.ctx->stream, x, ld, width, ignore_value, count, mean, m2);
 }
+int WorldMi355CreateLabelFeatureSet(WorldMi355Context* h, int n_features, const WorldMi355LabelFeature* features,
+                                    WorldMi355LabelFeatureSet** out) {
+  if (!out) return WM_ERR_BAD_ARG;
+  *out = nullptr;
+  if (!h) return WM_ERR_BAD_ARG;
+  OnDevice dev_(h->c);
+  LabelSet* s = nullptr;
+  const int rc = label_set_create(h->c, n_features, features, &s);              // a refused config makes no device call
+  *out = reinterpret_cast<WorldMi355LabelFeatureSet*>(s);
+  return rc;
+}
+void WorldMi355DestroyLabelFeatureSet(WorldMi355LabelFeatureSet* set) {
+  label_set_destroy(reinterpret_cast<LabelSet*>(set));
+}
+int WorldMi355LabelFeatureCount(const WorldMi355LabelFeatureSet* set) {
+  return label_set_count(reinterpret_cast<const LabelSet*>(set));
+}
+int WorldMi355LabelFeatures(WorldMi355Batch* b, const WorldMi355LabelFeatureSet* set, const int* line_off, const int* start,
+                            const int* end, const int* state_index, const char* const* name, const int* state_level,
+                            float* out, int64_t ld_out, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  const LabelSet* s = reinterpret_cast<const LabelSet*>(set);
+  if (const int rc = check_label_features(b->b, s, line_off, start, end, state_index, name, state_level, out, ld_out))
+    return rc;                                                                  // refused before any device call
+  OnDevice dev_(b->b.ctx[0]);
+  return launch_label_features(b->b, b->b.ctx->stream, *s, line_off, start, end, state_index, name, state_level, out,
+                               ld_out, status);
+}
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
   const int32_t a = n_frames, fs100 = (int32_t)(10000000.0 * frame_shift_samples / sampling_rate);

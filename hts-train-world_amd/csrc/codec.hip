@@ -704,3 +704,5 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 #include "dnn_train.hip"
 // ---- the step after it: tf.train.*'s update rules for every tensor of the model in one launch (the same arrangement) -
 #include "optim.hip"
+// ---- the network's input rows from aligned labels: data/scripts/makefeature.pl (the same arrangement) -
+#include "ffi.hip"

@@ -47,7 +47,9 @@ The way out goes on after `cmp` (the reference's `analysis` target is `features 
 ffo_files() / `ffo` writes the frame-by-frame training targets (:325-412: interpolate.pl on the msd stream, its voicing
 flag, window.pl, merge), stats_files() / `stats` the variances gen_param_files() reads and the GV of the corpus
 (:414-459), gv_data_files() / `gv-data` the per-utterance variance vectors of GV training (make_data_gv,
-scripts/Training.pl:1402-1491).
+scripts/Training.pl:1402-1491).  ffi_files() / `ffi` writes the other side of the training pairs, the acoustic model's
+input rows from aligned labels and a question config (make_train_data_dnn / make_gen_data_dnn, :1677-1723:
+data/scripts/makefeature.pl and x2x +af), which `dnn-train`, `dnn-forward` and `trj-eval` read.
 
 There is no CPU path: without a HIP device the library call fails.
 """
@@ -55,6 +57,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import struct
 import sys
 import wave
@@ -1048,6 +1051,166 @@ def ffo_files(jobs, streams, unvoiced_value=-1.0e10, ctx=None, max_batch_frames=
     return done
 
 
+# ---- the acoustic model's input rows from labels (data/scripts/makefeature.pl, Training.pl:1677-1723) ----------------
+_INTEGER = re.compile(rb"^[+-]?[0-9]+$")
+_LEADING_NUMBER = re.compile(rb"^\s*[+-]?(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?")
+
+
+def parse_question_config(text):
+    """makefeature.pl:63-180 on the text of a question config (str or bytes).  Returns (names, features): features is what
+    world.LabelFeatureSet takes, a list of (kind, pattern, min, max) with kind 0 binary, 1 float, 2 .. 7 the reserved
+    names in the script's order, pattern the text between the braces (None for a reserved feature), min = max = 0 for a
+    binary feature.  Raises ValueError with the script's message where the script dies."""
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    reserved = [n.encode() for n in W.RESERVED_LABEL_FEATURES]
+    names, features = [], []
+    for line in raw.split(b"\n"):
+        line = line.strip(b" \t\n\r\x0b\x0c")
+        if not line or line.startswith(b"#"):
+            continue
+        shown = line.decode("latin-1")
+        arr = line.split()
+        name, kind, patt = arr[0], None, b""
+        if name in reserved:
+            kind = 2 + reserved.index(name)
+        elif len(arr) > 1:
+            kind = 1 if arr[1].find(b"%d") > 0 else 0
+        if kind is None:
+            raise ValueError("ERROR: Cannot specify feature type : " + shown)
+        if kind <= 1 and arr[1].startswith(b"{") and arr[1].rfind(b"}") == len(arr[1]) - 1:
+            patt = arr[1][1:-1]
+        lo = hi = b""
+        for field in arr[1 if kind >= 2 else 2 if kind == 1 else 0:]:
+            if field.startswith(b"MIN="):
+                lo = field[4:]
+            elif field.startswith(b"MAX="):
+                hi = field[4:]
+        if kind <= 1 and patt == b"":
+            raise ValueError("ERROR: There is not feature patten : " + shown)
+        if kind == 1:
+            if patt.find(b"%d") < 0:
+                raise ValueError("ERROR: There is not '%d' in feature pattern : " + shown)
+            if patt.find(b"%d") != patt.rfind(b"%d"):
+                raise ValueError("ERROR: There are multiple '%d' in feature pattern : " + shown)
+            if b"," in patt:
+                raise ValueError("ERROR: There are multiple patterns for float in feature pattern : " + shown)
+        if kind >= 1:
+            if lo == b"" or hi == b"":
+                raise ValueError("ERROR: Min and max values are required : " + shown)
+            if not _INTEGER.match(lo) or not _INTEGER.match(hi):
+                raise ValueError("ERROR: Min and max values must be integer : " + shown)
+        names.append(name.decode("latin-1"))
+        features.append((kind, patt.decode("latin-1") if kind <= 1 else None, int(lo) if kind >= 1 else 0,
+                         int(hi) if kind >= 1 else 0))
+    return names, features
+
+
+def read_question_config(path):
+    """parse_question_config on a file."""
+    with open(path, "rb") as f:
+        return parse_question_config(f.read())
+
+
+def _perl_number(field):
+    m = _LEADING_NUMBER.match(field)                   # Perl's numeric value of a string: its leading number, else 0
+    return float(m.group(0)) if m else 0.0
+
+
+def parse_label(text, frame_shift):
+    """makefeature.pl:194-289 on the text of a label file; frame_shift in the label's time unit (100 ns, as
+    Training.pl:1685 passes it).  Returns (lines, state_level): lines a list of (start, end, name, state_index) with
+    start = int(0.5 + field 0 / frame_shift), end likewise, the state index the integer >= 2 between the name's last `[`
+    and its last character (else 0) and the name cut at that `[`; state_level whether the FIRST line had one.  A
+    phoneme-level line in a state-level file raises; a state-level line in a phoneme-level file is accepted with its name
+    cut, as the script's misspelt level check lets it through.  Raises ValueError with the script's message where the
+    script dies."""
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    body = raw.split(b"\n")
+    if body and body[-1] == b"":
+        body.pop()                                     # the text after the last newline is a line only if there is some
+    lines, level = [], None
+    for line in body:
+        line = line.strip(b" \t\n\r\x0b\x0c")
+        shown = line.decode("latin-1")
+        arr = line.split()
+        if len(arr) < 2:
+            raise ValueError("ERROR: There is not start/end time in label : " + shown)
+        start, end = (0.5 + _perl_number(f) / frame_shift for f in arr[:2])
+        if not (abs(start) < 1e15 and abs(end) < 1e15):
+            raise ValueError("ERROR: Start/end must be integer in label : " + shown)
+        start, end = int(start), int(end)
+        name = arr[2] if len(arr) > 2 else b""
+        left, right, state = name.rfind(b"["), name.rfind(b"]"), 0
+        if 0 < left < right:
+            inner = name[left + 1:-1]
+            if _INTEGER.match(inner) and int(inner) >= 2:
+                state = int(inner)
+                name = name[:left]
+        if end <= start or start < 0:
+            raise ValueError("ERROR: There is error of start/end value in label : " + shown)
+        if name == b"":
+            raise ValueError("ERROR: There is not model name in label : " + shown)
+        if level is None:
+            level = state > 0
+        elif level and state == 0:
+            raise ValueError("ERROR: There is phoneme-level line in state-level label : " + shown)
+        lines.append((start, end, name.decode("latin-1"), state))
+    if level is None:
+        raise ValueError("ERROR: Unknown label level")
+    return lines, level
+
+
+def read_label(path, frame_shift):
+    """parse_label on a file."""
+    with open(path, "rb") as f:
+        return parse_label(f.read(), frame_shift)
+
+
+def ffi_files(jobs, config, frame_shift, ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """make_train_data_dnn / make_gen_data_dnn (scripts/Training.pl:1677-1723) for a file list: `makefeature.pl config
+    frame_shift label | x2x +af > ffi`.
+
+    jobs:   [(label_file, ffi_out)]; ffi_out: float32 [T][n_features], T the sum of the lines' end - start (no header)
+    config: the question config's path, or what parse_question_config returned
+    frame_shift: in 100 ns units, as Training.pl:1685 passes it
+    Rank-sharded by frame count; with resume, utterances whose ffi file is complete are skipped.  Where the script warns,
+    the utterances are counted per kind and the counts printed on stderr ("Out of range": a value was clamped to 0 or 1;
+    "There is not state-level information in label").  Returns the frames written."""
+    import torch
+    jobs = list(jobs)
+    if any(len(j) != 2 for j in jobs):
+        raise ValueError("ffi_files: a job is (label_file, ffi_out)")
+    names, features = read_question_config(config) if isinstance(config, (str, os.PathLike)) else config
+    nf = len(features)
+    if nf < 1:
+        raise ValueError("ffi_files: the question config holds no feature")
+    labels = [read_label(j[0], frame_shift) for j in jobs]
+    frames = [sum(e - s for s, e, _, _ in lines) for lines, _ in labels]
+    todo = [i for i in range(len(jobs)) if not (resume and _size_is(jobs[i][1], 4 * nf * frames[i]))]
+    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    if not mine:
+        return 0
+    own_ctx = ctx is None
+    ctx = ctx or _own_context()
+    fset = W.LabelFeatureSet(ctx, features)
+    done, clamped, no_state = 0, 0, 0
+    for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+        b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
+        out, status = b.label_features(fset, [labels[i] for i in group])
+        rows, status = out.cpu().numpy(), status.cpu().numpy()
+        fo = b.frame_offsets
+        W.write_files([(jobs[i][1], np.ascontiguousarray(rows[fo[k]:fo[k + 1]])) for k, i in enumerate(group)], io_threads)
+        clamped += int((status & 1 != 0).sum())
+        no_state += int((status & 2 != 0).sum())
+        done += int(b.total_frames)
+        b.close()
+    fset.close()
+    if own_ctx:
+        ctx.close()
+    print("warnings: Out of range in %d utterances, no state-level information in %d" % (clamped, no_state), file=sys.stderr)
+    return done
+
+
 def stats_files(ffo_paths, streams, out_dir, names=("mgc", "lf0", "bap", "vib"), ctx=None,
                 max_batch_frames=MAX_BATCH_FRAMES, io_threads=8):
     """The recipe's `stats` stage (data/Makefile.in:414-459) over a list of ffo files.
@@ -1644,7 +1807,19 @@ def main(argv=None):
     p.add_argument("--silence", action="append", default=[], help="a label name to drop (may be repeated)")
     p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
     p.add_argument("--resume", action="store_true", help="skip utterances whose cmp file is already complete")
+    p = sub.add_parser("ffi", help="make_train_data_dnn / make_gen_data_dnn: the acoustic model's input rows from label files "
+                       "(makefeature.pl | x2x +af)")
+    p.add_argument("--scp", required=True, help="job list: the label file, then the ffi file to write")
+    p.add_argument("--config", required=True, help="the question config (qconf)")
+    p.add_argument("--frame-shift", type=int, required=True, help="one frame in the label's time unit of 100 ns (50000 for 5 ms)")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose ffi file is already complete")
     a = ap.parse_args(argv)
+    if a.cmd == "ffi":
+        if a.frame_shift < 1:
+            ap.error("--frame-shift must be positive")
+        n = ffi_files(_read_scp(a.scp, 2), a.config, a.frame_shift, resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
     if a.cmd == "ffo":
         n = ffo_files(_read_scp(a.scp, len(a.stream) + 1), a.stream, a.unvoiced_value, resume=a.resume)
         print("complete. %d frames" % n)

@@ -102,6 +102,16 @@ class MspfOption(C.Structure):
     _fields_ = [("frame_length", C.c_int), ("fft_length", C.c_int), ("emphasis", C.c_double)]
 
 
+class LabelFeature(C.Structure):
+    """include/world_mi355.h: WorldMi355LabelFeature (one feature of makefeature.pl's question config)."""
+    _fields_ = [("kind", C.c_int), ("pattern", C.c_char_p), ("min", C.c_int), ("max", C.c_int)]
+
+
+# makefeature.pl:55, in the order of the kinds 2 .. 7
+RESERVED_LABEL_FEATURES = ("Pos_C-State_in_Phone(Fw)", "Pos_C-State_in_Phone(Bw)", "Pos_C-Frame_in_State(Fw)",
+                           "Pos_C-Frame_in_State(Bw)", "Pos_C-Frame_in_Phone(Fw)", "Pos_C-Frame_in_Phone(Bw)")
+
+
 def build_library() -> None:
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "-j8"])
 
@@ -193,6 +203,12 @@ def load_library():
     L.WorldMi355DefaultOptimizerOption.argtypes = [C.c_int, C.POINTER(OptimizerOption)]
     L.WorldMi355OptimizerStep.argtypes = [vp, C.POINTER(OptimizerOption), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.WorldMi355WriteFiles.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int]
+    L.WorldMi355CreateLabelFeatureSet.argtypes = [vp, C.c_int, C.POINTER(LabelFeature), C.POINTER(vp)]
+    L.WorldMi355DestroyLabelFeatureSet.restype = None
+    L.WorldMi355DestroyLabelFeatureSet.argtypes = [vp]
+    L.WorldMi355LabelFeatureCount.argtypes = [vp]
+    L.WorldMi355LabelFeatures.argtypes = [vp, vp, _ip, _ip, _ip, _ip, C.POINTER(C.c_char_p), _ip, vp, C.c_int64, vp]
+    L.WorldMi355LabelPatternMatch.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, _ip, _ip]
     L.WorldMi355HtkHeader.restype = None
     L.WorldMi355HtkHeader.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.WorldMi355TimingEnable.argtypes = [vp, C.c_int]
@@ -273,6 +289,42 @@ class Context:
         if self.handle:
             load_library().WorldMi355DestroyContext(self.handle)
             self.handle = None
+
+
+class LabelFeatureSet:
+    """A compiled question config and its device tables (WorldMi355CreateLabelFeatureSet).  features: a list of
+    (kind, pattern, min, max) -- kind 0 binary, 1 float, 2 .. 7 the reserved names in RESERVED_LABEL_FEATURES' order;
+    pattern the text between the braces (None for a reserved feature) -- as recipe.read_question_config returns it.
+    Close it before its context."""
+
+    def __init__(self, ctx: Context, features):
+        feats = [(int(k), None if p is None else (p.encode("latin-1") if isinstance(p, str) else bytes(p)), int(lo), int(hi))
+                 for k, p, lo, hi in features]
+        if any(not -2 ** 31 <= v < 2 ** 31 for _, _, lo, hi in feats for v in (lo, hi)):
+            raise ValueError("LabelFeatureSet: min and max must fit an int")
+        arr = (LabelFeature * max(1, len(feats)))(*[LabelFeature(k, p, lo, hi) for k, p, lo, hi in feats])
+        h = C.c_void_p()
+        _check(load_library().WorldMi355CreateLabelFeatureSet(ctx.handle, len(feats), arr, C.byref(h)),
+               "CreateLabelFeatureSet")
+        self.ctx = ctx
+        self.handle = h
+        self.n_features = int(load_library().WorldMi355LabelFeatureCount(h))
+
+    def close(self):
+        if self.handle:
+            load_library().WorldMi355DestroyLabelFeatureSet(self.handle)
+            self.handle = None
+
+
+def label_pattern_match(pattern, name, is_float=False, engine=0):
+    """One pattern (the text between the braces) against one label name on the host (WorldMi355LabelPatternMatch):
+    engine 0 the backtracking matcher, 1 the kernel's bit-parallel program (binary patterns only).  Returns (matched,
+    captured value)."""
+    enc = lambda s: s.encode("latin-1") if isinstance(s, str) else bytes(s)
+    m, v = C.c_int(0), C.c_int(0)
+    _check(load_library().WorldMi355LabelPatternMatch(enc(pattern), 1 if is_float else 0, enc(name), int(engine),
+                                                      C.byref(m), C.byref(v)), "LabelPatternMatch")
+    return bool(m.value), int(v.value)
 
 
 def _ints(a):
@@ -694,6 +746,51 @@ class WorldBatch:
         _check(load_library().WorldMi355ComposeFfo(self.handle, n, data, dims, nwin, wptrs, sptrs, msds,
                                                    C.c_void_p(out.data_ptr())), "ComposeFfo")
         return out
+
+    def label_features(self, feature_set, labels, out=None):
+        """data/scripts/makefeature.pl for the batch (a synthesis-style one: f0_lengths are the labels' frame counts):
+        the acoustic model's input rows.  labels: per utterance (lines, state_level) as recipe.read_label returns them,
+        lines a list of (start, end, name, state_index) in frames with the state suffix cut from the name.  out: None, or
+        a float32 cuda tensor [total_frames][>= n_features] with unit column stride (a view of a wider or an unaligned
+        buffer works as it is); only its first n_features columns are written.  Returns (out float32 [total_frames]
+        [n_features] with the script's bits, status int32 [n_utt]: bit 1 a value was clamped to 0 or 1 -- the script's
+        "Out of range" warning --, bit 2 a state-related reserved feature met a phoneme-level file)."""
+        import torch
+        if len(labels) != self.n_utt:
+            raise ValueError(f"label_features: {len(labels)} label files for {self.n_utt} utterances")
+        nf = feature_set.n_features
+        line_off = np.zeros(self.n_utt + 1, dtype=np.int32)
+        rows, names = [], []
+        for u, (lines, _) in enumerate(labels):
+            line_off[u + 1] = line_off[u] + len(lines)
+            for start, end, name, state_index in lines:
+                raw = name.encode("latin-1") if isinstance(name, str) else bytes(name)
+                if b"\0" in raw:
+                    raise ValueError("label_features: a label name holds a NUL byte")
+                rows.append((start, end, state_index))
+                names.append(raw)
+        n = len(rows)
+        cols = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(n, 3).T)
+        if n and (np.abs(cols) >= 2 ** 31).any():
+            raise ValueError("label_features: a start, end or state index does not fit an int")
+        start, end, sidx = (np.ascontiguousarray(c, dtype=np.int32) for c in cols)
+        level = np.ascontiguousarray([1 if lv else 0 for _, lv in labels], dtype=np.int32)
+        if out is None:
+            out = torch.empty(self.total_frames, nf, dtype=torch.float32, device="cuda")
+        elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2
+              or out.shape[0] != self.total_frames or out.stride(1) != 1):
+            raise ValueError(f"label_features: out must be a float32 cuda tensor [{self.total_frames}][>= {nf}] with unit "
+                             "column stride")
+        ld = int(out.stride(0)) if self.total_frames > 1 else max(int(out.stride(0)), int(out.shape[1]))
+        if out.shape[1] < nf:
+            ld = min(ld, int(out.shape[1]))                      # refused by the library: ld_out < n_features
+        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        name_ptrs = (C.c_char_p * max(1, n))(*names)
+        ip = lambda a: a.ctypes.data_as(_ip)
+        _check(load_library().WorldMi355LabelFeatures(self.handle, feature_set.handle, ip(line_off), ip(start), ip(end),
+                                                      ip(sidx), name_ptrs, ip(level), C.c_void_p(out.data_ptr()), ld,
+                                                      C.c_void_p(status.data_ptr())), "LabelFeatures")
+        return out[:, :nf], status
 
     def column_moments(self, x, width=None, ignore_value=None):
         """Per-utterance moments of the first `width` columns (all of them by default) of x, float32 cuda

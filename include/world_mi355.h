@@ -547,6 +547,61 @@ int WorldMi355ComposeFfo(WorldMi355Batch* b, int n_streams, const float* const* 
  * a batch of zero frames returns WM_OK. */
 int WorldMi355ColumnMoments(WorldMi355Batch* b, const float* x, int64_t ld, int width, const double* ignore_value,
                             int64_t* count, double* mean, double* m2);
+/* ---- The acoustic model's input rows from aligned labels: data/scripts/makefeature.pl, which make_train_data_dnn and
+ * make_gen_data_dnn (scripts/Training.pl:1677-1723) pipe every label file through; the result is the `.ffi` rows that
+ * WorldMi355AcousticModelForward reads.
+ *
+ * A feature of the question config.  kind 0: binary, pattern is the text between the braces, comma-separated
+ * alternatives; the feature is 1 when any alternative matches the whole label name.  kind 1: float, one alternative
+ * with exactly one %d; the captured integer, normalised.  kind 2 .. 7: the reserved names in the order of
+ * makefeature.pl:55 -- state in phone forward / backward, frame in state forward / backward, frame in phone forward /
+ * backward; pattern is not read.  min, max: kinds 1 .. 7.  In a pattern `*` is any run of characters, `?` zero or ONE
+ * character, `.` any one character (the script does not escape it), every other byte itself; the match is Perl's
+ * ^...$ in backtracking order, which decides what %d ([+-]?[0-9]+) captures when several ways match.  A value below
+ * min is 0, above max 1 (the script's "Out of range" warning), else (float)((double)(v - min) / (double)(max - min)):
+ * the bits `perl makefeature.pl | x2x +af` gives for max - min <= 2^20.  An unmatched float feature is 0.
+ * Refused when the set is made: a pattern byte outside 0x21-0x7E, one of \ ( ) { } in a pattern (the script leaves them
+ * active as regex syntax), an alternative of more than 63 tokens (%d is one token): WM_ERR_UNSUPPORTED; a kind outside
+ * 0 .. 7, a NULL pattern, a float pattern without exactly one %d or with a comma, max - min > 2^20, and max <= min:
+ * WM_ERR_BAD_ARG -- this last differs from the script, which divides by zero only when it gets there.  An empty
+ * alternative is valid and matches nothing.  A captured integer beyond the range of int saturates.
+ * The float features are host work (a few dozen per config, evaluated once per distinct name of a call by a
+ * backtracking matcher and uploaded as a float32 table); the binary features are the device's.
+ * The set owns its device tables and is destroyed before its context. */
+typedef struct { int kind; const char* pattern; int min, max; } WorldMi355LabelFeature;
+typedef struct WorldMi355LabelFeatureSet WorldMi355LabelFeatureSet;
+int WorldMi355CreateLabelFeatureSet(WorldMi355Context* ctx, int n_features, const WorldMi355LabelFeature* features,
+                                    WorldMi355LabelFeatureSet** out);
+void WorldMi355DestroyLabelFeatureSet(WorldMi355LabelFeatureSet* set);
+int WorldMi355LabelFeatureCount(const WorldMi355LabelFeatureSet* set);
+/* The rows of a batch (a synthesis-style one: f0_lengths only).  Utterance u owns the label lines line_off[u] ..
+ * line_off[u+1]-1 (HOST, n_utt + 1 offsets); per line (HOST): start and end in frames (int(0.5 + time / frame_shift)),
+ * state_index (the integer >= 2 in the name's trailing [..], else 0) and name, the model name with that state suffix
+ * already cut; state_level[u] (HOST): the file's first line had a state suffix.  The rows of an utterance are its
+ * lines' [start, end) ranges one after another -- lines are not checked against each other, as in the script -- so
+ * the sum of end - start must equal the utterance's frame count.  A state-level line's phoneme reaches back while the
+ * previous line's state index is smaller and forward while the next one's is larger (:300-316); in a phoneme-level
+ * file every line is its own phoneme, whatever its state index (the script's misspelt level check lets such lines in).
+ * out: DEVICE float32, row t of the batch at out + t * ld_out, columns [0, n_features) written and nothing else; 16-byte
+ * stores where ld_out and the pointer allow, the same bits either way.  status: NULL, or DEVICE int[n_utt]: bit 1 a
+ * value of the utterance was clamped to 0 or 1 (the "Out of range" warning), bit 2 a state-related reserved feature
+ * (kinds 2 .. 5) met a phoneme-level file and took the value min (the "There is not state-level information" warning).
+ * No result depends on the batch around an utterance or on how names repeat.  Distinct names are found inside the
+ * call, on the host.  A NULL required pointer, a set of another context, ld_out < n_features, end <= start, start < 0,
+ * lines that do not add up to the frame count, an empty name: WM_ERR_BAD_ARG; a name longer than 1023 bytes or with a
+ * byte outside 0x21-0x7E: WM_ERR_UNSUPPORTED; all before any device call.  Asynchronous on the context's stream after
+ * its uploads (a second call on the same batch first waits for the first one's work); a batch of zero frames returns
+ * WM_OK.  Timed as "label_match_kernel" and "ffi_rows_kernel". */
+int WorldMi355LabelFeatures(WorldMi355Batch* b, const WorldMi355LabelFeatureSet* set, const int* line_off,
+                            const int* start, const int* end, const int* state_index, const char* const* name,
+                            const int* state_level, float* out, int64_t ld_out, int* status);
+/* One pattern against one name (host only: no context, no HIP call).  pattern and is_float as in a feature; engine 0 is
+ * the backtracking matcher, engine 1 the bit-parallel program of label_match_kernel stepped on the host through the
+ * kernel's own step function (binary patterns only: WM_ERR_BAD_ARG with is_float).  *matched: 0 / 1; *value (may be
+ * NULL): what %d captured, 0 otherwise.  Refusals as above. */
+int WorldMi355LabelPatternMatch(const char* pattern, int is_float, const char* name, int engine, int* matched,
+                                int* value);
+
 /* The 12-byte HTK header of addhtkheader.pl:60-75 (host only, native byte order). */
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]);
@@ -578,7 +633,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
  * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
  * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
  * column kernels and trj_reduce_kernel as one record, "dnn_layer_kernel": all layers of a call as one record,
- * "dnn_cost_kernel", "optimizer_step_kernel").  Enable clears earlier records; Query synchronises the stream and
+ * "dnn_cost_kernel", "optimizer_step_kernel", "label_match_kernel", "ffi_rows_kernel").  Enable clears earlier records; Query synchronises the stream and
  * returns the summed duration and the number of launches since Enable. */
 int WorldMi355TimingEnable(WorldMi355Context* ctx, int on);
 int WorldMi355TimingQuery(WorldMi355Context* ctx, const char* kernel, double* total_ms, int* launches);
