@@ -331,6 +331,8 @@ int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const 
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {
+  if (const int rc = check_compose_cmp(n_streams, streams, dims, n_windows, windows, window_sizes, out)) return rc;
+  if (!b) return WM_ERR_BAD_ARG;
   OnDevice dev_(b->b.ctx[0]);
   return launch_compose_cmp(b->b, n_streams, streams, dims, n_windows, windows, window_sizes, out);
 }

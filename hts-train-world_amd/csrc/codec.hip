@@ -26,6 +26,7 @@
 #include "fastmath.hpp"
 #include "fft.hpp"
 #include "freqt.hpp"
+#include "streamwin.hpp"
 #include "window.hpp"
 
 namespace wm {
@@ -589,36 +590,6 @@ int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const
 // contraction: the float32 results are bit-identical to the script's.
 namespace wm {
 
-constexpr int kCmpMaxStreams = 4, kCmpMaxWin = 4, kCmpMaxTaps = 15;
-struct CmpMeta {
-  int n_streams, total_cols;
-  int dim[kCmpMaxStreams], nwin[kCmpMaxStreams], col0[kCmpMaxStreams];
-  int wsize[kCmpMaxStreams][kCmpMaxWin];
-  unsigned chk[kCmpMaxStreams][kCmpMaxWin];                 // bit k: tap k takes part in the boundary check
-  double w[kCmpMaxStreams][kCmpMaxWin][kCmpMaxTaps];
-  const float* data[kCmpMaxStreams];
-};
-
-// One value of the composed row: window wi of stream s at dim j of `frame`, whose utterance covers frames lo .. hi.
-// cmp_compose_kernel and ffo_compose_kernel (ffo.hip) both take their values from here.
-__device__ __forceinline__ float cmp_window_value(const CmpMeta& m, int s, int wi, int j, int64_t frame, int64_t lo,
-                                                  int64_t hi) {
-#pragma clang fp contract(off)
-  const int dim = m.dim[s];
-  const int size = m.wsize[s][wi], nlr = (size - 1) / 2;
-  const float* src = m.data[s];
-  bool boundary = false;
-  double acc = 0.0;
-  for (int k = 0; k < size; ++k) {
-    int64_t l = frame + (k - nlr);
-    l = l < lo ? lo : (l > hi ? hi : l);
-    const double v = (double)src[l * dim + j];
-    if (((m.chk[s][wi] >> k) & 1u) && v == -1.0e+10) boundary = true;
-    acc += m.w[s][wi][k] * v;
-  }
-  return boundary ? -1.0e+10f : (float)acc;
-}
-
 __global__ __launch_bounds__(256) void cmp_compose_kernel(CmpMeta m, const int* __restrict__ frame_utt,
                                                           const int64_t* __restrict__ f_off, int64_t total_frames,
                                                           float* __restrict__ out) {
@@ -628,48 +599,31 @@ __global__ __launch_bounds__(256) void cmp_compose_kernel(CmpMeta m, const int* 
   const int col = (int)(idx - frame * m.total_cols);
   int s = 0;
 #pragma unroll
-  for (int q = 1; q < kCmpMaxStreams; ++q)
+  for (int q = 1; q < kWinMaxStreams; ++q)
     if (q < m.n_streams && col >= m.col0[q]) s = q;
-  const int dim = m.dim[s];
+  const int dim = m.win.dim[s];
   const int c = col - m.col0[s];
   const int wi = c / dim, j = c - wi * dim;
   const int u = frame_utt[frame];
   out[idx] = cmp_window_value(m, s, wi, j, frame, f_off[u], f_off[u + 1] - 1);
 }
 
-// the streams' windows into m; col0 and total_cols are the `cmp` row's (ComposeCmp's and ComposeFfo's limits)
-static int cmp_fill_meta(CmpMeta& m, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
-                         const double* const* const* windows, const int* const* window_sizes) {
-  if (n_streams < 1 || n_streams > kCmpMaxStreams) return WM_ERR_BAD_ARG;
-  memset(&m, 0, sizeof(m));
-  m.n_streams = n_streams;
-  int col = 0;
-  for (int s = 0; s < n_streams; ++s) {
-    if (dims[s] < 1 || n_windows[s] < 1 || n_windows[s] > kCmpMaxWin) return WM_ERR_BAD_ARG;
-    m.dim[s] = dims[s];
-    m.nwin[s] = n_windows[s];
-    m.col0[s] = col;
-    m.data[s] = d_data[s];
-    for (int i = 0; i < n_windows[s]; ++i) {
-      const int size = window_sizes[s][i];
-      if (size < 1 || size > kCmpMaxTaps || size % 2 != 1) return WM_ERR_BAD_ARG;   // window.pl:96-98
-      m.wsize[s][i] = size;
-      unsigned chk = (1u << size) - 1u;                           // window.pl:83-94: leading / trailing zero taps
-      for (int k = 0; k < size; ++k) { if (windows[s][i][k] != 0.0) break; chk &= ~(1u << k); }
-      for (int k = size - 1; k >= 0; --k) { if (windows[s][i][k] != 0.0) break; chk &= ~(1u << k); }
-      m.chk[s][i] = chk;
-      for (int k = 0; k < size; ++k) m.w[s][i][k] = windows[s][i][k];
-    }
-    col += dims[s] * n_windows[s];
-  }
-  m.total_cols = col;
+// What WorldMi355ComposeCmp refuses, on the host alone: no device call is made for a refused argument set.
+int check_compose_cmp(int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
+                      const double* const* const* windows, const int* const* window_sizes, const float* d_out) {
+  if (!d_data || !d_out) return WM_ERR_BAD_ARG;
+  if (const int rc = check_windows(n_streams, dims, n_windows, windows, window_sizes, kWinMaxStreams, kWinMaxWin, kWinMaxTaps))
+    return rc;
+  for (int s = 0; s < n_streams; ++s)
+    if (!d_data[s]) return WM_ERR_BAD_ARG;
   return WM_OK;
 }
 
 int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
                        const double* const* const* windows, const int* const* window_sizes, float* d_out) {
+  if (const int rc = check_compose_cmp(n_streams, d_data, dims, n_windows, windows, window_sizes, d_out)) return rc;
   CmpMeta m;
-  if (const int rc = cmp_fill_meta(m, n_streams, d_data, dims, n_windows, windows, window_sizes)) return rc;
+  cmp_fill_meta(m, n_streams, d_data, dims, n_windows, windows, window_sizes);
   const int64_t n = b.total_f * m.total_cols;
   if (n <= 0) return WM_OK;
   TimedScope ts_(b.ctx, b.ctx->stream, "cmp_compose_kernel");
@@ -679,30 +633,3 @@ int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, cons
 }
 
 }  // namespace wm
-
-// ---- SURVEY.md section 2, row 15, encoder half: SPTK's mcep + theq, the inverse of the bap decoder above ----------
-// mcep.hip is a file of its own but not a unit of its own: tests/hostsan/build_capi_harness.sh lists the library's
-// sources by name and does not change with a feature, so a new unit would leave the host-sanitizer harness with an
-// undefined launch_mel_cepstrum.  Compiled here, every build that lists codec.hip has it.  Its includes are guarded
-// headers this unit already has, and it reopens namespace wm.
-#include "mcep.hip"
-// ---- the decoder half: SPTK's mgc2sp at any gamma, every bin, in double (the same arrangement) ----------------------
-#include "mgc2sp.hip"
-// ---- the inverse of cmp_compose_kernel: static trajectories from `cmp`-layout means and variances (SPTK's mlpg) ------
-#include "mlpg.hip"
-// ---- the recipe's formant emphasis between the two: postfiltering_mcp of gen_wave (the same arrangement) --------------
-#include "mcpf.hip"
-// ---- the branch gen_wave takes instead with USEMSPF: postfiltering_mspf and make_mspf's sums (the same arrangement) ---
-#include "mspf.hip"
-// ---- the two stages after `cmp`: gap interpolation, `ffo` rows and per-utterance column moments (the same arrangement) -
-#include "ffo.hip"
-// ---- the criterion of trajectory training on the same banded factor: DNNDefine.trajectory_cost (the same arrangement) -
-#include "trj.hip"
-// ---- the network between `ffi` and `ffo`: DNNDefine.inference and the frame-level cost (the same arrangement) -
-#include "dnn.hip"
-// ---- its training pass: dropout, the backward pass and the cost gradients of DNNTraining.py (the same arrangement) -
-#include "dnn_train.hip"
-// ---- the step after it: tf.train.*'s update rules for every tensor of the model in one launch (the same arrangement) -
-#include "optim.hip"
-// ---- the network's input rows from aligned labels: data/scripts/makefeature.pl (the same arrangement) -
-#include "ffi.hip"

@@ -17,6 +17,7 @@ namespace wm {
 
 constexpr double kPi = 3.1415926535897932384;
 constexpr double kLog2 = 0.69314718055994529;
+constexpr double kLn2Pi = 1.8378770664093454835606594728112;  // ln 2 pi of the Gaussian costs (trj.hip, dnn.hip, dnn_train.hip)
 constexpr double kSafe = 0.000000000001;                       // kMySafeGuardMinimum
 constexpr double kEps = 0.00000000000000022204460492503131;   // kEps
 constexpr double kDefaultF0 = 500.0;

@@ -28,38 +28,9 @@
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "dnn.hpp"
 
 namespace wm {
-
-constexpr int kDnnMaxLayers = 8;
-constexpr int kDnnBM = 128, kDnnBN = 128, kDnnBK = 32;
-constexpr int kDnnLd = 132;                                  // words per k row of either LDS tile (16-byte rows)
-constexpr int64_t kDnnChunk = 65536, kDnnMaxChunk = (int64_t)1 << 20;
-constexpr double kDnnLn2Pi = 1.8378770664093454835606594728112;
-typedef float dnn_f32x16 __attribute__((ext_vector_type(16)));
-
-// 0 linear, 1 sigmoid, 2 tanh, 3 ReLU (Config.pm.in:228).  expf and tanhf are the device library's (1 and 2 ulp), the
-// addition and the division IEEE: the activation's own error stays under 8 * 2^-24 |value|.
-template <int ACT> __device__ __forceinline__ float dnn_act(float v) {
-  if (ACT == 1) return 1.0f / (1.0f + expf(-v));
-  if (ACT == 2) return tanhf(v);
-  if (ACT == 3) return v > 0.0f ? v : 0.0f;
-  return v;
-}
-
-struct DnnLayer {
-  const float* A;          // [M][K], row stride lda
-  const float* W;          // [K][N], contiguous
-  const float* bias;       // [N]
-  const float* sd;         // null, or [n_spkrs][N]
-  const int* spk;          // [n_utt], read with sd
-  const int* frame_utt;    // of row 0 of this chunk
-  float* C;                // [M][N], row stride ldc
-  int* status;             // null, or [n_utt]: the output layer flags non-finite results (bit 2)
-  int64_t lda, ldc;
-  int M, N, K, tiles_n;
-  int a_vec, w_vec;        // 16-byte loads are possible (base and stride aligned)
-};
 
 template <int ACT>
 __global__ __launch_bounds__(256) void dnn_layer_kernel(DnnLayer p) {
@@ -262,7 +233,7 @@ __global__ __launch_bounds__(256) void dnn_cost_kernel(float* __restrict__ out, 
     }
     __syncthreads();
   }
-  if (tid == 0) cost[u] = 0.5 * (kDnnLn2Pi + lnsum / (double)D + msum / ((double)T * (double)D));
+  if (tid == 0) cost[u] = 0.5 * (kLn2Pi + lnsum / (double)D + msum / ((double)T * (double)D));
 }
 
 // What WorldMi355AcousticModelForward refuses, on the host alone: no device call is made for a refused argument set.
@@ -288,19 +259,7 @@ int check_dnn(int n_utt, const WorldMi355AcousticModel* m, const float* x, int64
   return WM_OK;
 }
 
-struct DnnWs : StageWs {
-  float* h[2] = {nullptr, nullptr};
-  int* spk = nullptr;
-  int* status = nullptr;
-  std::vector<int> h_spk;           // the pageable source of the upload: it outlives the call, and the next call rewrites
-                                    // it without a wait -- a copy from pageable memory returns once the source has
-                                    // been read or staged (as mspf.hip's h_tab and synthesis.hip's order rely on)
-  int64_t cap = 0, cap_utt = 0;     // floats per buffer; utterances
-  int n_buf = 0;
-  bool train = false;               // a DnnTrainWs (dnn_train.hip): this struct with the training pass's buffers behind it
-};
-
-static void dnn_launch_layer(int act, const DnnLayer& L, hipStream_t st) {
+void dnn_launch_layer(int act, const DnnLayer& L, hipStream_t st) {
   const int64_t blocks = (int64_t)((L.M + kDnnBM - 1) / kDnnBM) * L.tiles_n;
   const dim3 g((unsigned)blocks), t(256);
   switch (act) {
@@ -309,6 +268,12 @@ static void dnn_launch_layer(int act, const DnnLayer& L, hipStream_t st) {
     case 2: hipLaunchKernelGGL((dnn_layer_kernel<2>), g, t, 0, st, L); break;
     default: hipLaunchKernelGGL((dnn_layer_kernel<3>), g, t, 0, st, L); break;
   }
+}
+
+void dnn_launch_check(hipStream_t st, const float* x, int64_t ld, int width, int64_t rows, const int* frame_utt, int* status,
+                      int bit) {
+  hipLaunchKernelGGL(dnn_check_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, ld, width, rows, frame_utt,
+                     status, bit);
 }
 
 int launch_dnn(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const float* x, int64_t ld_x, const int* spkr,
@@ -351,12 +316,8 @@ int launch_dnn(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const
   if (const int rc = wm_check(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)b.n_utt, st))) return rc;
   {
     TimedScope ts_(b.ctx, st, "dnn_layer_kernel");
-    const unsigned check_blocks = (unsigned)((b.total_f + 3) / 4);
-    hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, x, ld_x, m.n_inputs, b.total_f,
-                       (const int*)b.d_frame_utt, d_status, 1);
-    if (cost != nullptr)
-      hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, obs, ld_obs, m.n_outputs, b.total_f,
-                         (const int*)b.d_frame_utt, d_status, 1);
+    dnn_launch_check(st, x, ld_x, m.n_inputs, b.total_f, b.d_frame_utt, d_status, 1);
+    if (cost != nullptr) dnn_launch_check(st, obs, ld_obs, m.n_outputs, b.total_f, b.d_frame_utt, d_status, 1);
     for (int64_t r0 = 0; r0 < b.total_f; r0 += chunk) {
       const int64_t rows = b.total_f - r0 < chunk ? b.total_f - r0 : chunk;
       const float* A = x + r0 * ld_x;

@@ -1,6 +1,6 @@
 // dnn_train.hip -- the training pass of the recipe's acoustic model (data/scripts/DNNTraining.py with
-// DNNDefine.inference at keep_prob < 1, DNNDefine.cost and their gradients), for a whole batch of utterances.  Included
-// at the end of codec.hip after dnn.hip, whose tile conventions, activation codes, input check and workspace it shares.
+// DNNDefine.inference at keep_prob < 1, DNNDefine.cost and their gradients), for a whole batch of utterances.  It shares
+// dnn.hip's tile conventions, activation codes, input check and workspace through dnn.hpp.
 //
 // Forward with dropout (TF 1.x tf.nn.dropout, div(x, keep_prob) * mask), per frame t of utterance u with speaker s(u):
 //   a_i = act_h((h_{i-1} W_i + b_i) + sd_i[s(u)]),   h_i = m ? fl(a_i / p) : 0,   out = act_o(h_{L-1} W_o + b_o),
@@ -22,7 +22,15 @@
 // dealt to four waves, a lane per column); an utterance cut by a chunk boundary carries its four wave sums and its open
 // group's sum to the next chunk, so the order depends on the utterance's length alone.  dnn_fold_kernel adds the
 // finished utterances in order into double accumulators and rounds once.  No atomics on any value.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
 #include <algorithm>
+
+#include "batch.hpp"
+#include "common.hpp"
+#include "dnn.hpp"
 
 namespace wm {
 
@@ -474,7 +482,7 @@ __global__ __launch_bounds__(256) void dnn_cost_grad_kernel(float* __restrict__ 
     }
     __syncthreads();
   }
-  if (cost != nullptr && tid == 0) cost[u] = 0.5 * (kDnnLn2Pi + lnsum / (double)D + msum / ((double)T * (double)D));
+  if (cost != nullptr && tid == 0) cost[u] = 0.5 * (kLn2Pi + lnsum / (double)D + msum / ((double)T * (double)D));
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -699,12 +707,8 @@ int launch_dnn_train_forward(Batch& b, hipStream_t st, const WorldMi355AcousticM
   const DnnMask mask = dnn_mask_of(drop);
   {
     TimedScope ts_(b.ctx, st, "dnn_layer_kernel");
-    const unsigned check_blocks = (unsigned)((b.total_f + 3) / 4);
-    hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, x, ld_x, m.n_inputs, b.total_f,
-                       (const int*)b.d_frame_utt, d_status, 1);
-    if (want)
-      hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, obs, ld_obs, m.n_outputs, b.total_f,
-                         (const int*)b.d_frame_utt, d_status, 1);
+    dnn_launch_check(st, x, ld_x, m.n_inputs, b.total_f, b.d_frame_utt, d_status, 1);
+    if (want) dnn_launch_check(st, obs, ld_obs, m.n_outputs, b.total_f, b.d_frame_utt, d_status, 1);
     for (int64_t r0 = 0; r0 < b.total_f; r0 += chunk) {
       const int64_t rows = b.total_f - r0 < chunk ? b.total_f - r0 : chunk;
       dnn_train_chunk(b, st, m, mask, W, false, x, ld_x, r0, rows, out + r0 * ld_out, ld_out, d_status);
@@ -750,11 +754,8 @@ int launch_dnn_backward(Batch& b, hipStream_t st, const WorldMi355AcousticModel&
   const size_t acc_layer = (size_t)(1 + W->n_spk) * (size_t)W->max_w;
   if (const int rc = wm_check(hipMemsetAsync(W->acc, 0, sizeof(double) * acc_layer * (size_t)(L + 1), st))) return rc;
   TimedScope ts_(b.ctx, st, "dnn_backward_kernel");
-  const unsigned check_blocks = (unsigned)((b.total_f + 3) / 4);
-  hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, x, ld_x, m.n_inputs, b.total_f,
-                     (const int*)b.d_frame_utt, d_status, 1);
-  hipLaunchKernelGGL(dnn_check_kernel, dim3(check_blocks), dim3(256), 0, st, G, ld_g, m.n_outputs, b.total_f,
-                     (const int*)b.d_frame_utt, d_status, 1);
+  dnn_launch_check(st, x, ld_x, m.n_inputs, b.total_f, b.d_frame_utt, d_status, 1);
+  dnn_launch_check(st, G, ld_g, m.n_outputs, b.total_f, b.d_frame_utt, d_status, 1);
   // an utterance's status is settled before any of its rows reaches a gradient: with more than one chunk a forward pass
   // of every chunk comes first (a non-finite output in a later chunk flags rows of an earlier one)
   if (b.total_f > chunk)

@@ -11,7 +11,7 @@
 // utterance; there are no atomics (the status word is put together in LDS by the block's waves).
 //
 // ffo_compose_kernel is cmp_compose_kernel with a voicing column in front of the streams that have one: the values
-// come from the same device function, cmp_window_value (codec.hip).
+// come from the same device function, cmp_window_value (streamwin.hpp).
 //
 // column_moments_kernel: block (utterance, 64 columns), four waves, a lane per column -- the arrangement and the
 // summation order of mspf_mean_kernel (mspf.hip): wave q sums the 32-frame blocks q, q + 4, ... (each block in frame
@@ -23,6 +23,7 @@
 
 #include "batch.hpp"
 #include "common.hpp"
+#include "streamwin.hpp"
 
 namespace wm {
 
@@ -102,9 +103,9 @@ __global__ __launch_bounds__(64 * kGapMaxWaves) void interpolate_gaps_kernel(
 
 struct FfoMeta {
   CmpMeta c;                                        // c.col0 and c.total_cols are the `cmp` row's and not used here
-  int row0[kCmpMaxStreams];                         // the stream's first column in the `ffo` row, its voicing column if any
+  int row0[kWinMaxStreams];                         // the stream's first column in the `ffo` row, its voicing column if any
   int width;
-  const float* msd[kCmpMaxStreams];
+  const float* msd[kWinMaxStreams];
 };
 
 __global__ __launch_bounds__(256) void ffo_compose_kernel(FfoMeta m, const int* __restrict__ frame_utt,
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void ffo_compose_kernel(FfoMeta m, const int* 
   const int col = (int)(idx - frame * m.width);
   int s = 0;
 #pragma unroll
-  for (int q = 1; q < kCmpMaxStreams; ++q)
+  for (int q = 1; q < kWinMaxStreams; ++q)
     if (q < m.c.n_streams && col >= m.row0[q]) s = q;
   int c = col - m.row0[s];
   if (m.msd[s] != nullptr) {
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void ffo_compose_kernel(FfoMeta m, const int* 
     }
     --c;
   }
-  const int dim = m.c.dim[s];
+  const int dim = m.c.win.dim[s];
   const int wi = c / dim, j = c - wi * dim;
   const int u = frame_utt[frame];
   out[idx] = cmp_window_value(m.c, s, wi, j, frame, f_off[u], f_off[u + 1] - 1);
@@ -200,17 +201,7 @@ int check_interpolate_gaps(const float* d_x, int dim, double ignore_value, const
 }
 int check_compose_ffo(int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
                       const double* const* const* windows, const int* const* window_sizes, const float* d_out) {
-  if (!d_data || !dims || !n_windows || !windows || !window_sizes || !d_out) return WM_ERR_BAD_ARG;
-  if (n_streams < 1 || n_streams > kCmpMaxStreams) return WM_ERR_BAD_ARG;
-  for (int s = 0; s < n_streams; ++s) {
-    if (!d_data[s] || !windows[s] || !window_sizes[s]) return WM_ERR_BAD_ARG;
-    if (dims[s] < 1 || n_windows[s] < 1 || n_windows[s] > kCmpMaxWin) return WM_ERR_BAD_ARG;
-    for (int i = 0; i < n_windows[s]; ++i) {
-      const int size = window_sizes[s][i];
-      if (!windows[s][i] || size < 1 || size > kCmpMaxTaps || size % 2 != 1) return WM_ERR_BAD_ARG;
-    }
-  }
-  return WM_OK;
+  return check_compose_cmp(n_streams, d_data, dims, n_windows, windows, window_sizes, d_out);   // msd may be null
 }
 int check_column_moments(const float* d_x, int64_t ld, int width, const double* ignore_value, const int64_t* d_count,
                          const double* d_mean, const double* d_m2) {
@@ -240,7 +231,7 @@ int launch_compose_ffo(Batch& b, hipStream_t st, int n_streams, const float* con
   if (const int rc = check_compose_ffo(n_streams, d_data, dims, n_windows, windows, window_sizes, d_out)) return rc;
   FfoMeta m;
   memset(&m, 0, sizeof(m));
-  if (const int rc = cmp_fill_meta(m.c, n_streams, d_data, dims, n_windows, windows, window_sizes)) return rc;
+  cmp_fill_meta(m.c, n_streams, d_data, dims, n_windows, windows, window_sizes);
   int col = 0;
   for (int s = 0; s < n_streams; ++s) {
     m.row0[s] = col;

@@ -7,11 +7,10 @@
 //       rule; edge 1: the column is clamped, window.pl's rule and cmp_compose_kernel's),
 //   P   diag(1 / variance),    out = c with (W' P W) c = W' P mu.
 // R = W' P W is symmetric, banded (half-bandwidth 2 max h_i) and positive definite with a static window.  The kernel
-// is a banded LDL' in double, right-looking, one column per lane and sequential in t:
-//   forward   row t of R and of r = W' P mu is built from the taps that reach frame t (float32 loads, double sums); the
-//             updates earlier pivots owe it wait in a register triangle D[a][j] (row t + a, offset j), which every pivot
-//             shifts by one row IN the multiply-add that updates it, so the triangle is indexed at compile time and
-//             never moves.  z / d and the B multipliers go to the batch's workspace, [frame][k][column].
+// is the banded LDL' of banded.hpp in double, right-looking, one column per lane and sequential in t:
+//   forward   row t of R and of r = W' P mu is built from the taps that reach frame t (float32 loads, double sums) and
+//             takes in the updates earlier pivots owe it (banded.hpp's register triangle).  z / d and the B multipliers
+//             go to the batch's workspace, [frame][k][column].
 //   backward  c[t] = z[t] / d[t] - sum_j l[t][j] c[t + j], float32 out, voicing mask.
 // B is a template parameter (0, 2, 4, 14) and the launcher takes the smallest that holds a stream's band.
 //
@@ -21,30 +20,26 @@
 #include <math.h>
 #include <string.h>
 
+#include "banded.hpp"
 #include "batch.hpp"
 #include "common.hpp"
 
 namespace wm {
 
-constexpr int kMlpgMaxStreams = 4, kMlpgMaxWin = 4, kMlpgMaxTaps = 15;
 struct MlpgMeta {
-  int n_streams;                                  // of this launch: the streams that share one B
+  BandTable<kWinMaxTaps> t;
   int edge, var_per_frame, input_type;
   float unvoiced;
-  int dim[kMlpgMaxStreams], nwin[kMlpgMaxStreams], hmax[kMlpgMaxStreams];
-  int chunks[kMlpgMaxStreams], blk0[kMlpgMaxStreams];          // 64-lane chunks per utterance; first block of the stream
-  int wsize[kMlpgMaxStreams][kMlpgMaxWin];
-  double w[kMlpgMaxStreams][kMlpgMaxWin][kMlpgMaxTaps];
-  const float* mean[kMlpgMaxStreams];
-  const float* var[kMlpgMaxStreams];
-  const float* msd[kMlpgMaxStreams];
-  float* out[kMlpgMaxStreams];
-  int64_t ws_off[kMlpgMaxStreams];                // in doubles
+  const float* mean[kWinMaxStreams];
+  const float* var[kWinMaxStreams];
+  const float* msd[kWinMaxStreams];
+  float* out[kWinMaxStreams];
   int64_t ld_mean, ld_var;
 };
+static_assert(sizeof(MlpgMeta) == 2264, "the kernel's arguments are the size they were before the tables were shared");
 
-// A stream's taps as the block keeps them in LDS: window i at wz[i][0 .. size), zeros up to kMlpgRow.  An index
-// tp - tau + h_i with tau in [t - h_i, t + h_i] and tp in [t, t + B] lies in [0, 2 h_i + B] <= 28: no range check.
+// The row length of the taps in LDS (band_stage_taps): an index tp - tau + h_i with tau in [t - h_i, t + h_i] and tp in
+// [t, t + B] lies in [0, 2 h_i + B] <= 28.
 constexpr int kMlpgRow = 32;
 
 // The coefficient of row (tau, i) of W at column tp < T, tau - h_i <= tp; with edge 0, tp <= tau + h_i + 14.
@@ -63,31 +58,23 @@ template <int B>
 __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __restrict__ f_off,
                                                   double* __restrict__ ws, int* __restrict__ status) {
   constexpr int BB = B > 0 ? B : 1;
-  int s = 0;
-#pragma unroll
-  for (int q = 1; q < kMlpgMaxStreams; ++q)
-    if (q < m.n_streams && (int)blockIdx.x >= m.blk0[q]) s = q;
-  const int rel = (int)blockIdx.x - m.blk0[s];
-  const int u = rel / m.chunks[s];
-  const int col = (rel - u * m.chunks[s]) * 64 + (int)threadIdx.x;
+  const BandBlock blk = band_decode(m.t);
+  const int s = blk.s, u = blk.u, col = blk.col;
   const int64_t fb = f_off[u];
   const int T = (int)(f_off[u + 1] - fb);
-  const int dim = m.dim[s];
-  __shared__ double wz[kMlpgMaxWin][kMlpgRow];
-  for (int e = (int)threadIdx.x; e < kMlpgMaxWin * kMlpgRow; e += 64) {
-    const int i = e / kMlpgRow, k = e - i * kMlpgRow;
-    wz[i][k] = i < m.nwin[s] && k < m.wsize[s][i] ? m.w[s][i][k < kMlpgMaxTaps ? k : 0] : 0.0;
-  }
+  const int dim = m.t.win.dim[s];
+  __shared__ double wz[kWinMaxWin][kMlpgRow];
+  band_stage_taps(m.t, s, wz);
   __syncthreads();
   if (T <= 0 || col >= dim) return;
-  const int nwin = m.nwin[s], hmax = m.hmax[s], edge = m.edge;
+  const int nwin = m.t.win.nwin[s], hmax = m.t.hmax[s], edge = m.edge;
   const float* __restrict__ mean = m.mean[s] + col;
   const float* __restrict__ var = m.var[s] + col;
   const float* __restrict__ msd = m.msd[s];
   float* __restrict__ out = m.out[s] + col;
   const int64_t ldm = m.ld_mean, ldv = m.var_per_frame ? m.ld_var : 0;   // one variance row: every frame reads row 0
   const int64_t vb = m.var_per_frame ? fb : 0;
-  double* __restrict__ wc = ws + m.ws_off[s] + col;
+  double* __restrict__ wc = ws + m.t.ws_off[s] + col;
   const float inf = __builtin_inff();
   bool bad = false, sing = false;
   const bool is_prec = m.input_type != 0;
@@ -105,20 +92,15 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
   };
 
   // with one variance row, the rows of R away from the ends are all the same: fi[j] = sum_i p_i sum_k w_i[k] w_i[k + j]
-  double pw[kMlpgMaxWin], fi[B + 1];
+  double pw[kWinMaxWin], fi[B + 1];
 #pragma unroll
   for (int j = 0; j <= B; ++j) fi[j] = 0.0;
 #pragma unroll
-  for (int i = 0; i < kMlpgMaxWin; ++i) {
+  for (int i = 0; i < kWinMaxWin; ++i) {
     pw[i] = 0.0;
     if (!m.var_per_frame && i < nwin) {
       pw[i] = precision(var[i * dim]);
-      const int size = m.wsize[s][i];
-      for (int k = 0; k < size; ++k) {
-        const double pk = pw[i] * wz[i][k];
-#pragma unroll
-        for (int j = 0; j <= B; ++j) fi[j] = __builtin_fma(pk, wz[i][k + j], fi[j]);
-      }
+      band_fi_add<B>(pw[i], wz[i], m.t.win.wsize[s][i], fi);
     }
   }
 
@@ -138,9 +120,9 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
 #pragma unroll
       for (int j = 0; j <= B; ++j) e[j] = fi[j];
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
-          const int size = m.wsize[s][i], h = (size - 1) >> 1;
+          const int size = m.t.win.wsize[s][i], h = (size - 1) >> 1;
           const float* mp = mean + (fb + t - h) * ldm + i * dim;
           for (int k = size - 1; k >= 0; --k, mp += ldm) {                // row tau = t + h - k
             const float mu = *mp;
@@ -152,9 +134,9 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
 #pragma unroll
       for (int j = 0; j <= B; ++j) e[j] = 0.0;
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
-          const int size = m.wsize[s][i], h = (size - 1) >> 1;
+          const int size = m.t.win.wsize[s][i], h = (size - 1) >> 1;
           const int lo = t - h < 0 ? 0 : t - h, hi = t + h > T - 1 ? T - 1 : t + h;
           for (int tau = lo; tau <= hi; ++tau) {
             const float mu = mean[(fb + tau) * ldm + i * dim];
@@ -176,9 +158,9 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
       if (B > 0 && edge != 0 && j1 >= 1 && j1 <= B) {                     // the clamp lands the rows' tails on it
         double ee = 0.0;
 #pragma unroll
-        for (int i = 0; i < kMlpgMaxWin; ++i)
+        for (int i = 0; i < kWinMaxWin; ++i)
           if (i < nwin) {
-            const int size = m.wsize[s][i], h = (size - 1) >> 1;
+            const int size = m.t.win.wsize[s][i], h = (size - 1) >> 1;
             const int lo = t - h < 0 ? 0 : t - h, hi = t + h > T - 1 ? T - 1 : t + h;
             for (int tau = lo; tau <= hi; ++tau) {
               const double p = precision(var[(vb + tau) * ldv + i * dim]);
@@ -203,16 +185,7 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
     } else {
       double* wr = wc + (fb + t) * (int64_t)((B + 1) * dim);
       wr[0] = zi;
-#pragma unroll
-      for (int a = 1; a <= B; ++a) {
-        const double l = e[a] * inv;
-        wr[(int64_t)a * dim] = l;
-        // row t + a becomes row (t + 1) + (a - 1): the shift is the destination of the update
-#pragma unroll
-        for (int j = 0; j + a <= B; ++j)
-          D[a - 1][j] = __builtin_fma(-l, e[a + j], (a < B && j + a < B) ? D[a < B ? a : 0][j] : 0.0);
-        q[a - 1] = __builtin_fma(-l, z, a < B ? q[a < B ? a : 0] : 0.0);
-      }
+      band_pivot<B>(e, z, inv, D, q, wr, dim);
     }
   }
 
@@ -241,25 +214,18 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
   }
 }
 
-// the instantiation that holds a stream's band (half-bandwidth 2 max h_i)
-static int mlpg_band(int hmax) { return hmax == 0 ? 0 : hmax == 1 ? 2 : hmax == 2 ? 4 : 14; }
-
 // What WorldMi355ParameterGeneration refuses, on the host alone: no device call is made for a refused argument set.
 int check_mlpg(int n_streams, const float* const* mean, int64_t ld_mean, const float* const* var, int64_t ld_var,
                const int* dims, const int* n_windows, const double* const* const* windows,
                const int* const* window_sizes, const WorldMi355MlpgOption* opt, float* const* out) {
-  if (!mean || !var || !dims || !n_windows || !windows || !window_sizes || !opt || !out) return WM_ERR_BAD_ARG;
-  if (n_streams < 1 || n_streams > kMlpgMaxStreams) return WM_ERR_BAD_ARG;
+  if (!mean || !var || !opt || !out) return WM_ERR_BAD_ARG;
+  if (const int rc = check_windows(n_streams, dims, n_windows, windows, window_sizes, kWinMaxStreams, kWinMaxWin, kWinMaxTaps))
+    return rc;
   if (opt->edge < 0 || opt->edge > 1 || opt->input_type < 0 || opt->input_type > 1) return WM_ERR_BAD_ARG;
   for (int s = 0; s < n_streams; ++s) {
-    if (!mean[s] || !var[s] || !out[s] || !windows[s] || !window_sizes[s]) return WM_ERR_BAD_ARG;
-    if (dims[s] < 1 || n_windows[s] < 1 || n_windows[s] > kMlpgMaxWin) return WM_ERR_BAD_ARG;
+    if (!mean[s] || !var[s] || !out[s]) return WM_ERR_BAD_ARG;
     const int64_t row = (int64_t)dims[s] * n_windows[s];
     if (ld_mean < row || (opt->var_per_frame && ld_var < row)) return WM_ERR_BAD_ARG;
-    for (int i = 0; i < n_windows[s]; ++i) {
-      const int size = window_sizes[s][i];
-      if (!windows[s][i] || size < 1 || size > kMlpgMaxTaps || size % 2 != 1) return WM_ERR_BAD_ARG;
-    }
   }
   return WM_OK;
 }
@@ -277,16 +243,11 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
     return rc;
   if (b.total_f <= 0 || b.n_utt <= 0) return WM_OK;
   // the factor: (B + 1) doubles per frame and column of the streams with a band
-  int band[kMlpgMaxStreams];
-  int64_t ws_off[kMlpgMaxStreams], need = 0;
-  for (int s = 0; s < n_streams; ++s) {
-    int hmax = 0;
-    for (int i = 0; i < n_windows[s]; ++i) hmax = hmax > (window_sizes[s][i] - 1) / 2 ? hmax : (window_sizes[s][i] - 1) / 2;
-    band[s] = mlpg_band(hmax);
-    ws_off[s] = need;
-    if (band[s] > 0) need += b.total_f * (int64_t)(band[s] + 1) * dims[s];
-    if (((int64_t)dims[s] + 63) / 64 * b.n_utt > (int64_t)1 << 28) return WM_ERR_BAD_ARG;
-  }
+  BandPlan plan;
+  if (const int rc = band_plan(plan, n_streams, dims, n_windows, window_sizes, b.total_f, b.n_utt,
+                               [](int B) { return B > 0 ? B + 1 : 0; }))
+    return rc;
+  const int64_t need = plan.need;
   MlpgWs* W = static_cast<MlpgWs*>(b.mlpg.get());
   if (need > 0 && (W == nullptr || W->cap < need)) {
     std::unique_ptr<MlpgWs> N(new MlpgWs());
@@ -300,7 +261,6 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
   if (d_status != nullptr)
     if (const int rc = wm_check(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)b.n_utt, st))) return rc;
   TimedScope ts_(b.ctx, st, "mlpg_kernel");
-  static const int kBands[4] = {0, 2, 4, 14};
   for (int g = 0; g < 4; ++g) {
     MlpgMeta m;
     memset(&m, 0, sizeof(m));
@@ -310,28 +270,15 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
     m.unvoiced = (float)opt.unvoiced_value;
     m.ld_mean = ld_mean;
     m.ld_var = ld_var;
-    int blocks = 0;
-    for (int s = 0; s < n_streams; ++s) {
-      if (band[s] != kBands[g]) continue;
-      const int k = m.n_streams++;
-      m.dim[k] = dims[s];
-      m.nwin[k] = n_windows[s];
-      m.chunks[k] = (dims[s] + 63) / 64;
-      m.blk0[k] = blocks;
-      blocks += m.chunks[k] * b.n_utt;
-      for (int i = 0; i < n_windows[s]; ++i) {
-        const int size = window_sizes[s][i];
-        m.wsize[k][i] = size;
-        m.hmax[k] = m.hmax[k] > (size - 1) / 2 ? m.hmax[k] : (size - 1) / 2;
-        for (int t = 0; t < size; ++t) m.w[k][i][t] = windows[s][i][t];
-      }
-      m.mean[k] = mean[s];
-      m.var[k] = var[s];
-      m.msd[k] = msd != nullptr ? msd[s] : nullptr;
-      m.out[k] = out[s];
-      m.ws_off[k] = ws_off[s];
+    int src[kWinMaxStreams];
+    const int blocks = band_group(m.t, src, plan, kBands[g], n_streams, dims, n_windows, windows, window_sizes, b.n_utt);
+    if (m.t.n_streams == 0) continue;
+    for (int k = 0; k < m.t.n_streams; ++k) {
+      m.mean[k] = mean[src[k]];
+      m.var[k] = var[src[k]];
+      m.msd[k] = msd != nullptr ? msd[src[k]] : nullptr;
+      m.out[k] = out[src[k]];
     }
-    if (m.n_streams == 0) continue;
     double* d_ws = W != nullptr ? W->d : nullptr;
     switch (kBands[g]) {
       case 0: hipLaunchKernelGGL((mlpg_kernel<0>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status); break;

@@ -1,6 +1,5 @@
 // optim.hip -- the parameter update of DNNTraining.py's training step (DNNDefine.get_optimizer: tf.train.* of TF 1.x at
-// their default hyper-parameters), for every tensor of a model in one launch.  Included at the end of codec.hip after
-// dnn_train.hip.
+// their default hyper-parameters), for every tensor of a model in one launch.
 //
 // With g the gradient, p the parameter and r the tensor's rate, everything float32, every operation rounded on its own
 // in the order written (no contraction: a fused a * b + c would be another rule, bit for bit):
@@ -21,6 +20,12 @@
 // tensors' first blocks -- the same for all its lanes, in scalar registers.  Where param, grad and the slots of a tensor
 // are all 16-byte aligned the elements move as float4 (a tail shorter than 4 one by one), otherwise one by one.  A
 // non-finite gradient element stores 1 into its tensor's status; the update is applied as written all the same.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "batch.hpp"
+#include "common.hpp"
 
 namespace wm {
 

@@ -7,7 +7,7 @@
 //   A = sum_i p_i W_i' W_i,  r = sum_i p_i W_i' mu_i,  c = A^-1 r,  e = o - c,
 //   logdet = ln det A,  mahal = e' A e = sum_i p_i |W_i e|^2,  pv = mean_t (c_t - mean c)^2,  ov the same of o.
 // The reference forms A^-1 densely (O(T^3) per column); A is banded with half-bandwidth B = 2 max h_i and the kernel
-// keeps mlpg_kernel's banded LDL' in double, one column per lane, one wave per (utterance, stream, 64 dimensions):
+// keeps the banded LDL' of banded.hpp (mlpg_kernel's) in double, one column per lane, one wave per (utterance, stream, 64 dimensions):
 //   sweep 1, forward   factor A, z = L^-1 (r - A o), sum ln d_t, the running mean and M2 of o (Welford), the input
 //                      checks: the system is solved for x = c - o = -e (see there);
 //   sweep 2, backward  x, c = o + x with its running mean and M2, and the band of A^-1 by the backward recurrence
@@ -23,33 +23,29 @@
 #include <math.h>
 #include <string.h>
 
+#include "banded.hpp"
 #include "batch.hpp"
 #include "common.hpp"
 
 namespace wm {
 
-constexpr int kTrjMaxTaps = 5, kTrjRow = 16, kTrjTerms = 4;       // terms: ln det A, e' A e, (pv - ov)^2 / gv_var, ln gv_var
-constexpr double kLn2Pi = 1.8378770664093454835606594728112;
+constexpr int kTrjRow = 16, kTrjTerms = 4;        // terms: ln det A, e' A e, (pv - ov)^2 / gv_var, ln gv_var
 struct TrjMeta {
-  int n_streams;                                  // of this launch: the streams that share one B
+  BandTable<kTrjMaxTaps> t;
   int D;                                          // all columns of the call
   int width;                                      // of a row of grad_var
   double gv_weight;
-  int dim[kMlpgMaxStreams], nwin[kMlpgMaxStreams], hmax[kMlpgMaxStreams];
-  int chunks[kMlpgMaxStreams], blk0[kMlpgMaxStreams];
-  int col0[kMlpgMaxStreams];                      // the stream's first column among the D
-  int var0[kMlpgMaxStreams];                      // the stream's window 0 in a row of grad_var
-  int wsize[kMlpgMaxStreams][kMlpgMaxWin];
-  double w[kMlpgMaxStreams][kMlpgMaxWin][kTrjMaxTaps];
-  const float* pred[kMlpgMaxStreams];
-  const float* obs[kMlpgMaxStreams];
-  const float* var[kMlpgMaxStreams];
-  const float* gv_var[kMlpgMaxStreams];
-  float* c[kMlpgMaxStreams];                      // or null
-  float* grad[kMlpgMaxStreams];                   // or null
-  int64_t ws_off[kMlpgMaxStreams];                // in doubles
+  int col0[kWinMaxStreams];                      // the stream's first column among the D
+  int var0[kWinMaxStreams];                      // the stream's window 0 in a row of grad_var
+  const float* pred[kWinMaxStreams];
+  const float* obs[kWinMaxStreams];
+  const float* var[kWinMaxStreams];
+  const float* gv_var[kWinMaxStreams];
+  float* c[kWinMaxStreams];                      // or null
+  float* grad[kWinMaxStreams];                   // or null
   int64_t ld, ld_grad;
 };
+static_assert(sizeof(TrjMeta) == 1080, "the kernel's arguments are the size they were before the tables were shared");
 
 // A sum over the frames of an utterance whose terms share a sign (ln d_t, the trace, the quadratic form): the same
 // value added T times rounds the same way T times, so the lost parts are kept and added at the end (Neumaier).
@@ -68,26 +64,18 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
                                                  double* __restrict__ tab, double* __restrict__ grad_var,
                                                  int* __restrict__ status) {
   constexpr int BB = B > 0 ? B : 1;
-  int s = 0;
-#pragma unroll
-  for (int q = 1; q < kMlpgMaxStreams; ++q)
-    if (q < m.n_streams && (int)blockIdx.x >= m.blk0[q]) s = q;
-  const int rel = (int)blockIdx.x - m.blk0[s];
-  const int u = rel / m.chunks[s];
-  const int col = (rel - u * m.chunks[s]) * 64 + (int)threadIdx.x;
+  const BandBlock blk = band_decode(m.t);
+  const int s = blk.s, u = blk.u, col = blk.col;
   const int64_t fb = f_off[u];
   const int T = (int)(f_off[u + 1] - fb);
-  const int dim = m.dim[s];
-  // taps as mlpg_kernel keeps them (zeros beyond a window's size: an index up to 2 h + B <= 8 needs no range check),
-  // and gz[i][k] = sum_m w_i[m] w_i[m + k], row t of W_i' W_i at column t + k away from the ends
-  __shared__ double wz[kMlpgMaxWin][kTrjRow];
-  __shared__ double gz[kMlpgMaxWin][8];
-  {
-    const int e = (int)threadIdx.x, i = e / kTrjRow, k = e - i * kTrjRow;             // 4 x 16 entries, 64 lanes
-    wz[i][k] = i < m.nwin[s] && k < m.wsize[s][i] ? m.w[s][i][k < kTrjMaxTaps ? k : 0] : 0.0;
-  }
+  const int dim = m.t.win.dim[s];
+  // the taps (an index up to 2 h + B <= 8 needs no range check: 4 x 16 entries, 64 lanes), and
+  // gz[i][k] = sum_m w_i[m] w_i[m + k], row t of W_i' W_i at column t + k away from the ends
+  __shared__ double wz[kWinMaxWin][kTrjRow];
+  __shared__ double gz[kWinMaxWin][8];
+  band_stage_taps(m.t, s, wz);
   __syncthreads();
-  if (threadIdx.x < kMlpgMaxWin * 8) {
+  if (threadIdx.x < kWinMaxWin * 8) {
     const int i = (int)threadIdx.x >> 3, k = (int)threadIdx.x & 7;
     double a = 0.0;
     for (int mm = 0; mm + k < kTrjRow; ++mm) a = __builtin_fma(wz[i][mm], wz[i][mm + k], a);
@@ -95,34 +83,29 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
   }
   __syncthreads();
   if (T <= 0 || col >= dim) return;
-  const int nwin = m.nwin[s], hmax = m.hmax[s];
+  const int nwin = m.t.win.nwin[s], hmax = m.t.hmax[s];
   const float* __restrict__ pred = m.pred[s] + col;
   const float* __restrict__ obs = m.obs[s] + col;
   float* __restrict__ cout = m.c[s] != nullptr ? m.c[s] + col : nullptr;
   float* __restrict__ grad = m.grad[s] != nullptr ? m.grad[s] + col : nullptr;
   const int64_t ld = m.ld, ldg = m.ld_grad;
   const int64_t row = (int64_t)(B + 2) * dim;                            // doubles per frame of this stream's workspace
-  double* __restrict__ wc = ws + m.ws_off[s] + col;
+  double* __restrict__ wc = ws + m.t.ws_off[s] + col;
   const float inf = __builtin_inff();
   bool bad = false, sing = false;
 
   // one variance row: the rows of A away from the ends are all fi[j] = sum_i p_i gz[i][j]
-  double pw[kMlpgMaxWin], fi[B + 1];
+  double pw[kWinMaxWin], fi[B + 1];
 #pragma unroll
   for (int j = 0; j <= B; ++j) fi[j] = 0.0;
 #pragma unroll
-  for (int i = 0; i < kMlpgMaxWin; ++i) {
+  for (int i = 0; i < kWinMaxWin; ++i) {
     pw[i] = 0.0;
     if (i < nwin) {
       const float v = m.var[s][i * dim + col];
       bad |= !(v > 0.0f && v < inf);
       pw[i] = 1.0 / (double)v;
-      const int size = m.wsize[s][i];
-      for (int k = 0; k < size; ++k) {
-        const double pk = pw[i] * wz[i][k];
-#pragma unroll
-        for (int j = 0; j <= B; ++j) fi[j] = __builtin_fma(pk, wz[i][k + j], fi[j]);
-      }
+      band_fi_add<B>(pw[i], wz[i], m.t.win.wsize[s][i], fi);
     }
   }
   const float gvf = m.gv_var[s][col];
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
   TrjSum logdet;
   double mo = 0.0, m2o = 0.0;
   {
-    double D[BB][BB], q[BB], ow[B + 1], dw[kMlpgMaxWin][B + 1];          // ow[j] = o[t + j]; dw[i][k] = (mu_i - W_i o)[t + h_i - k]
+    double D[BB][BB], q[BB], ow[B + 1], dw[kWinMaxWin][B + 1];          // ow[j] = o[t + j]; dw[i][k] = (mu_i - W_i o)[t + h_i - k]
 #pragma unroll
     for (int a = 0; a < BB; ++a) {
       q[a] = 0.0;
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
     for (int j = 0; j <= B; ++j) {
       ow[j] = 0.0;
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i) dw[i][j] = 0.0;
+      for (int i = 0; i < kWinMaxWin; ++i) dw[i][j] = 0.0;
     }
     for (int t = -B; t < T; ++t) {
 #pragma unroll
@@ -162,9 +145,9 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
       }
       if (t < -hmax) continue;
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
-          const int tau = t + ((m.wsize[s][i] - 1) >> 1);
+          const int tau = t + ((m.t.win.wsize[s][i] - 1) >> 1);
           double dn = 0.0;
           if (tau >= 0 && tau <= T - 1) {
             const float mu = pred[(fb + tau) * ld + i * dim];
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
         m2o = __builtin_fma(dl, o - mo, m2o);
       }
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
           double zi = 0.0;
 #pragma unroll
@@ -201,9 +184,9 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
 #pragma unroll
         for (int j = 0; j <= B; ++j) e[j] = 0.0;
 #pragma unroll
-        for (int i = 0; i < kMlpgMaxWin; ++i)
+        for (int i = 0; i < kWinMaxWin; ++i)
           if (i < nwin) {
-            const int size = m.wsize[s][i], h = (size - 1) >> 1;
+            const int size = m.t.win.wsize[s][i], h = (size - 1) >> 1;
             const int lo = t - h < 0 ? 0 : t - h, hi = t + h > T - 1 ? T - 1 : t + h;
             for (int tau = lo; tau <= hi; ++tau) {
               const double* wk = &wz[i][t - tau + h];
@@ -228,15 +211,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
       double* wr = wc + (fb + t) * row;
       wr[0] = z * inv;
       wr[(int64_t)(B + 1) * dim] = inv;
-#pragma unroll
-      for (int a = 1; a <= B; ++a) {
-        const double l = e[a] * inv;
-        wr[(int64_t)a * dim] = l;
-#pragma unroll
-        for (int j = 0; j + a <= B; ++j)
-          D[a - 1][j] = __builtin_fma(-l, e[a + j], (a < B && j + a < B) ? D[a < B ? a : 0][j] : 0.0);
-        q[a - 1] = __builtin_fma(-l, z, a < B ? q[a < B ? a : 0] : 0.0);
-      }
+      band_pivot<B>(e, z, inv, D, q, wr, dim);
     }
   }
 
@@ -249,7 +224,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
   }
 
   // ---- sweep 2: x = c - o, c and its moments, the band of A^-1 and the traces ----
-  TrjSum tr[kMlpgMaxWin];
+  TrjSum tr[kWinMaxWin];
   double mc = 0.0, m2c = 0.0;
   {
     double cw[BB], Zw[BB][B + 1];                                       // x[t + 1 + j]; Zw[r][j] = Z[t + 1 + r][t + 1 + r + j]
@@ -289,9 +264,9 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
 #pragma unroll
       for (int a = 1; a <= B; ++a) Zn[0] = __builtin_fma(-l[a - 1], Zn[a], Zn[0]);
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
-          const int h = (m.wsize[s][i] - 1) >> 1;
+          const int h = (m.t.win.wsize[s][i] - 1) >> 1;
           double acc = 0.0;
           if (t >= h && t + h <= T - 1) {
 #pragma unroll
@@ -338,10 +313,10 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
   // ---- sweep 4: s = A^-1 g and, h_i frames behind it, row tau = t + h_i of every W_i on x, o and s ----
   // W_i e = -W_i x, and the residual mu_i - W_i c = (mu_i - W_i o) + W_i e, again by way of the exact difference.
   const double inv_dt = 1.0 / ((double)m.D * (double)T), gv_2d = m.gv_weight / (2.0 * (double)m.D);
-  TrjSum mah, dpt[kMlpgMaxWin];
-  double dpg[kMlpgMaxWin];
+  TrjSum mah, dpt[kWinMaxWin];
+  double dpg[kWinMaxWin];
 #pragma unroll
-  for (int i = 0; i < kMlpgMaxWin; ++i) dpg[i] = 0.0;
+  for (int i = 0; i < kWinMaxWin; ++i) dpg[i] = 0.0;
   {
     double sw[B + 1], xw[B + 1], ow[B + 1];                              // s, x, o at t + j
 #pragma unroll
@@ -366,9 +341,9 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
       xw[0] = xv;
       ow[0] = ov_;
 #pragma unroll
-      for (int i = 0; i < kMlpgMaxWin; ++i)
+      for (int i = 0; i < kWinMaxWin; ++i)
         if (i < nwin) {
-          const int tau = t + ((m.wsize[s][i] - 1) >> 1);
+          const int tau = t + ((m.t.win.wsize[s][i] - 1) >> 1);
           if (tau >= 0 && tau <= T - 1) {
             double yx = 0.0, yo = 0.0, ys = 0.0;
 #pragma unroll
@@ -396,7 +371,7 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
   if (grad_var != nullptr) {
     double* gp = grad_var + (int64_t)u * m.width + m.var0[s] + col;
 #pragma unroll
-    for (int i = 0; i < kMlpgMaxWin; ++i)
+    for (int i = 0; i < kWinMaxWin; ++i)
       if (i < nwin) gp[i * dim] = -pw[i] * pw[i] * (0.5 * inv_dt * (dpt[i].get() - tr[i].get()) + gv_2d * dpg[i]);
   }
 }
@@ -406,12 +381,12 @@ __global__ __launch_bounds__(64) void trj_kernel(TrjMeta m, const int64_t* __res
 struct TrjReduceMeta {
   int n_streams, D, M, width;
   double msd_weight;
-  int dim[kMlpgMaxStreams], nwin[kMlpgMaxStreams], var0[kMlpgMaxStreams];
-  const float* msd_pred[kMlpgMaxStreams];         // null: the stream has no voicing column
-  const float* msd_obs[kMlpgMaxStreams];
-  const float* msd_var[kMlpgMaxStreams];
-  float* grad[kMlpgMaxStreams];                   // or null
-  float* grad_msd[kMlpgMaxStreams];               // or null
+  int dim[kWinMaxStreams], nwin[kWinMaxStreams], var0[kWinMaxStreams];
+  const float* msd_pred[kWinMaxStreams];         // null: the stream has no voicing column
+  const float* msd_obs[kWinMaxStreams];
+  const float* msd_var[kWinMaxStreams];
+  float* grad[kWinMaxStreams];                   // or null
+  float* grad_msd[kWinMaxStreams];               // or null
   int64_t ld, ld_grad;
 };
 
@@ -422,7 +397,7 @@ __global__ __launch_bounds__(64) void trj_reduce_kernel(TrjReduceMeta m, const i
   const int64_t fb = f_off[u];
   const int T = (int)(f_off[u + 1] - fb);
   __shared__ double red[64];
-  __shared__ double sq[kMlpgMaxStreams], sums[kTrjTerms];
+  __shared__ double sq[kWinMaxStreams], sums[kTrjTerms];
   __shared__ int flag;
   const float inf = __builtin_inff();
   if (lane == 0) flag = T > 0 ? status[u] : 0;
@@ -500,22 +475,17 @@ int check_trj(int n_streams, const float* const* pred, const float* const* obs, 
               const int* const* window_sizes, const float* const* msd_pred, const float* const* msd_obs,
               const float* const* msd_var, const WorldMi355TrajectoryOption* opt, const double* cost,
               float* const* grad_pred, float* const* grad_msd, int64_t ld_grad) {
-  if (!pred || !obs || !var || !gv_var || !dims || !n_windows || !windows || !window_sizes || !opt || !cost)
-    return WM_ERR_BAD_ARG;
-  if (n_streams < 1 || n_streams > kMlpgMaxStreams) return WM_ERR_BAD_ARG;
+  if (!pred || !obs || !var || !gv_var || !opt || !cost) return WM_ERR_BAD_ARG;
+  if (const int rc = check_windows(n_streams, dims, n_windows, windows, window_sizes, kWinMaxStreams, kWinMaxWin, kTrjMaxTaps))
+    return rc;
   if (opt->edge != 0 || !(opt->msd_weight == opt->msd_weight) || !(opt->gv_weight == opt->gv_weight)) return WM_ERR_BAD_ARG;
   if (msd_pred != nullptr && (!msd_obs || !msd_var)) return WM_ERR_BAD_ARG;
   for (int s = 0; s < n_streams; ++s) {
-    if (!pred[s] || !obs[s] || !var[s] || !gv_var[s] || !windows[s] || !window_sizes[s]) return WM_ERR_BAD_ARG;
-    if (dims[s] < 1 || n_windows[s] < 1 || n_windows[s] > kMlpgMaxWin) return WM_ERR_BAD_ARG;
+    if (!pred[s] || !obs[s] || !var[s] || !gv_var[s]) return WM_ERR_BAD_ARG;
     const int64_t row = (int64_t)dims[s] * n_windows[s];
     if (ld < row || (grad_pred != nullptr && !grad_pred[s])) return WM_ERR_BAD_ARG;
     if ((grad_pred != nullptr || grad_msd != nullptr) && ld_grad < row) return WM_ERR_BAD_ARG;
     if (msd_pred != nullptr && msd_pred[s] != nullptr && (!msd_obs[s] || !msd_var[s])) return WM_ERR_BAD_ARG;
-    for (int i = 0; i < n_windows[s]; ++i) {
-      const int size = window_sizes[s][i];
-      if (!windows[s][i] || size < 1 || size > kTrjMaxTaps || size % 2 != 1) return WM_ERR_BAD_ARG;
-    }
   }
   return WM_OK;
 }
@@ -536,15 +506,13 @@ int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred
                                msd_obs, msd_var, &opt, cost, grad_pred, grad_msd, ld_grad))
     return rc;
   if (b.total_f <= 0 || b.n_utt <= 0) return WM_OK;
-  int band[kMlpgMaxStreams], col0[kMlpgMaxStreams], var0[kMlpgMaxStreams], D = 0, M = 0, width = 0;
-  int64_t ws_off[kMlpgMaxStreams], need = 0;
+  BandPlan plan;
+  if (const int rc = band_plan(plan, n_streams, dims, n_windows, window_sizes, b.total_f, b.n_utt,
+                               [](int B) { return B + 2; }))
+    return rc;
+  int col0[kWinMaxStreams], var0[kWinMaxStreams], D = 0, M = 0, width = 0;
+  int64_t need = plan.need;
   for (int s = 0; s < n_streams; ++s) {
-    int hmax = 0;
-    for (int i = 0; i < n_windows[s]; ++i) hmax = hmax > (window_sizes[s][i] - 1) / 2 ? hmax : (window_sizes[s][i] - 1) / 2;
-    band[s] = 2 * hmax;
-    ws_off[s] = need;
-    need += b.total_f * (int64_t)(band[s] + 2) * dims[s];
-    if (((int64_t)dims[s] + 63) / 64 * b.n_utt > (int64_t)1 << 28) return WM_ERR_BAD_ARG;
     const bool has_msd = msd_pred != nullptr && msd_pred[s] != nullptr;
     col0[s] = D;
     var0[s] = width + (has_msd ? 1 : 0);
@@ -572,8 +540,7 @@ int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred
   if (d_status == nullptr) d_status = W->status;
   if (const int rc = wm_check(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)b.n_utt, st))) return rc;
   TimedScope ts_(b.ctx, st, "trj_kernel");
-  static const int kBands[3] = {0, 2, 4};
-  for (int g = 0; g < 3; ++g) {
+  for (int g = 0; g < 3; ++g) {                          // five taps: no stream has the widest band
     TrjMeta m;
     memset(&m, 0, sizeof(m));
     m.D = D;
@@ -581,32 +548,20 @@ int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred
     m.gv_weight = opt.gv_weight;
     m.ld = ld;
     m.ld_grad = ld_grad;
-    int blocks = 0;
-    for (int s = 0; s < n_streams; ++s) {
-      if (band[s] != kBands[g]) continue;
-      const int k = m.n_streams++;
-      m.dim[k] = dims[s];
-      m.nwin[k] = n_windows[s];
-      m.chunks[k] = (dims[s] + 63) / 64;
-      m.blk0[k] = blocks;
-      blocks += m.chunks[k] * b.n_utt;
+    int src[kWinMaxStreams];
+    const int blocks = band_group(m.t, src, plan, kBands[g], n_streams, dims, n_windows, windows, window_sizes, b.n_utt);
+    if (m.t.n_streams == 0) continue;
+    for (int k = 0; k < m.t.n_streams; ++k) {
+      const int s = src[k];
       m.col0[k] = col0[s];
       m.var0[k] = var0[s];
-      for (int i = 0; i < n_windows[s]; ++i) {
-        const int size = window_sizes[s][i];
-        m.wsize[k][i] = size;
-        m.hmax[k] = m.hmax[k] > (size - 1) / 2 ? m.hmax[k] : (size - 1) / 2;
-        for (int t = 0; t < size; ++t) m.w[k][i][t] = windows[s][i][t];
-      }
       m.pred[k] = pred[s];
       m.obs[k] = obs[s];
       m.var[k] = var[s];
       m.gv_var[k] = gv_var[s];
       m.c[k] = c != nullptr ? c[s] : nullptr;
       m.grad[k] = grad_pred != nullptr ? grad_pred[s] : nullptr;
-      m.ws_off[k] = ws_off[s];
     }
-    if (m.n_streams == 0) continue;
     double* tab = W->d + tab_off;
     switch (kBands[g]) {
       case 0: hipLaunchKernelGGL((trj_kernel<0>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, W->d, tab, grad_var, d_status); break;

@@ -25,6 +25,41 @@ ERRORS = {1: "HIP error", 2: "bad argument", 3: "unsupported fft_size", 4: "no H
           5: "unsupported configuration"}
 
 
+def _window_tables(window_lists):
+    """The windows of the stream/window bundle four calls take, from one list of coefficient lists per stream:
+    (n_windows array, window pointer table, size pointer table, what to keep alive until the call returns)."""
+    n = len(window_lists)
+    nwin = (C.c_int * n)(*[len(wins) for wins in window_lists])
+    keep, wptrs, sptrs = [], (C.POINTER(_dp) * n)(), (C.POINTER(C.c_int) * n)()
+    for s, wins in enumerate(window_lists):
+        arrs = [(C.c_double * len(w))(*w) for w in wins]
+        pa = (_dp * len(wins))(*[C.cast(a, _dp) for a in arrs])
+        sz = (C.c_int * len(wins))(*[len(w) for w in wins])
+        keep += [arrs, pa, sz]
+        wptrs[s] = C.cast(pa, C.POINTER(_dp))
+        sptrs[s] = C.cast(sz, _ip)
+    return nwin, wptrs, sptrs, keep
+
+
+def _shared_row_stride(rows, cols, total_frames):
+    """One row stride for the matrices `rows` and the column vectors `cols` (None entries stay None): as given when
+    all share one, else packed side by side.  Returns (row stride, rows, cols, what to keep alive)."""
+    import torch
+    ts = list(rows) + [c for c in cols if c is not None]
+    ld = {int(t.stride(0)) for t in ts}
+    if total_frames > 1 and len(ld) == 1 and all(t.stride(1) == 1 for t in rows):
+        return ld.pop(), rows, cols, ts
+    mat = torch.cat(list(rows) + [c[:, None] for c in cols if c is not None], dim=1)
+    at, r2, c2 = 0, [], []
+    for t in rows:
+        r2.append(mat[:, at:at + t.shape[1]])
+        at += int(t.shape[1])
+    for c in cols:
+        c2.append(None if c is None else mat[:, at])
+        at += 0 if c is None else 1
+    return int(mat.shape[1]), r2, c2, [mat]
+
+
 class WorldParams(C.Structure):
     """include/world_mi355.h: WorldMi355Params."""
     _fields_ = [("fs", C.c_int), ("frame_period", C.c_double), ("f0_floor", C.c_double),
@@ -668,19 +703,11 @@ class WorldBatch:
         Returns float32 [total_frames][sum n_windows * dim] (window.pl + merge of the recipe's cmp stage)."""
         import torch
         n = len(streams)
-        dp = C.POINTER(C.c_double)
         data = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t, _ in streams])
         dims = (C.c_int * n)(*[int(t.shape[1]) for t, _ in streams])
-        nwin = (C.c_int * n)(*[len(w) for _, w in streams])
-        keep, wptrs, sptrs = [], (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
-        for s, (t, wins) in enumerate(streams):
+        for t, _ in streams:
             assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float32" and t.shape[0] == self.total_frames
-            arrs = [(C.c_double * len(w))(*w) for w in wins]
-            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
-            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
-            keep += [arrs, pa, sz]
-            wptrs[s] = C.cast(pa, C.POINTER(dp))
-            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        nwin, wptrs, sptrs, keep = _window_tables([wins for _, wins in streams])
         cols = sum(int(t.shape[1]) * len(w) for t, w in streams)
         out = torch.empty(self.total_frames, cols, dtype=torch.float32, device="cuda")
         _check(load_library().WorldMi355ComposeCmp(self.handle, n, data, dims, nwin, wptrs, sptrs,
@@ -722,25 +749,17 @@ class WorldBatch:
         n = len(streams)
         if n < 1:
             raise ValueError("compose_ffo: no streams")
-        dp = C.POINTER(C.c_double)
-        keep, wptrs, sptrs = [], (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
-        for s, (t, wins, msd) in enumerate(streams):
+        for t, wins, msd in streams:
             self._f32_rows(t, "compose_ffo")
             if len(wins) < 1 or any(len(w) < 1 for w in wins):
                 raise ValueError("compose_ffo: a stream needs at least one window, a window at least one coefficient")
             if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and msd.is_contiguous()
                                         and tuple(msd.shape) == (self.total_frames,)):
                 raise ValueError(f"compose_ffo: msd must be a contiguous float32 cuda tensor [{self.total_frames}]")
-            arrs = [(C.c_double * len(w))(*w) for w in wins]
-            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
-            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
-            keep += [arrs, pa, sz]
-            wptrs[s] = C.cast(pa, C.POINTER(dp))
-            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        nwin, wptrs, sptrs, keep = _window_tables([wins for _, wins, _ in streams])
         data = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t, _, _ in streams])
         msds = (C.c_void_p * n)(*[C.c_void_p(None if m is None else m.data_ptr()) for _, _, m in streams])
         dims = (C.c_int * n)(*[int(t.shape[1]) for t, _, _ in streams])
-        nwin = (C.c_int * n)(*[len(w) for _, w, _ in streams])
         cols = sum(int(t.shape[1]) * len(w) + (0 if m is None else 1) for t, w, m in streams)
         out = torch.empty(self.total_frames, cols, dtype=torch.float32, device="cuda")
         _check(load_library().WorldMi355ComposeFfo(self.handle, n, data, dims, nwin, wptrs, sptrs, msds,
@@ -843,39 +862,15 @@ class WorldBatch:
             if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and tuple(msd.shape) == (tf,)):
                 raise ValueError("parameter_generation: msd must be float32 cuda [total_frames]")
 
-        def common_stride(rows, cols):
-            """(row stride, rows, columns, what to keep alive): as given when all share one stride, else packed"""
-            ts = list(rows) + [c for c in cols if c is not None]
-            ld = {int(t.stride(0)) for t in ts}
-            if tf > 1 and len(ld) == 1 and all(t.stride(1) == 1 for t in rows):
-                return ld.pop(), rows, cols, ts
-            mat = torch.cat(list(rows) + [c[:, None] for c in cols if c is not None], dim=1)
-            at, r2, c2 = 0, [], []
-            for t in rows:
-                r2.append(mat[:, at:at + t.shape[1]])
-                at += int(t.shape[1])
-            for c in cols:
-                c2.append(None if c is None else mat[:, at])
-                at += 0 if c is None else 1
-            return int(mat.shape[1]), r2, c2, [mat]
-
-        ld_mean, means, msds, keep_m = common_stride([t for t, _, _, _ in streams], [m for _, _, _, m in streams])
+        ld_mean, means, msds, keep_m = _shared_row_stride([t for t, _, _, _ in streams], [m for _, _, _, m in streams], tf)
         if var_per_frame:
-            ld_var, vars_, _, keep_v = common_stride([v for _, v, _, _ in streams], [])
+            ld_var, vars_, _, keep_v = _shared_row_stride([v for _, v, _, _ in streams], [], tf)
         else:
             ld_var, vars_, keep_v = 0, [v.contiguous() for _, v, _, _ in streams], []
-        dp = C.POINTER(C.c_double)
         vpn = C.c_void_p * n
-        nwin = (C.c_int * n)(*[len(w) for _, _, w, _ in streams])
         dims = (C.c_int * n)(*[int(t.shape[1]) // len(w) for t, _, w, _ in streams])
-        keep, wptrs, sptrs = [keep_m, keep_v, vars_], (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
-        for s, (_, _, wins, _) in enumerate(streams):
-            arrs = [(C.c_double * len(w))(*w) for w in wins]
-            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
-            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
-            keep += [arrs, pa, sz]
-            wptrs[s] = C.cast(pa, C.POINTER(dp))
-            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        nwin, wptrs, sptrs, keep = _window_tables([wins for _, _, wins, _ in streams])
+        keep += [keep_m, keep_v, vars_]
         outs = [torch.empty(tf, int(dims[s]), dtype=torch.float32, device="cuda") for s in range(n)]
         status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
         o = MlpgOption()
@@ -930,32 +925,12 @@ class WorldBatch:
         # one row stride for pred, obs and the voicing columns: as given when they share one, else packed side by side
         rows = [t for p, o, _, _ in streams for t in (p, o)]
         cols = [t for _, _, _, msd in streams if msd is not None for t in msd]
-        keep = [rows, cols, var, gv_var]
-        if not (tf > 1 and len({int(t.stride(0)) for t in rows + cols}) == 1 and all(t.stride(1) == 1 for t in rows)):
-            mat = torch.cat(rows + [c[:, None] for c in cols], dim=1)
-            keep.append(mat)
-            at, r2, c2 = 0, [], []
-            for t in rows:
-                r2.append(mat[:, at:at + t.shape[1]])
-                at += int(t.shape[1])
-            for _ in cols:
-                c2.append(mat[:, at])
-                at += 1
-            rows, cols, ld = r2, c2, int(mat.shape[1])
-        else:
-            ld = int(rows[0].stride(0))
+        ld, rows, cols, keep_rows = _shared_row_stride(rows, cols, tf)
         cols = iter(cols)
         msds = [(next(cols), next(cols)) if msd is not None else None for _, _, _, msd in streams]
-        dp = C.POINTER(C.c_double)
         vpn = C.c_void_p * n
-        wptrs, sptrs = (C.POINTER(dp) * n)(), (C.POINTER(C.c_int) * n)()
-        for s, (_, _, wins, _) in enumerate(streams):
-            arrs = [(C.c_double * len(w))(*w) for w in wins]
-            pa = (dp * len(wins))(*[C.cast(a, dp) for a in arrs])
-            sz = (C.c_int * len(wins))(*[len(w) for w in wins])
-            keep += [arrs, pa, sz]
-            wptrs[s] = C.cast(pa, C.POINTER(dp))
-            sptrs[s] = C.cast(sz, C.POINTER(C.c_int))
+        nwin, wptrs, sptrs, keep = _window_tables([wins for _, _, wins, _ in streams])
+        keep += [keep_rows, var, gv_var]
         cost = torch.zeros(self.n_utt, 3, dtype=torch.float64, device="cuda")      # a batch of zero frames launches nothing
         status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
         c = [torch.empty(tf, d, dtype=torch.float32, device="cuda") for d in dims] if want_c else None
@@ -974,7 +949,7 @@ class WorldBatch:
         _check(load_library().WorldMi355TrajectoryCost(
             self.handle, n, vpn(*[ptr(t) for t in rows[0::2]]), vpn(*[ptr(t) for t in rows[1::2]]), ld,
             vpn(*[col(var, c0) for _, c0, _ in layout]), vpn(*gv_ptrs), (C.c_int * n)(*dims),
-            (C.c_int * n)(*[len(w) for _, _, w, _ in streams]), wptrs, sptrs,
+            nwin, wptrs, sptrs,
             vpn(*[ptr(m and m[0]) for m in msds]), vpn(*[ptr(m and m[1]) for m in msds]),
             vpn(*[col(var, mc) for mc, _, _ in layout]), C.byref(o), ptr(cost),
             None if c is None else vpn(*[ptr(t) for t in c]),

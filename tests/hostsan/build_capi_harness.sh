@@ -8,7 +8,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
 src="$root/hts-train-world_amd/csrc"
 pids=()
-for f in cheaptrick.hip d4c.hip stonemask.hip dio.hip synthesis.hip harvest.hip codec.hip status.hip vibrato.hip context.cpp capi.cpp fileio.cpp; do
+for f in $(make -s -C "$src" print-units); do
   $HIPCC -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 --cuda-host-only $SAN -Wno-comment -I"$root/include" -I"$src" -x hip -c "$src/$f" -o "$out/${f%.*}.o" 2> "$out/${f%.*}.log" &
   pids+=($!)
 done

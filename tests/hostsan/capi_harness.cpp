@@ -257,6 +257,26 @@ int main(int argc, char** argv) {
       printf("CreateBatch: %s\n", WorldMi355LastError());
       if (!inject) return 6;
     }
+    // the stream/window bundle of ComposeCmp: a valid one is read tap by tap at its exact sizes; a null window and a
+    // window of 16 taps are refused on the host
+    if (b) {
+      const size_t tf = (size_t)WorldMi355BatchTotalFrames(b);
+      std::vector<float> data(tf * 2, 0.5f), out(tf * 4, NAN);
+      const float* streams[1] = {data.data()};
+      const int dims[1] = {2}, nwin[1] = {2}, sizes_ok[2] = {1, 3}, sizes_16[2] = {1, 16};
+      std::vector<double> w0(1, 1.0), w1{-0.5, 0.0, 0.5}, w16(16, 0.0);
+      const double* wins_ok[2] = {w0.data(), w1.data()};
+      const double* wins_null[2] = {w0.data(), nullptr};
+      const double* wins_16[2] = {w0.data(), w16.data()};
+      const double* const* windows[1] = {wins_ok};
+      const int* sizes[1] = {sizes_ok};
+      if (WorldMi355ComposeCmp(b, 1, streams, dims, nwin, windows, sizes, out.data()) != WM_OK) return 7;
+      windows[0] = wins_null;
+      if (WorldMi355ComposeCmp(b, 1, streams, dims, nwin, windows, sizes, out.data()) != WM_ERR_BAD_ARG) return 8;
+      windows[0] = wins_16;
+      sizes[0] = sizes_16;
+      if (WorldMi355ComposeCmp(b, 1, streams, dims, nwin, windows, sizes, out.data()) != WM_ERR_BAD_ARG) return 9;
+    }
     if (b) WorldMi355DestroyBatch(b);
     WorldMi355DestroyContext(ctx);
   }

@@ -174,6 +174,25 @@ def test_cli_parses_the_new_subcommands(pkg, tmp_path, capsys):
             main(argv)
 
 
+def test_compose_cmp_refuses_bad_arguments_without_a_device(pkg):
+    """WorldMi355ComposeCmp checks its arguments on the host, as ComposeFfo does, before it looks at the batch: each of
+    these returns WM_ERR_BAD_ARG (2) and makes no device call."""
+    import ctypes as C
+    lib = pkg.load_library()
+    x, out = np.zeros((3, 2), dtype=np.float32), np.zeros((3, 4), dtype=np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    data, dims = (C.c_void_p * 1)(vp(x)), (C.c_int * 1)(2)
+    nwin, wptrs, sptrs, keep = pkg.world._window_tables([[[1.0], [-0.5, 0.0, 0.5]]])
+    assert list(nwin) == [2] and [sptrs[0][i] for i in range(2)] == [1, 3] and wptrs[0][1][2] == 0.5
+    call = lib.WorldMi355ComposeCmp
+    assert call(None, 1, data, dims, nwin, wptrs, sptrs, vp(out)) == 2          # a null batch, everything else valid
+    assert call(None, 1, data, None, nwin, wptrs, sptrs, vp(out)) == 2          # null dims
+    assert call(None, 0, data, dims, nwin, wptrs, sptrs, vp(out)) == 2          # no streams
+    assert call(None, 5, data, dims, nwin, wptrs, sptrs, vp(out)) == 2          # more streams than the kernels hold
+    assert lib.WorldMi355ComposeFfo(None, 1, data, dims, nwin, wptrs, sptrs, None, vp(out)) == 2
+    del keep
+
+
 def test_file_checks_raise_value_error(pkg, tmp_path):
     streams = [(2, [[1.0]], False), (1, [[1.0]], True)]
     a, b, out = (str(tmp_path / n) for n in ("a.mgc", "a.lf0", "a.ffo"))
