@@ -277,6 +277,14 @@ class Context:
                "CreateContext")
         self.handle = h
 
+    def set_stream(self, stream_ptr: int | None = None):
+        """Move the context to another HIP stream (WorldMi355SetStream): waits on the host for everything queued on the
+        stream it had, then points every later call of the context and of its batches at `stream_ptr` (None or 0: the
+        legacy default stream, as in the constructor).  Work of other streams is not waited for: the caller orders the
+        new stream behind whatever produced its inputs."""
+        _check(load_library().WorldMi355SetStream(self.handle, C.c_void_p(stream_ptr) if stream_ptr else None),
+               "SetStream")
+
     def synchronize(self):
         _check(load_library().WorldMi355Synchronize(self.handle), "Synchronize")
 

@@ -4,6 +4,7 @@
 // exact size (analysis.cpp:172-176) -- a scatter that is one element off lands in a red zone.  Kernels do not run in
 // the stub, so nothing here checks arithmetic; what is checked is that every call returns, outputs are written and
 // finite, the error-handler path unwinds cleanly, and the sanitizers stay silent.
+#include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,6 +27,7 @@ extern "C" long HipStubCreations();
 extern "C" long HipStubDevPtrs();
 extern "C" void HipStubNextPulses(long index);
 extern "C" void HipStubTraceMark(const char* text);
+extern "C" void HipStubTraceStream(const char* label, void* stream);
 
 static int g_handler_calls = 0;
 static void on_error(const char* where, int code, const char* message, void* user) {
@@ -199,8 +201,246 @@ static int batched_sequence() {
   return 0;
 }
 
+// `capi_harness streams`: every entry point that queues device work, at tiny sizes, on a context whose stream is NOT the
+// legacy default stream, for the rules of tests/stream_rules.py (checked in tests/test_sanitizers.py): nothing may be
+// queued on stream 0, and a stream of the library's own is forked from the caller's and joined back into it within
+// the call.  The trace starts with the
+// names of the NULL stream and of the two caller streams ("# stream U s1"); "# caller U" says which one the context is
+// on from there.  The last steps re-point the context (WorldMi355SetStream) and call once more.
+template <class T> static T* dev(std::vector<std::vector<unsigned char>>& pool, size_t n, T fill) {
+  pool.emplace_back((n ? n : 1) * sizeof(T));
+  T* p = (T*)pool.back().data();
+  for (size_t i = 0; i < n; ++i) p[i] = fill;
+  return p;
+}
+static int stream_sequence() {
+  int last_code = 0;
+  WorldMi355SetErrorHandler(on_error, &last_code);
+  hipStream_t U = nullptr, V = nullptr;
+  if (hipStreamCreateWithFlags(&U, hipStreamNonBlocking) != hipSuccess || !U) return 40;
+  if (hipStreamCreateWithFlags(&V, hipStreamNonBlocking) != hipSuccess || !V) return 40;
+  HipStubTraceStream("null", nullptr);
+  HipStubTraceStream("U", U);
+  HipStubTraceStream("V", V);
+  const int fs = 16000, F = 1024, bins = F / 2 + 1;
+  WorldMi355Params p;
+  WorldMi355DefaultParams(fs, 5.0, &p);
+  WorldMi355Context* ctx = nullptr;
+  if (WorldMi355CreateContext(-1, U, &ctx) != 0 || !ctx) return 41;
+  HipStubTraceMark("caller U");
+  std::vector<std::vector<unsigned char>> pool;
+  const int lens[2] = {4800, 8000}, frames[3] = {5, 64, 33};
+  int big_f[16], big_y[16];
+  int64_t big_tf = 0, big_ty = 0;
+  for (int u = 0; u < 16; ++u) {                                          // the split Synthesis, as in `batched`
+    big_y[u] = (1 << 18) + 4000 * ((u * 7) % 16);
+    big_f[u] = (big_y[u] - 1) / 80 + 1;
+    big_tf += big_f[u];
+    big_ty += big_y[u];
+  }
+  WorldMi355Batch *b = nullptr, *bf = nullptr, *bb = nullptr;
+  if (WorldMi355CreateBatch(ctx, &p, 2, lens, nullptr, nullptr, &b) != 0) return 42;
+  if (WorldMi355CreateBatch(ctx, &p, 3, nullptr, frames, nullptr, &bf) != 0) return 43;
+  if (WorldMi355CreateBatch(ctx, &p, 16, nullptr, big_f, big_y, &bb) != 0) return 44;
+  bool ok = true;
+  for (int round = 0; round < 2 && ok; ++round) {                         // the second time with TimedScope's records
+    if (round == 1 && WorldMi355TimingEnable(ctx, 1) != 0) return 47;
+    {  // ---- WORLD and its codec on the analysis batch
+      const size_t tx = (size_t)WorldMi355BatchTotalSamples(b), tf = (size_t)WorldMi355BatchTotalFrames(b);
+      const size_t ty = (size_t)WorldMi355BatchTotalOutputSamples(b);
+      const int nd = 20, na = WorldMi355GetNumberOfAperiodicities(fs), apd = 5;
+      double *x = dev(pool, tx, 0.1), *t = dev(pool, tf, 0.0), *f0 = dev(pool, tf, 120.0), *rf0 = dev(pool, tf, 120.0);
+      double *sp = dev(pool, tf * bins, 1.0), *ap = dev(pool, tf * bins, 0.5), *y = dev(pool, ty, 0.0);
+      double *csp = dev(pool, tf * nd, 0.0), *cap = dev(pool, tf * (size_t)(na > 0 ? na : 1), 0.0);
+      int16_t *pcm_in = dev(pool, tx, (int16_t)100), *pcm_out = dev(pool, ty, (int16_t)0);
+      float *lf0 = dev(pool, tf, 4.8f), *mgc = dev(pool, tf * nd, 0.0f), *bap = dev(pool, tf * apd, 0.0f);
+      int* ust = dev(pool, 2, 0);
+      ok = ok && step("SamplesFromPcm16", 0, [&] { return WorldMi355SamplesFromPcm16(b, pcm_in, x); });
+      ok = ok && step("Dio", 0, [&] { return WorldMi355Dio(b, x, t, f0); });
+      ok = ok && step("Harvest", 0, [&] { return WorldMi355Harvest(b, x, t, f0); });
+      for (size_t i = 0; i < tf; ++i) { t[i] = i * 0.005; f0[i] = (i % 7 == 0) ? 0.0 : 100.0 + (double)(i % 50); }
+      ok = ok && step("StoneMask", 0, [&] { return WorldMi355StoneMask(b, x, t, f0, rf0); });
+      ok = ok && step("CheapTrick", 0, [&] { return WorldMi355CheapTrick(b, x, t, f0, sp); });
+      ok = ok && step("D4C", 0, [&] { return WorldMi355D4C(b, x, t, f0, ap); });
+      ok = ok && step("Analyze (forked)", 0, [&] { return WorldMi355Analyze(b, x, t, f0, sp, ap); });
+      ok = ok && step("AnalyzeSynthesize 1", 1, [&] { return WorldMi355AnalyzeSynthesize(b, x, t, f0, sp, ap, y); });
+      ok = ok && step("AnalyzeSynthesize 2 (overlapped)", 2, [&] { return WorldMi355AnalyzeSynthesize(b, x, t, f0, sp, ap, y); });
+      ok = ok && step("Synthesis in one part", 3, [&] { return WorldMi355Synthesis(b, f0, sp, ap, y); });
+      ok = ok && step("SamplesToPcm16", 0, [&] { return WorldMi355SamplesToPcm16(b, y, pcm_out); });
+      ok = ok && step("UtteranceStatus", 0, [&] { return WorldMi355UtteranceStatus(b, x, f0, sp, ap, ust); });
+      ok = ok && step("CodeSpectralEnvelope", 0, [&] { return WorldMi355CodeSpectralEnvelope(b, sp, nd, csp); });
+      ok = ok && step("DecodeSpectralEnvelope", 0, [&] { return WorldMi355DecodeSpectralEnvelope(b, csp, nd, sp); });
+      ok = ok && step("CodeAperiodicity", 0, [&] { return WorldMi355CodeAperiodicity(b, ap, cap); });
+      ok = ok && step("DecodeAperiodicity", 0, [&] { return WorldMi355DecodeAperiodicity(b, cap, ap); });
+      ok = ok && step("RecipeFeatures", 0, [&] { return WorldMi355RecipeFeatures(b, f0, sp, ap, nd, apd, lf0, mgc, bap); });
+      ok = ok && step("RecipeDecode", 0, [&] { return WorldMi355RecipeDecode(b, lf0, mgc, bap, nd, apd, f0, sp, ap); });
+    }
+    {  // ---- Synthesis in two parts: sp / ap of the large batch are never read by the host layer
+      double *f0b = dev(pool, (size_t)big_tf, 110.0), *yb = dev(pool, (size_t)big_ty, 0.0);
+      ok = ok && step("Synthesis in two parts", 4, [&] { return WorldMi355Synthesis(bb, f0b, f0b, f0b, yb); });
+    }
+    {  // ---- the recipe's stages on the frame batch (5, 64 and 33 frames)
+      const size_t tf = (size_t)WorldMi355BatchTotalFrames(bf);
+      const int nu = 3, dim = 2, nw = 3, row = dim * nw, order = 8, K = 33;
+      std::vector<double> w0{1.0}, w1{-0.5, 0.0, 0.5}, w2{1.0, -2.0, 1.0};
+      const double* wins[3] = {w0.data(), w1.data(), w2.data()};
+      const int sizes3[3] = {1, 3, 3};
+      const double* const* windows[1] = {wins};
+      const int* sizes[1] = {sizes3};
+      const int dims[1] = {dim}, nwin[1] = {nw};
+      float *st32 = dev(pool, tf * dim, 0.5f), *cmp = dev(pool, tf * row, 0.5f), *ffo = dev(pool, tf * (row + 1), 0.5f);
+      float *msd = dev(pool, tf, 1.0f), *gap = dev(pool, tf * dim, 0.5f), *voiced = dev(pool, tf, 0.0f);
+      int *ust = dev(pool, nu, 0), *fst = dev(pool, tf, 0);
+      const float* streams[1] = {st32};
+      const float* msds[1] = {msd};
+      ok = ok && step("ComposeCmp", 0, [&] { return WorldMi355ComposeCmp(bf, 1, streams, dims, nwin, windows, sizes, cmp); });
+      ok = ok && step("ComposeFfo", 0, [&] { return WorldMi355ComposeFfo(bf, 1, streams, dims, nwin, windows, sizes, msds, ffo); });
+      ok = ok && step("InterpolateGaps", 0, [&] { return WorldMi355InterpolateGaps(bf, st32, dim, -1e10, gap, voiced, ust); });
+      int64_t* cnt = dev(pool, (size_t)nu * dim, (int64_t)0);
+      double *mom1 = dev(pool, (size_t)nu * dim, 0.0), *mom2 = dev(pool, (size_t)nu * dim, 0.0);
+      const double ignore = -1e10;
+      ok = ok && step("ColumnMoments", 0, [&] { return WorldMi355ColumnMoments(bf, st32, dim, dim, &ignore, cnt, mom1, mom2); });
+      double *x64 = dev(pool, tf * dim, 0.25), *o64 = dev(pool, tf * dim, 0.0), *um = dev(pool, (size_t)nu * dim, 0.0);
+      ok = ok && step("ColumnMeans", 0, [&] { return WorldMi355ColumnMeans(bf, x64, dim, um); });
+      double *spec = dev(pool, tf * bins, 1.0), *mc = dev(pool, tf * (order + 1), 0.1), *mc2 = dev(pool, tf * (order + 1), 0.0);
+      double* gain = dev(pool, tf, 0.0);
+      WorldMi355McepOption mo;
+      WorldMi355DefaultMcepOption(&mo);
+      mo.order = order;
+      ok = ok && step("MelCepstrum", 0, [&] { return WorldMi355MelCepstrum(bf, spec, &mo, mc, fst); });
+      WorldMi355Mgc2spOption go;
+      WorldMi355DefaultMgc2spOption(&go);
+      go.order = order;
+      ok = ok && step("MelCepstrumToSpectrum", 0, [&] { return WorldMi355MelCepstrumToSpectrum(bf, mc, &go, spec, nullptr, fst); });
+      WorldMi355McpfOption po;
+      WorldMi355DefaultMcpfOption(&po);
+      po.order = order;
+      ok = ok && step("MelCepstrumPostfilter", 0, [&] { return WorldMi355MelCepstrumPostfilter(bf, mc, &po, mc2, gain, fst); });
+      WorldMi355MspfOption so;
+      WorldMi355DefaultMspfOption(&so);
+      std::vector<double> tab_mean((size_t)dim * K, 0.0), tab_std((size_t)dim * K, 1.0);
+      double *s1 = dev(pool, (size_t)dim * K, 0.0), *s2 = dev(pool, (size_t)dim * K, 0.0);
+      int64_t n_frames = 0;
+      ok = ok && step("ModulationSpectrumStats", 0,
+                      [&] { return WorldMi355ModulationSpectrumStats(bf, x64, dim, &so, nullptr, s1, s2, &n_frames); });
+      ok = ok && step("ModulationSpectrumPostfilter", 0, [&] {
+             return WorldMi355ModulationSpectrumPostfilter(bf, x64, dim, &so, tab_mean.data(), tab_std.data(), tab_mean.data(),
+                                                           tab_std.data(), o64, ust);
+           });
+      // parameter generation and the trajectory cost over compose_cmp's layout
+      float *var = dev(pool, (size_t)row, 1.0f), *gv = dev(pool, (size_t)dim, 1.0f), *traj = dev(pool, tf * dim, 0.0f);
+      float* gpred = dev(pool, tf * row, 0.0f);
+      double *cost3 = dev(pool, (size_t)nu * 3, 0.0), *gvar = dev(pool, (size_t)nu * row, 0.0);
+      const float *means[1] = {cmp}, *vars[1] = {var}, *gvs[1] = {gv};
+      float *outs[1] = {traj}, *gpreds[1] = {gpred};
+      WorldMi355MlpgOption lo;
+      WorldMi355DefaultMlpgOption(&lo);
+      ok = ok && step("ParameterGeneration", 0, [&] {
+             return WorldMi355ParameterGeneration(bf, 1, means, row, vars, 0, dims, nwin, windows, sizes, nullptr, &lo, outs, ust);
+           });
+      // the same rows through a 15-tap window: a wider band, the workspace is replaced while the context may have work queued
+      std::vector<double> w15(15, 0.0);
+      for (int i = 0; i < 15; ++i) w15[(size_t)i] = (i - 7) / 28.0;
+      const double* wins15[3] = {w0.data(), w15.data(), w2.data()};
+      const int sizes15[3] = {1, 15, 3};
+      const double* const* windows15[1] = {wins15};
+      const int* sizes_15[1] = {sizes15};
+      ok = ok && step("ParameterGeneration with 15 taps", 0, [&] {
+             return WorldMi355ParameterGeneration(bf, 1, means, row, vars, 0, dims, nwin, windows15, sizes_15, nullptr, &lo, outs, ust);
+           });
+      WorldMi355TrajectoryOption to;
+      WorldMi355DefaultTrajectoryOption(&to);
+      ok = ok && step("TrajectoryCost", 0, [&] {
+             return WorldMi355TrajectoryCost(bf, 1, means, means, row, vars, gvs, dims, nwin, windows, sizes, nullptr, nullptr,
+                                             nullptr, &to, cost3, outs, gpreds, nullptr, row, gvar, ust);
+           });
+      // the acoustic model: 3 inputs, one hidden layer of 4 units, 2 outputs
+      const int n_in = 3, n_hid = 4, n_out = 2, units[1] = {n_hid};
+      float *W0 = dev(pool, (size_t)n_in * n_hid, 0.1f), *W1 = dev(pool, (size_t)n_hid * n_out, 0.1f);
+      float *B0 = dev(pool, (size_t)n_hid, 0.0f), *B1 = dev(pool, (size_t)n_out, 0.0f), *mvar = dev(pool, (size_t)n_out, 1.0f);
+      const float *weights[2] = {W0, W1}, *biases[2] = {B0, B1};
+      WorldMi355AcousticModel am;
+      memset(&am, 0, sizeof(am));
+      am.n_layers = 1; am.n_inputs = n_in; am.n_outputs = n_out; am.n_spkrs = 1;
+      am.hidden_activation = 2; am.output_activation = 0;
+      am.units = units; am.weights = weights; am.biases = biases; am.variances = mvar;
+      float *ax = dev(pool, tf * n_in, 0.5f), *aout = dev(pool, tf * n_out, 0.0f), *aobs = dev(pool, tf * n_out, 0.25f);
+      float* gout = dev(pool, tf * n_out, 0.0f);
+      double *acost = dev(pool, (size_t)nu, 0.0), *agvar = dev(pool, (size_t)nu * n_out, 0.0);
+      ok = ok && step("AcousticModelForward", 0, [&] {
+             return WorldMi355AcousticModelForward(bf, &am, ax, n_in, nullptr, aout, n_out, aobs, n_out, acost, ust);
+           });
+      WorldMi355Dropout drop = {0.8f, 1u, 0u};
+      ok = ok && step("AcousticModelTrainForward", 0, [&] {
+             return WorldMi355AcousticModelTrainForward(bf, &am, &drop, ax, n_in, nullptr, aout, n_out, aobs, n_out, acost, gout,
+                                                        n_out, agvar, ust);
+           });
+      float *gW0 = dev(pool, (size_t)n_in * n_hid, 0.0f), *gW1 = dev(pool, (size_t)n_hid * n_out, 0.0f);
+      float *gB0 = dev(pool, (size_t)n_hid, 0.0f), *gB1 = dev(pool, (size_t)n_out, 0.0f);
+      float *gws[2] = {gW0, gW1}, *gbs[2] = {gB0, gB1};
+      ok = ok && step("AcousticModelBackward", 0, [&] {
+             return WorldMi355AcousticModelBackward(bf, &am, &drop, ax, n_in, nullptr, gout, n_out, gws, gbs, nullptr, ust);
+           });
+      WorldMi355OptimizerOption oo;
+      WorldMi355DefaultOptimizerOption(4, &oo);
+      float *m0 = dev(pool, (size_t)n_in * n_hid, 0.0f), *m1 = dev(pool, (size_t)n_hid * n_out, 0.0f);
+      float *v0 = dev(pool, (size_t)n_in * n_hid, 0.0f), *v1 = dev(pool, (size_t)n_hid * n_out, 0.0f);
+      float *params[2] = {W0, W1}, *slot0[2] = {m0, m1}, *slot1[2] = {v0, v1};
+      const float* grads[2] = {gW0, gW1};
+      const int64_t counts[2] = {n_in * n_hid, n_hid * n_out};
+      const float rates[2] = {0.1f, 0.2f};
+      int* ost = dev(pool, 2, 0);
+      ok = ok && step("OptimizerStep", 0,
+                      [&] { return WorldMi355OptimizerStep(ctx, &oo, 2, params, grads, slot0, slot1, counts, rates, ost); });
+      // label features: two binary questions, a float one, a reserved one; four lines over the three utterances
+      const WorldMi355LabelFeature feats[4] = {{0, "*-a+*", 0, 0}, {0, "*-b+*,*-c+*", 0, 0}, {1, "*/A:%d_*", 0, 10}, {6, nullptr, 0, 70}};
+      WorldMi355LabelFeatureSet* set = nullptr;
+      if (ok && WorldMi355CreateLabelFeatureSet(ctx, 4, feats, &set) != 0) return 45;
+      const int line_off[4] = {0, 1, 3, 4}, lstart[4] = {0, 0, 30, 0}, lend[4] = {5, 30, 64, 33}, lstate[4] = {0, 0, 0, 0};
+      const int level[3] = {0, 0, 0};
+      const char* names_a[4] = {"x^x-a+b=c/A:3_1", "x^a-b+c=x/A:12_2", "a^b-c+x=x/A:0_3", "x^x-a+b=c/A:3_1"};
+      const char* names_b[4] = {"x^x-c+b=a/A:7_1", "x^a-a+c=x/A:-2_2", "a^b-b+x=x/A:9_3", "x^x-c+b=a/A:7_1"};
+      float* ffi = dev(pool, tf * 4, 0.0f);
+      ok = ok && step("LabelFeatures", 0, [&] {
+             return WorldMi355LabelFeatures(bf, set, line_off, lstart, lend, lstate, names_a, level, ffi, 4, ust);
+           });
+      ok = ok && step("LabelFeatures again (other names)", 0, [&] {
+             return WorldMi355LabelFeatures(bf, set, line_off, lstart, lend, lstate, names_b, level, ffi, 4, ust);
+           });
+      WorldMi355DestroyLabelFeatureSet(set);
+      float *vlf0 = dev(pool, tf, 5.0f), *vib = dev(pool, tf * 2, 0.0f), *vout = dev(pool, tf * 2, 0.0f);
+      const int seg_off[4] = {0, 1, 2, 3}, seg_start[3] = {0, 0, 0}, seg_end[3] = {5, 64, 33};
+      const double seg_pitch[3] = {220.0, 0.0, 180.0};
+      int too_long = 0;
+      ok = ok && step("Vibrato", 0,
+                      [&] { return WorldMi355Vibrato(bf, vlf0, seg_off, seg_start, seg_end, seg_pitch, vib, vout, &too_long); });
+    }
+  }
+  // ---- the context moves to V: everything from here on is V's, the side streams included
+  ok = ok && step("SetStream", 0, [&] { return WorldMi355SetStream(ctx, V); });
+  HipStubTraceMark("caller V");
+  {
+    const size_t tx = (size_t)WorldMi355BatchTotalSamples(b), tf = (size_t)WorldMi355BatchTotalFrames(b);
+    double *x = dev(pool, tx, 0.1), *t = dev(pool, tf, 0.0), *f0 = dev(pool, tf, 120.0);
+    double *sp = dev(pool, tf * bins, 1.0), *ap = dev(pool, tf * bins, 0.5), *y = dev(pool, (size_t)WorldMi355BatchTotalOutputSamples(b), 0.0);
+    ok = ok && step("AnalyzeSynthesize after SetStream", 2, [&] { return WorldMi355AnalyzeSynthesize(b, x, t, f0, sp, ap, y); });
+  }
+  HipStubTraceMark("step teardown attempt 1");
+  if (!ok || g_steps_failed || WorldMi355Synchronize(ctx) != 0) return 46;
+  WorldMi355DestroyBatch(b);
+  WorldMi355DestroyBatch(bf);
+  WorldMi355DestroyBatch(bb);
+  WorldMi355DestroyContext(ctx);
+  (void)hipStreamDestroy(U);
+  (void)hipStreamDestroy(V);
+  WorldMi355SetErrorHandler(nullptr, nullptr);
+  printf("capi streams ok: %ld launches\n", HipStubLaunches());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && strcmp(argv[1], "batched") == 0) return batched_sequence();
+  if (argc > 1 && strcmp(argv[1], "streams") == 0) return stream_sequence();
   int last_code = 0;
   if (getenv("HIP_STUB_DEVICES") && atoi(getenv("HIP_STUB_DEVICES")) == 0) {
     // no device: the drop-in entry points report to the handler and return (reference entry points are void)

@@ -97,6 +97,11 @@ void HipStubTraceMark(const char* text) {                    // a line of the ha
   std::lock_guard<std::mutex> g(g_trace_mu);
   fprintf(g_trace, "# %s\n", text);
 }
+void HipStubTraceStream(const char* label, void* stream) {    // "# stream <label> s<k>": which trace name a stream of
+  if (!g_trace) return;                                       // the harness has (NULL is the legacy default stream)
+  std::lock_guard<std::mutex> g(g_trace_mu);
+  fprintf(g_trace, "# stream %s%s\n", label, ordinal(0, stream).c_str());
+}
 
 hipError_t hipGetDeviceCount(int* n) { *n = g_devices; return g_devices > 0 ? hipSuccess : hipErrorNoDevice; }
 hipError_t hipGetDevice(int* d) { *d = g_device.load(); return hipSuccess; }

@@ -58,7 +58,31 @@ def test_host_file_writer_under_asan_ubsan(tmp_path):
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
-def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
+@pytest.fixture(scope="module")
+def capi_harness(tmp_path_factory):
+    """tests/hostsan/capi_harness, built once for every test of this file that runs it: a stand-alone program, every
+    translation unit of the library compiled host-only under AddressSanitizer + UBSan against the stub runtime."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    rt = [p for p in ("/opt/rocm/lib/llvm/lib/clang",) if os.path.isdir(p)]
+    if not os.path.exists(hipcc) or not rt:
+        pytest.skip("hipcc / clang sanitizer runtimes not installed")
+    out = tmp_path_factory.mktemp("hs")
+    r = subprocess.run(["bash", os.path.join(ROOT, "tests", "hostsan", "build_capi_harness.sh"), str(out)],
+                       capture_output=True, text=True, timeout=900)
+    exe = out / "capi_harness"
+    assert r.returncode == 0 and exe.exists(), (r.stdout[-2000:], r.stderr[-2000:],
+                                                  [open(p).read()[-600:] for p in map(str, out.glob("*.log")) if os.path.getsize(p)])
+    return exe
+
+
+SAN_ENV = dict(ASAN_OPTIONS="abort_on_error=0:halt_on_error=1:detect_leaks=1",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+# pulse totals : per-utterance maxima of the six counting launches of a round: lists rendered in one piece (below
+# 2 x 16384 pulses, synthesis_prepare_finish) and in two, and a second part that outgrows the first one's records
+PULSES = "1000:50,1000:50,40000:300,33000:200,20000:100,90000:400"
+
+
+def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path, capi_harness):
     """the host marshalling under sanitizers.  Every translation unit of the library is compiled
     host-only (hipcc --cuda-host-only: no device code) with AddressSanitizer + UBSan and linked against
     tests/hostsan/hip_stub.cpp -- "device" memory is host heap, kernels do not run -- and tests/hostsan/capi_harness.cpp
@@ -78,18 +102,8 @@ def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
     error, the same call made again succeeds and queues what an undisturbed call queues -- less only what the failed
     attempt had already queued for set-ups that are made once (a table, a work arena) -- and everything after it is
     unchanged."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    rt = [p for p in ("/opt/rocm/lib/llvm/lib/clang",) if os.path.isdir(p)]
-    if not os.path.exists(hipcc) or not rt:
-        pytest.skip("hipcc / clang sanitizer runtimes not installed")
-    out = tmp_path / "hs"
-    r = subprocess.run(["bash", os.path.join(ROOT, "tests", "hostsan", "build_capi_harness.sh"), str(out)],
-                       capture_output=True, text=True, timeout=900)
-    exe = out / "capi_harness"
-    assert r.returncode == 0 and exe.exists(), (r.stdout[-2000:], r.stderr[-2000:],
-                                                  [open(p).read()[-600:] for p in map(str, out.glob("*.log")) if os.path.getsize(p)])
-    env = dict(os.environ, ASAN_OPTIONS="abort_on_error=0:halt_on_error=1:detect_leaks=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    exe = capi_harness
+    env = dict(os.environ, **SAN_ENV)
 
     def run(**extra):
         p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=dict(env, **extra))
@@ -104,9 +118,7 @@ def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
     for n in (0, 1, 3, 8, 21, 34, 55, 89, 120):
         assert "handler:" in run(HIP_STUB_FAIL_MALLOC_AFTER=str(n))
 
-    # pulse totals : per-utterance maxima of the six counting launches of a round: lists rendered in one piece (below
-    # 2 x 16384 pulses, synthesis_prepare_finish) and in two, and a second part that outgrows the first one's records
-    pulses = "1000:50,1000:50,40000:300,33000:200,20000:100,90000:400"
+    pulses = PULSES
     trace_file = tmp_path / "trace.txt"
 
     def canonical(lines):                   # streams and events renamed in order of first appearance
@@ -165,3 +177,110 @@ def test_host_layer_of_the_c_abi_under_asan_ubsan(tmp_path):
                 assert all(line in it for line in got[at:at + n_got]), (var, k)         # a subsequence, in order
                 missing = collections.Counter(map(strip, want[at:at + n_want])) - collections.Counter(map(strip, got[at:at + n_got]))
                 assert not missing - collections.Counter(map(strip, first_try[1])), (var, k, missing)
+
+
+def _violations(lines, caller="s0"):
+    import stream_rules
+    return stream_rules.check(lines, caller)
+
+
+def test_stream_rules_notice_handmade_mistakes():
+    """The checker of tests/stream_rules.py against traces written by hand: a correct fork and join, and each mistake
+    the rules are there for, one at a time."""
+    head = ["# stream null s0", "# stream U s1", "# stream V s2", "# caller U", "# step call"]
+    good = head + ["launch k grid 1 1 1 block 64 1 1 s1", "hipEventRecord s1 e0", "hipStreamWaitEvent s3 e0",
+                   "launch k grid 1 1 1 block 64 1 1 s3", "hipEventRecord s3 e1", "hipStreamWaitEvent s4 e1",
+                   "hipMemsetAsync s4", "hipEventRecord s4 e2", "hipStreamWaitEvent s1 e1", "hipStreamWaitEvent s1 e2"]
+    assert _violations(good)[0] == []
+
+    def texts(lines):
+        return [t for _, _, t in _violations(lines)[0]]
+    assert any("R1" in t for t in texts(head + ["hipMemsetAsync s0"]))
+    assert any("R1" in t for t in texts(head + ["hipEventRecord s0 e9"]))
+    assert any("not forked" in t for t in texts([l for l in good if l != "hipStreamWaitEvent s3 e0"]))
+    assert any("s4 is not joined" in t for t in texts(good[:-1]))
+    # s3 reaches the caller through s4, which waited for it and is joined itself; without s4's join neither does
+    assert texts([l for l in good if l != "hipStreamWaitEvent s1 e1"]) == []
+    assert any("s3 is not joined" in t for t in texts([l for l in good if not l.startswith("hipStreamWaitEvent s1")]))
+    # an event recorded BEFORE the side stream's last work joins nothing
+    late = good[:-2] + ["hipStreamWaitEvent s1 e1", "hipStreamWaitEvent s1 e2", "launch k grid 1 1 1 block 64 1 1 s4"]
+    assert any("s4 is not joined" in t for t in texts(late))
+    # a fork from an event of an EARLIER step is none; a host synchronise of the side stream is a join
+    stale = head + ["hipEventRecord s1 e0", "# step next", "hipStreamWaitEvent s3 e0", "hipMemsetAsync s3",
+                    "hipStreamSynchronize s3"]
+    assert texts(stale) == ["s3 was not forked from s1 and carries 'hipMemsetAsync s3'"]
+    # after the context has moved, the stream it left is like any other
+    moved = head + ["# caller V", "# step after", "launch k grid 1 1 1 block 64 1 1 s1"]
+    assert any("not forked from s2" in t for t in texts(moved))
+
+
+def test_stream_rules_hold_on_the_recorded_trace():
+    """R2 of tests/stream_rules.py over tests/golden/host_call_trace.txt as it is: the trace was recorded before the rules
+    were written, from contexts on the default stream (its `s0`), so it validates the checker -- including the one
+    path that starts a stream without a fork, the drop-in Synthesis()'s upload stream (the rule it obeys is in the
+    module's docstring)."""
+    golden = open(os.path.join(ROOT, "tests", "golden", "host_call_trace.txt")).read().splitlines()
+    bad, stats = _violations(golden, caller="s0")
+    print("recorded trace:", stats)
+    assert bad == []
+    assert stats["steps"] == 16 and stats["side_streams"] >= 16 and stats["work"] > 300
+    # the upload rule was needed by the drop-in Synthesis() steps (their first attempts, one a round) and by nothing else
+    drop_in = [i for i, l in enumerate(golden) if l.startswith("# step drop-in Synthesis")]
+    assert stats["unforked"] == len(drop_in) == 2
+
+
+STREAM_STEPS = ("SamplesFromPcm16", "Dio", "Harvest", "StoneMask", "CheapTrick", "D4C", "Analyze (forked)",
+                "AnalyzeSynthesize 1", "AnalyzeSynthesize 2 (overlapped)", "Synthesis in one part", "SamplesToPcm16",
+                "UtteranceStatus", "CodeSpectralEnvelope", "DecodeSpectralEnvelope", "CodeAperiodicity",
+                "DecodeAperiodicity", "RecipeFeatures", "RecipeDecode", "Synthesis in two parts", "ComposeCmp", "ComposeFfo",
+                "InterpolateGaps", "ColumnMoments", "ColumnMeans", "MelCepstrum", "MelCepstrumToSpectrum",
+                "MelCepstrumPostfilter", "ModulationSpectrumStats", "ModulationSpectrumPostfilter", "ParameterGeneration",
+                "ParameterGeneration with 15 taps", "TrajectoryCost", "AcousticModelForward", "AcousticModelTrainForward", "AcousticModelBackward",
+                "OptimizerStep", "LabelFeatures", "LabelFeatures again (other names)", "Vibrato")
+
+
+def test_every_entry_point_keeps_to_the_callers_stream(tmp_path, capi_harness):
+    """`capi_harness streams` (a stand-alone program under AddressSanitizer + UBSan, against the stub runtime): a context
+    on a stream U that is NOT the default stream drives every entry point that queues device work -- the WORLD stages,
+    both one-call forms, Synthesis in one part and in two, the sample formats, the codec, and every recipe stage: cmp /
+    ffo composition, gap interpolation, moments, mel-cepstra both ways, both postfilters and their statistics,
+    parameter generation, the trajectory cost, the acoustic model's three passes, the optimiser step, label features
+    (twice on one batch) and vibrato -- once plain and once with timing on (TimedScope's records), then moves to a
+    stream V (WorldMi355SetStream) and calls again.  The trace must obey tests/stream_rules.py: R1 nothing on the default
+    stream, R2 every stream of the library's own forked from the caller's and joined back within the call.  No path
+    of this sequence leaves work on a side stream across calls, so no step needs the upload rule."""
+    trace_file = tmp_path / "streams.txt"
+    p = subprocess.run([str(capi_harness), "streams"], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, HIP_STUB_TRACE=str(trace_file), HIP_STUB_PULSES=PULSES, **SAN_ENV))
+    text = p.stdout + p.stderr
+    assert p.returncode == 0 and "capi streams ok" in text, text[-4000:]
+    assert "AddressSanitizer" not in text and "LeakSanitizer" not in text and "runtime error" not in text, text[-4000:]
+    lines = trace_file.read_text().splitlines()
+    assert lines[:4] == ["# stream null s0", "# stream U s1", "# stream V s2", "# caller U"]
+    marks = [l[2:] for l in lines if l.startswith("# ")]
+    steps = [m[len("step "):-len(" attempt 1")] for m in marks if m.startswith("step ") and m.endswith(" attempt 1")]
+    assert steps == list(STREAM_STEPS) * 2 + ["SetStream", "AnalyzeSynthesize after SetStream", "teardown"]
+    assert not any(m.endswith("attempt 2") for m in marks)
+    # every step but the re-pointing and the teardown queued something, and on the caller's stream of the moment
+    at = {}
+    for i, l in enumerate(lines):
+        if l.startswith("# step "):
+            at[i] = []
+            cur = at[i]
+        elif not l.startswith("#") and at:
+            cur.append(l)
+    bodies = list(at.values())
+    assert all(any(c.startswith(("launch ", "hipMemcpyAsync", "hipMemsetAsync")) for c in b) for b in bodies[:-3])
+    assert bodies[-3] == ["hipStreamSynchronize s1"]                       # SetStream waits for the stream it leaves
+    assert any(c.endswith(" s2") for c in bodies[-2]) and not any(re.search(r" s1\b", c) for c in bodies[-2])
+    # the wider band of the second ParameterGeneration replaces the batch's workspace the first time round: the call
+    # waits for the caller's stream before anything else (the earlier call's kernel may still use the smaller block)
+    regrow = [b for i, b in at.items() if lines[i].startswith("# step ParameterGeneration with 15 taps")]
+    assert regrow[0][0] == "hipStreamSynchronize s1" and not any("Synchronize" in c for c in regrow[1])
+    # the multi-stream paths are in it (otherwise R2 would hold vacuously), TimedScope's records too
+    bad, stats = _violations(lines)
+    print("streams trace: %d lines," % len(lines), stats)
+    assert stats["side_streams"] >= 12 and sum(1 for l in lines if l.startswith("hipEventRecord s1")) > 100
+    assert any("hipDeviceSynchronize" in l for l in lines)                  # the split Synthesis's third piece
+    assert bad == [], bad[:10]
+    assert stats["unforked"] == 0                                           # no step needed the upload rule
