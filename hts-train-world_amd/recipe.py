@@ -56,6 +56,8 @@ There is no CPU path: without a HIP device the library call fails.
 from __future__ import annotations
 
 import argparse
+import contextlib
+import math
 import os
 import re
 import struct
@@ -132,6 +134,117 @@ def _batches(order, frames, limit):
         yield cur
 
 
+def _size_is(path, size):
+    try:
+        return os.path.getsize(str(path)) == size
+    except OSError:
+        return False
+
+
+def _rows_in(job, width, n_paths=None, what=None):
+    """Frames of `job` from the size of its first file, rows of `width` float32; with n_paths the job must hold that
+    many paths, which `what` names in the error."""
+    size = os.path.getsize(job[0])
+    if (n_paths is not None and len(job) != n_paths) or size % (4 * width):
+        raise ValueError("%s: %d bytes are no rows of %d float32%s" % (job[0], size, width, ", or not " + what if what else ""))
+    return size // (4 * width)
+
+
+def _my_jobs(frames, todo=lambda i: True):
+    """This rank's share of the jobs i with todo(i): the partition by frame count is made on those alone."""
+    left = [i for i in range(len(frames)) if todo(i)]
+    return [left[k] for k in _my_share([frames[i] for i in left])]
+
+
+def _upload(a, pinned=False):
+    """One host array as a device tensor: the drivers' only way onto the GPU."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return t.pin_memory().cuda(non_blocking=True) if pinned else t.cuda()
+
+
+def _put(path, rows, head=None):
+    if head is None:
+        np.ascontiguousarray(rows).tofile(path)
+    else:
+        with open(path, "wb") as f:
+            f.write(head)
+            f.write(np.ascontiguousarray(rows).tobytes())
+
+
+def _row_slices(b, host, paths):
+    """[(path, the rows of utterance k of batch `b` in the slab `host`)] for paths[k] that are not None: row slices of
+    a contiguous slab, contiguous themselves."""
+    fo = b.frame_offsets
+    return [(p, host[fo[k]:fo[k + 1]]) for k, p in enumerate(paths) if p is not None]
+
+
+class _Stage:
+    """What a file-list driver holds open: the context (its own when the caller gave none), the threads that read and
+    write files, and the writes in flight.  Leaving it waits for every write that was submitted; then, after a body
+    that did not raise, the first write that failed raises; a context made here is closed either way, a caller's never.
+    `frames` adds up the frames of the batches opened.  A driver opens it ahead of its first call into the library:
+    _own_context imports torch first (analysis_files says why)."""
+
+    def __init__(self, ctx, io_threads):
+        self.pool = ThreadPoolExecutor(io_threads)
+        self.writes, self.frames = [], 0
+        self.own_ctx = ctx is None
+        self.ctx = ctx or _own_context()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, failed, *_):
+        try:
+            self.pool.shutdown(wait=True)
+            if failed is None:
+                for w_ in self.writes:
+                    w_.result()
+        finally:
+            if self.own_ctx:
+                self.ctx.close()
+
+    def groups(self, jobs, frames, limit):
+        """The plan: the jobs in descending frame order, cut into groups of at most `limit` frames."""
+        return _batches(sorted(jobs, key=lambda i: -frames[i]), frames, limit)
+
+    def batch(self, params=None, **lengths):
+        """`with stage.batch(f0_lengths=...) as b`: a WorldBatch that is closed when the block is left, also by an
+        exception.  Without params the batch only carries lengths (48 kHz, 5 ms: no stage of such a driver reads them)."""
+        b = W.WorldBatch(self.ctx, params or W.default_params(48000, 5.0), **lengths)
+        self.frames += int(b.total_frames)
+        return contextlib.closing(b)
+
+    def batches(self, jobs, frames, limit, params=None):
+        """(group, stage.batch over the group's frame counts) along the plan."""
+        for group in self.groups(jobs, frames, limit):
+            yield group, self.batch(params, f0_lengths=[frames[i] for i in group])
+
+    def load(self, paths, cols=None, want=None):
+        """The float32 files `paths`, read by the pool as rows of `cols`, as one device tensor.  want: per path (frames,
+        the file that says so), checked."""
+        parts = list(self.pool.map(lambda p: _f32(p, cols), paths))
+        for p, a, (n, first) in zip(paths, parts, want or ()):
+            if len(a) != n:
+                raise ValueError("%s has %d frames, %s has %d" % (p, len(a), first, n))
+        return _upload(np.concatenate(parts))
+
+    def submit(self, fn, *args):
+        self.writes.append(self.pool.submit(fn, *args))
+
+    def put(self, b, host, paths, head=None):
+        """Utterance k's rows of the host slab to paths[k] (None: not written), one pool job each, beside the next
+        batch; head(rows): bytes in front of them (an HTK header)."""
+        for path, rows in _row_slices(b, host, paths):
+            self.submit(_put, path, rows, head(len(rows)) if head else None)
+
+    def put_native(self, b, slabs, threads):
+        """slabs: [(host slab, paths)] as put takes them, all files in ONE native call (WorldMi355WriteFiles: plain
+        threads, no interpreter lock) beside the next batch; the slabs live on in the job's arguments."""
+        self.submit(W.write_files, [item for host, paths in slabs for item in _row_slices(b, host, paths)], threads)
+
+
 def wav_header(path):
     """(sample count, sampling rate) from the header alone: what the partition needs (no samples are decoded)."""
     with wave.open(str(path), "rb") as w:
@@ -145,10 +258,7 @@ def outputs_complete(job, n_frames, fs, spec_dim=0, ap_dim=24):
     short left its last files missing or short (the native writer creates, fills and closes file after file)."""
     bins = capi.cheaptrick_fft_size(fs) // 2 + 1
     want = (4 * n_frames, 4 * n_frames * (spec_dim if spec_dim else bins), 4 * n_frames * (ap_dim if spec_dim else bins))
-    try:
-        return all(os.path.getsize(str(p)) == w for p, w in zip(job[1:4], want))
-    except OSError:
-        return False
+    return all(_size_is(p, w) for p, w in zip(job[1:4], want))
 
 
 def analysis_files(jobs, frame_period=5.0, fft_size=0, spec_dim=0, ap_dim=24, ctx=None,
@@ -162,60 +272,41 @@ def analysis_files(jobs, frame_period=5.0, fft_size=0, spec_dim=0, ap_dim=24, ct
     resume=True (every rank writes its shard only): a rank skips the jobs of ITS shard whose outputs are complete
     (outputs_complete) -- the partition is made on the whole list first, so ranks that start at different times agree on
     it whatever is on disk; the reference's recipe re-runs every utterance (data/Makefile.in:206-216)."""
-    import torch
+    import torch  # noqa: F401 -- ahead of capi below, the first call into the library: where libworld_mi355.so is
+    #                            loaded before torch, a fresh process's torch finds no GPU (`recipe.py analysis` did)
     jobs = list(jobs)
+    if gather and resume:
+        raise ValueError("resume goes with every rank writing its own shard (gather=False)")
     with ThreadPoolExecutor(io_threads) as pool:
         heads = list(pool.map(lambda j: wav_header(j[0]), jobs))
-        frames = [sharding.frame_count(n, fs, frame_period) for n, fs in heads]
-        for fs in sorted({h[1] for h in heads}):
-            own_size = capi.cheaptrick_fft_size(fs)                    # GetFFTSizeForCheapTrick at the 71 Hz floor
-            if fft_size not in (0, own_size):
-                # analysis.cpp:157-179 sizes the rows by argv[6] but CheapTrick still runs at its own default
-                # size for fs: any other value makes the reference write past or short of its rows
-                raise ValueError("fft_size %d is not CheapTrick's size for %d Hz (%d)" % (fft_size, fs, own_size))
-        own_ctx = ctx is None
-        ctx = ctx or _own_context()
-        if gather and resume:
-            raise ValueError("resume goes with every rank writing its own shard (gather=False)")
+    frames = [sharding.frame_count(n, fs, frame_period) for n, fs in heads]
+    for fs in sorted({h[1] for h in heads}):
+        own_size = capi.cheaptrick_fft_size(fs)                    # GetFFTSizeForCheapTrick at the 71 Hz floor
+        if fft_size not in (0, own_size):
+            # analysis.cpp:157-179 sizes the rows by argv[6] but CheapTrick still runs at its own default
+            # size for fs: any other value makes the reference write past or short of its rows
+            raise ValueError("fft_size %d is not CheapTrick's size for %d Hz (%d)" % (fft_size, fs, own_size))
+    with _Stage(ctx, io_threads) as stage:
         if gather:
-            done = _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, ctx, max_batch_frames, io_threads)
-            if own_ctx:
-                ctx.close()
-            return done
+            return _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, stage.ctx, max_batch_frames, io_threads)
         mine = _my_share(frames)
         if resume:
             mine = [i for i in mine if not outputs_complete(jobs[i], frames[i], heads[i][1], spec_dim, ap_dim)]
-        done = 0
-        writes = []
         for fs in sorted({heads[i][1] for i in mine}):
             params = W.default_params(fs, frame_period)
-            idx = sorted((i for i in mine if heads[i][1] == fs), key=lambda i: -frames[i])
-            for group in _batches(idx, frames, max_batch_frames):
-                xs = [x for x, _ in pool.map(lambda i: read_wav(jobs[i][0]), group)]   # this batch only, dropped after it
-                b = W.WorldBatch(ctx, params, x_lengths=[len(x) for x in xs])
-                x = torch.from_numpy(np.concatenate(xs)).pin_memory().cuda(non_blocking=True)
-                del xs
-                t, f0, sp, ap = b.analyze(x)
-                if spec_dim:
-                    f0o, spo, apo = b.recipe_features(f0, sp, ap, spec_dim, ap_dim)         # analysis.cpp:292-366
-                else:
-                    f0o, spo, apo = f0.float(), sp.float(), ap.float()                      # :360-390
-                f0h, sph, aph = (v.cpu().numpy() for v in (f0o, spo, apo))
-                fo = b.frame_offsets
-                items = []                     # row slices of contiguous slabs: contiguous themselves
-                for k, i in enumerate(group):
-                    a, e = fo[k], fo[k + 1]
-                    items.extend(zip(jobs[i][1:], (f0h[a:e], sph[a:e], aph[a:e])))
-                # the batch's files in ONE native call (WorldMi355WriteFiles: plain threads, no interpreter lock),
-                # beside the next batch's decoding and analysis; the slabs live on in the job's arguments
-                writes.append(pool.submit(W.write_files, items, io_threads))
-                done += int(b.total_frames)
-                b.close()
-        for w_ in writes:
-            w_.result()
-        if own_ctx:
-            ctx.close()
-    return done
+            for group in stage.groups([i for i in mine if heads[i][1] == fs], frames, max_batch_frames):
+                xs = [x for x, _ in stage.pool.map(lambda i: read_wav(jobs[i][0]), group)]   # this batch only, dropped after it
+                with stage.batch(params, x_lengths=[len(x) for x in xs]) as b:
+                    x = _upload(np.concatenate(xs), pinned=True)
+                    del xs
+                    t, f0, sp, ap = b.analyze(x)
+                    if spec_dim:
+                        f0o, spo, apo = b.recipe_features(f0, sp, ap, spec_dim, ap_dim)     # analysis.cpp:292-366
+                    else:
+                        f0o, spo, apo = f0.float(), sp.float(), ap.float()                  # :360-390
+                    stage.put_native(b, [(v.cpu().numpy(), [jobs[i][col] for i in group])
+                                         for col, v in enumerate((f0o, spo, apo), 1)], io_threads)
+    return stage.frames
 
 
 def _rank_world():
@@ -257,40 +348,27 @@ def synth_files(jobs, frame_period, fft_size, fs, spec_dim=0, ap_dim=24, ctx=Non
     """jobs: [(f0_in, sp_in, ap_in, wav_out)].  Writes what `synth f0 sp ap wav frame_period fft_size fs
     [spec_dim [ap_dim]]` writes.  In the coded form the ap bins beyond the coding order, which the reference
     leaves uninitialised (synth.cpp:240-245), are 0."""
-    import torch
     jobs = list(jobs)
     w = fft_size // 2 + 1
+    cols = (None, spec_dim, ap_dim) if spec_dim else (None, w, w)
     frames = [os.path.getsize(j[0]) // 4 for j in jobs]                                     # synth.cpp:151-158
     mine = _my_share(frames)
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    params = W.default_params(fs, frame_period, fft_size=fft_size)
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+    with _Stage(ctx, io_threads) as stage:
+        params = W.default_params(fs, frame_period, fft_size=fft_size)
+        for group in stage.groups(mine, frames, max_batch_frames):
             T = [frames[i] for i in group]
             ylen = [int((t - 1) * frame_period / 1000.0 * fs) + 1 for t in T]              # synth.cpp:259
-            b = W.WorldBatch(ctx, params, f0_lengths=T, y_lengths=ylen)
-            cols = (spec_dim, ap_dim) if spec_dim else (w, w)
-            f0s, sps, aps = zip(*pool.map(lambda i: (_f32(jobs[i][0]), _f32(jobs[i][1], cols[0]),
-                                                     _f32(jobs[i][2], cols[1])), group))
-            dev = lambda parts: torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda()
-            if spec_dim:
-                f0, sp, ap = b.recipe_decode(dev(f0s), dev(sps), dev(aps))                  # synth.cpp:168-256
-            else:
-                f0, sp, ap = dev(f0s).double(), dev(sps).double(), dev(aps).double()
-            y = b.synthesize(f0, sp, ap).cpu().numpy()
-            yo = b.out_offsets
-            for k, i in enumerate(group):
-                writes.append(pool.submit(write_wav, jobs[i][3], y[yo[k]:yo[k + 1]], fs))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+            with stage.batch(params, f0_lengths=T, y_lengths=ylen) as b:
+                f0, sp, ap = (stage.load([jobs[i][c] for i in group], cols[c]) for c in range(3))
+                if spec_dim:
+                    f0, sp, ap = b.recipe_decode(f0, sp, ap)                                # synth.cpp:168-256
+                else:
+                    f0, sp, ap = f0.double(), sp.double(), ap.double()
+                y = b.synthesize(f0, sp, ap).cpu().numpy()
+                yo = b.out_offsets
+                for k, i in enumerate(group):
+                    stage.submit(write_wav, jobs[i][3], y[yo[k]:yo[k + 1]], fs)
+    return stage.frames
 
 
 def read_window(path):
@@ -299,6 +377,15 @@ def read_window(path):
         tok = f.readline().split()
     n = int(tok[0])
     return [float(v) for v in tok[1:1 + n]]
+
+
+def _windows(ws):
+    """A stream's windows as coefficient lists: each a window file (read_window) or the coefficients themselves."""
+    return [read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws]
+
+
+def _streams_arg(streams):
+    return [(int(d), _windows(ws), bool(m)) for d, ws, m in streams]
 
 
 def cmp_files(jobs, streams, sampling_rate, frame_shift, htk_type=9, ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
@@ -310,45 +397,21 @@ def cmp_files(jobs, streams, sampling_rate, frame_shift, htk_type=9, ctx=None, m
              merges them (mgc, lf0, bap, vib); the four must have the same T
     streams: [(dim_s, [window files or coefficient lists])] per stream
     sampling_rate, frame_shift: addhtkheader.pl's SAMPFREQ and FRAMESHIFT (samples)"""
-    import torch
     jobs = list(jobs)
     ns = len(streams)
     dims = [int(d) for d, _ in streams]
-    wins = [[read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws] for _, ws in streams]
+    wins = [_windows(ws) for _, ws in streams]
     cols = sum(d * len(w) for d, w in zip(dims, wins))
     frames = [os.path.getsize(j[0]) // (4 * dims[0]) for j in jobs]
     mine = _my_share(frames)
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            T = [frames[i] for i in group]
-            b = W.WorldBatch(ctx, W.default_params(sampling_rate, 5.0), f0_lengths=T)
-            dev = []
-            for s_ in range(ns):
-                parts = list(pool.map(lambda i: _f32(jobs[i][s_], dims[s_]), group))
-                for i, a in zip(group, parts):
-                    if len(a) != frames[i]:
-                        raise ValueError("%s has %d frames, %s has %d" % (jobs[i][s_], len(a), jobs[i][0], frames[i]))
-                dev.append((torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda(), wins[s_]))
-            out = b.compose_cmp(dev).cpu().numpy()
-            fo = b.frame_offsets
-
-            def put(path, rows):
-                with open(path, "wb") as f:
-                    f.write(W.htk_header(len(rows), sampling_rate, frame_shift, 4 * cols, htk_type))
-                    f.write(np.ascontiguousarray(rows).tobytes())
-            for k, i in enumerate(group):
-                writes.append(pool.submit(put, jobs[i][ns], out[fo[k]:fo[k + 1]]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+    head = lambda n: W.htk_header(n, sampling_rate, frame_shift, 4 * cols, htk_type)
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames, W.default_params(sampling_rate, 5.0)):
+            with batch as b:
+                want = [(frames[i], jobs[i][0]) for i in group]
+                dev = [(stage.load([jobs[i][s_] for i in group], dims[s_], want), wins[s_]) for s_ in range(ns)]
+                stage.put(b, b.compose_cmp(dev).cpu().numpy(), [jobs[i][ns] for i in group], head)
+    return stage.frames
 
 
 # ---- parameter generation (scripts/Training.pl:2755-2810 gen_param) ------------------------------------------------
@@ -368,10 +431,7 @@ def ffo_layout(streams):
 def gen_param_complete(job, n_frames, streams):
     """True when every stream file of `job` = (ffo, out_0, ..., out_k) exists with the size generation writes
     (float32 [n_frames][dim_s]): the test behind `resume`, as outputs_complete is for analysis."""
-    try:
-        return all(os.path.getsize(str(p)) == 4 * n_frames * int(d) for p, (d, _, _) in zip(job[1:], streams))
-    except OSError:
-        return False
+    return all(_size_is(p, 4 * n_frames * int(d)) for p, (d, _, _) in zip(job[1:], streams))
 
 
 def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx=None,
@@ -386,49 +446,28 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
     var_path: one float32 row in the ffo layout, the global variances (:2788-2791)
     A frame with voicing value below 0.5 (:2782) receives unvoiced_value in every dim of its stream (:2783, :2800-2801).
     Rank-sharded by frame count; with resume, utterances whose stream files are complete are skipped."""
-    import torch
     jobs = list(jobs)
-    streams = [(int(d), [read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws],
-                bool(m)) for d, ws, m in streams]
+    streams = _streams_arg(streams)
     layout, width = ffo_layout(streams)
     var = np.fromfile(var_path, dtype=np.float32)
     if var.size != width:
         raise ValueError("%s has %d values, an ffo row has %d" % (var_path, var.size, width))
-    frames = []
-    for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 1 + len(streams) or size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not %d output paths" % (j[0], size, width, len(streams)))
-        frames.append(size // (4 * width))
-    todo = [i for i in range(len(jobs)) if not (resume and gen_param_complete(jobs[i], frames[i], streams))]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    dvar = torch.from_numpy(var).cuda()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
-            args = [(rows[:, c0:c0 + n], dvar[c0:c0 + n], wins, None if mcol is None else rows[:, mcol])
-                    for (mcol, c0, n), (_, wins, _) in zip(layout, streams)]
-            outs, status = b.parameter_generation(args, edge=edge, unvoiced_value=unvoiced_value)
-            for k in np.nonzero(status.cpu().numpy())[0]:
-                print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
-                      file=sys.stderr)
-            host = [o.cpu().numpy() for o in outs]
-            fo = b.frame_offsets
-            for k, i in enumerate(group):
-                for s_, h in enumerate(host):
-                    writes.append(pool.submit(np.ascontiguousarray(h[fo[k]:fo[k + 1]]).tofile, jobs[i][1 + s_]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+    frames = [_rows_in(j, width, 1 + len(streams), "%d output paths" % len(streams)) for j in jobs]
+    mine = _my_jobs(frames, lambda i: not (resume and gen_param_complete(jobs[i], frames[i], streams)))
+    with _Stage(ctx, io_threads) as stage:
+        dvar = _upload(var)
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                rows = stage.load([jobs[i][0] for i in group], width)
+                args = [(rows[:, c0:c0 + n], dvar[c0:c0 + n], wins, None if mcol is None else rows[:, mcol])
+                        for (mcol, c0, n), (_, wins, _) in zip(layout, streams)]
+                outs, status = b.parameter_generation(args, edge=edge, unvoiced_value=unvoiced_value)
+                for k in np.nonzero(status.cpu().numpy())[0]:
+                    print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
+                          file=sys.stderr)
+                for s_, o in enumerate(outs):
+                    stage.put(b, o.cpu().numpy(), [jobs[i][1 + s_] for i in group])
+    return stage.frames
 
 
 # ---- trajectory training's criterion and outputs (scripts/Training.pl:930-940, DNNDefine.trajectory_cost) --------------
@@ -452,7 +491,6 @@ def trajectory_files(jobs, streams, var_path, gv_path, msd_weight=1.0, gv_weight
     parameter_generation's (edge 0, no voicing mask) and no cost is evaluated.  Returns one entry per job: the cost
     trj + msd_weight msd + gv_weight gv, or None (no targets; skipped by resume; another rank's; a flagged utterance,
     which is reported on stderr and whose flagged columns are zeros).  Rank-sharded by frame count."""
-    import torch
     from . import training
     jobs = [tuple(j) for j in jobs]
     streams = _streams_arg(streams)
@@ -468,52 +506,37 @@ def trajectory_files(jobs, streams, var_path, gv_path, msd_weight=1.0, gv_weight
             raise ValueError("%s has %d values, the streams have %d static columns" % (gv_path, gv.size, sum(d for d, _, _ in streams)))
     frames = []
     for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 3 or size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not (pred, obs, out)" % (j[0], size, width))
-        if j[1] is not None and os.path.getsize(j[1]) != size:
+        frames.append(_rows_in(j, width, 3, "(pred, obs, out)"))
+        if j[1] is not None and os.path.getsize(j[1]) != 4 * width * frames[-1]:
             raise ValueError("%s and %s differ in size" % (j[0], j[1]))
-        frames.append(size // (4 * width))
-    todo = [i for i in range(len(jobs))
-            if not (resume and jobs[i][2] is not None and _size_is(jobs[i][2], 4 * frames[i] * out_cols))]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    dvar = torch.from_numpy(var).cuda()
-    dgv = torch.from_numpy(gv).cuda() if need_gv else None
+    mine = _my_jobs(frames, lambda i: not (resume and jobs[i][2] is not None
+                                           and _size_is(jobs[i][2], 4 * frames[i] * out_cols)))
     costs = [None] * len(jobs)
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
+    with _Stage(ctx, io_threads) as stage:
+        dvar = _upload(var)
+        dgv = _upload(gv) if need_gv else None
         for with_obs in (True, False):
             part = [i for i in mine if (jobs[i][1] is not None) == with_obs]
-            for group in _batches(sorted(part, key=lambda i: -frames[i]), frames, max_batch_frames):
-                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-                load = lambda col: torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][col], width), group)))).cuda()
-                pred = load(0)
-                if with_obs:
-                    cost, c, _, _, status = b.trajectory_cost(training.stream_views(pred, load(1), streams), dvar, dgv,
-                                                              msd_weight, gv_weight, want_grad_pred=False,
-                                                              want_grad_var=False)
-                    total = (cost[:, 0] + msd_weight * cost[:, 1] + gv_weight * cost[:, 2]).cpu().numpy()
-                else:
-                    c, status = b.parameter_generation([(pred[:, c0:c0 + n], dvar[c0:c0 + n], wins, None)
-                                                        for (_, c0, n), (_, wins, _) in zip(layout, streams)], edge=0)
-                status = status.cpu().numpy()
-                for k in np.nonzero(status)[0]:
-                    print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
-                          file=sys.stderr)
-                host = training.final_outputs(b, pred, c, streams).cpu().numpy()
-                fo = b.frame_offsets
-                for k, i in enumerate(group):
-                    if with_obs and status[k] == 0:
-                        costs[i] = float(total[k])
-                    if jobs[i][2] is not None:
-                        writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][2]))
-                b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
+            for group, batch in stage.batches(part, frames, max_batch_frames):
+                with batch as b:
+                    load = lambda col: stage.load([jobs[i][col] for i in group], width)
+                    pred = load(0)
+                    if with_obs:
+                        cost, c, _, _, status = b.trajectory_cost(training.stream_views(pred, load(1), streams), dvar, dgv,
+                                                                  msd_weight, gv_weight, want_grad_pred=False,
+                                                                  want_grad_var=False)
+                        total = (cost[:, 0] + msd_weight * cost[:, 1] + gv_weight * cost[:, 2]).cpu().numpy()
+                    else:
+                        c, status = b.parameter_generation([(pred[:, c0:c0 + n], dvar[c0:c0 + n], wins, None)
+                                                            for (_, c0, n), (_, wins, _) in zip(layout, streams)], edge=0)
+                    status = status.cpu().numpy()
+                    for k in np.nonzero(status)[0]:
+                        print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
+                              file=sys.stderr)
+                    stage.put(b, training.final_outputs(b, pred, c, streams).cpu().numpy(), [jobs[i][2] for i in group])
+                    for k, i in enumerate(group):
+                        if with_obs and status[k] == 0:
+                            costs[i] = float(total[k])
     return costs
 
 
@@ -556,46 +579,33 @@ def forward_files(jobs, model_path, out_dir, spkr=None, extension="ffo", ctx=Non
         raise ValueError("speaker %d: the model has %d" % (s_id, model.n_spkrs))
     frames = []
     for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 2 or size % (4 * n_in):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not (ffi, ffo)" % (j[0], size, n_in))
-        frames.append(size // (4 * n_in))
+        frames.append(_rows_in(j, n_in, 2, "(ffi, ffo)"))
         if j[1] is not None and os.path.getsize(j[1]) != 4 * n_out * frames[-1]:
             raise ValueError("%s does not hold %d rows of %d float32, as %s asks" % (j[1], frames[-1], n_out, j[0]))
     mine = [i for i in _my_share(frames) if frames[i] > 0]
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    model = model.cuda()
-    var_row = model.variance.variances[s_id].detach().to(torch.float32).cpu().numpy()
-    os.makedirs(str(out_dir), exist_ok=True)
+    bases = [os.path.join(str(out_dir), os.path.splitext(os.path.basename(j[0]))[0]) for j in jobs]
     costs = [None] * len(jobs)
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
+    with _Stage(ctx, io_threads) as stage:
+        model = model.cuda()
+        var_row = model.variance.variances[s_id].detach().to(torch.float32).cpu().numpy()
+        os.makedirs(str(out_dir), exist_ok=True)
         for with_obs in (True, False):
             part = [i for i in mine if (jobs[i][1] is not None) == with_obs]
-            for group in _batches(sorted(part, key=lambda i: -frames[i]), frames, max_batch_frames):
-                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-                load = lambda col, w: torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][col], w), group)))).cuda()
-                out, cost, status = model.infer(b, load(0, n_in), [s_id] * len(group), load(1, n_out) if with_obs else None,
-                                                max_chunk_frames)
-                host, status = out.cpu().numpy(), status.cpu().numpy()
-                cost = cost.cpu().numpy() if cost is not None else None
-                fo = b.frame_offsets
-                for k, i in enumerate(group):
-                    base = os.path.join(str(out_dir), os.path.splitext(os.path.basename(jobs[i][0]))[0])
-                    if status[k]:
-                        print("warning: %s: status %d, its rows are zeros" % (jobs[i][0], int(status[k])), file=sys.stderr)
-                    elif with_obs:
-                        costs[i] = float(cost[k])
-                        report("    Evaluation: cost = %e (%s)" % (costs[i], jobs[i][0]))
-                    writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile,
-                                              base + "." + extension if extension else base))
-                    writes.append(pool.submit(var_row.tofile, base + ".var"))
-                b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
+            for group, batch in stage.batches(part, frames, max_batch_frames):
+                with batch as b:
+                    load = lambda col, w: stage.load([jobs[i][col] for i in group], w)
+                    out, cost, status = model.infer(b, load(0, n_in), [s_id] * len(group),
+                                                    load(1, n_out) if with_obs else None, max_chunk_frames)
+                    host, status = out.cpu().numpy(), status.cpu().numpy()
+                    cost = cost.cpu().numpy() if cost is not None else None
+                    for k, i in enumerate(group):
+                        if status[k]:
+                            print("warning: %s: status %d, its rows are zeros" % (jobs[i][0], int(status[k])), file=sys.stderr)
+                        elif with_obs:
+                            costs[i] = float(cost[k])
+                            report("    Evaluation: cost = %e (%s)" % (costs[i], jobs[i][0]))
+                        stage.submit(var_row.tofile, bases[i] + ".var")
+                    stage.put(b, host, [bases[i] + "." + extension if extension else bases[i] for i in group])
     return costs
 
 
@@ -904,89 +914,76 @@ def train_files(jobs, model_path, n_inputs, units, n_outputs, n_spkrs=1, varianc
     own_ctx = ctx is None and device != "cpu"
     if own_ctx:
         ctx = _own_context()
-    x = torch.from_numpy(np.concatenate([_f32(j[0], n_inputs) for j in jobs])).to(device)
-    obs = torch.from_numpy(np.concatenate([_f32(j[1], n_outputs) for j in jobs])).to(device)
-    file_spkr = [int(j[2]) for j in jobs]
-    f_off = np.concatenate([[0], np.cumsum(frames)])
-    if updates == "tf1":
-        opt = Tf1Optimizer(model, optimizer, learning_rate, ctx, adapt)
-        state = model.optimizer_state if restore is not None else None
-        if state is not None and str(state.get("rule")) == opt.name:
-            opt.load_state_arrays(state)
-        elif restore is not None:
-            report("%s holds no state of optimiser %s: its state begins anew" % (restore, opt.name))
-    else:
-        opt = make_optimizer(model, optimizer, learning_rate)
-        if adapt:
-            si = {id(p) for k, p in model.named_parameters() if k.split(".")[-1].startswith("si_")}
-            for g in opt.param_groups:
-                if g["params"] and id(g["params"][0]) in si:
-                    g["lr"] = 0.0
-    state_of = (lambda: opt.state_arrays()) if updates == "tf1" else (lambda: None)
-    batch = (lambda lengths: W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)) if ctx is not None \
-        else (lambda lengths: None)
-    draws = minibatches(np.repeat(file_spkr, frames), batch_size, n_steps, seed, start) if layout is None \
-        else utterance_minibatches(file_spkr, batch_size, n_steps, seed, start)
-    log = []
-    for step, draw in enumerate(draws, start):
-        opt.zero_grad(set_to_none=True)
-        live = []
-        try:
-            if layout is None:
-                rows, lengths, spkrs = draw
-                idx = torch.from_numpy(rows).to(device)
-                live.append(batch(lengths))
-                cost = _train_cost(model, live[0], x[idx], obs[idx], lengths, spkrs, keep_prob, seed, step)
-            else:
-                files, spkrs = draw
-                lengths = [frames[i] for i in files]
-                idx = torch.from_numpy(np.concatenate([np.arange(f_off[i], f_off[i + 1]) for i in files])).to(device)
-                live.append(batch(lengths))
-                parts, off = [], np.concatenate([[0], np.cumsum(lengths)])
-                for s in sorted(set(spkrs)):
-                    k0, k1 = spkrs.index(s), len(spkrs) - spkrs[::-1].index(s)
-                    live.append(batch(lengths[k0:k1]))
-                    parts.append((s, live[-1], int(off[k0]), int(off[k1])))
-                cost = _train_cost_trajectory(model, live[0], parts, x[idx], obs[idx], spkrs, layout, gv_var, msd_weight,
-                                              gv_weight, keep_prob, seed, step)
-            cost.backward()
-        finally:
-            for b in live:
-                if b is not None:
-                    b.close()
-        opt.step()
-        if log_interval > 0 and ((step - start) % log_interval == 0 or step == start + n_steps - 1):
-            log.append((step, float(cost.detach())))
-            report("Step %7d: cost = %e" % log[-1])
-        if save_interval > 0 and (step + 1 - start) % save_interval == 0 and step + 1 < start + n_steps:
-            model.save(model_path, step + 1, state_of())
-    model.save(model_path, start + n_steps, state_of())
-    if own_ctx:
-        ctx.close()
+    try:
+        x = torch.from_numpy(np.concatenate([_f32(j[0], n_inputs) for j in jobs])).to(device)
+        obs = torch.from_numpy(np.concatenate([_f32(j[1], n_outputs) for j in jobs])).to(device)
+        file_spkr = [int(j[2]) for j in jobs]
+        f_off = np.concatenate([[0], np.cumsum(frames)])
+        if updates == "tf1":
+            opt = Tf1Optimizer(model, optimizer, learning_rate, ctx, adapt)
+            state = model.optimizer_state if restore is not None else None
+            if state is not None and str(state.get("rule")) == opt.name:
+                opt.load_state_arrays(state)
+            elif restore is not None:
+                report("%s holds no state of optimiser %s: its state begins anew" % (restore, opt.name))
+        else:
+            opt = make_optimizer(model, optimizer, learning_rate)
+            if adapt:
+                si = {id(p) for k, p in model.named_parameters() if k.split(".")[-1].startswith("si_")}
+                for g in opt.param_groups:
+                    if g["params"] and id(g["params"][0]) in si:
+                        g["lr"] = 0.0
+        state_of = (lambda: opt.state_arrays()) if updates == "tf1" else (lambda: None)
+        batch = (lambda lengths: W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)) if ctx is not None \
+            else (lambda lengths: None)
+        draws = minibatches(np.repeat(file_spkr, frames), batch_size, n_steps, seed, start) if layout is None \
+            else utterance_minibatches(file_spkr, batch_size, n_steps, seed, start)
+        log = []
+        for step, draw in enumerate(draws, start):
+            opt.zero_grad(set_to_none=True)
+            live = []
+            try:
+                if layout is None:
+                    rows, lengths, spkrs = draw
+                    idx = torch.from_numpy(rows).to(device)
+                    live.append(batch(lengths))
+                    cost = _train_cost(model, live[0], x[idx], obs[idx], lengths, spkrs, keep_prob, seed, step)
+                else:
+                    files, spkrs = draw
+                    lengths = [frames[i] for i in files]
+                    idx = torch.from_numpy(np.concatenate([np.arange(f_off[i], f_off[i + 1]) for i in files])).to(device)
+                    live.append(batch(lengths))
+                    parts, off = [], np.concatenate([[0], np.cumsum(lengths)])
+                    for s in sorted(set(spkrs)):
+                        k0, k1 = spkrs.index(s), len(spkrs) - spkrs[::-1].index(s)
+                        live.append(batch(lengths[k0:k1]))
+                        parts.append((s, live[-1], int(off[k0]), int(off[k1])))
+                    cost = _train_cost_trajectory(model, live[0], parts, x[idx], obs[idx], spkrs, layout, gv_var, msd_weight,
+                                                  gv_weight, keep_prob, seed, step)
+                cost.backward()
+            finally:
+                for b in live:
+                    if b is not None:
+                        b.close()
+            opt.step()
+            if log_interval > 0 and ((step - start) % log_interval == 0 or step == start + n_steps - 1):
+                log.append((step, float(cost.detach())))
+                report("Step %7d: cost = %e" % log[-1])
+            if save_interval > 0 and (step + 1 - start) % save_interval == 0 and step + 1 < start + n_steps:
+                model.save(model_path, step + 1, state_of())
+        model.save(model_path, start + n_steps, state_of())
+    finally:
+        if own_ctx:
+            ctx.close()
     return log
 
 
 # ---- training targets, their variances and the GV data (data/Makefile.in:325-459, Training.pl:1402-1491) -------------
-def _streams_arg(streams):
-    return [(int(d), [read_window(w) if isinstance(w, (str, os.PathLike)) else [float(v) for v in w] for w in ws],
-             bool(m)) for d, ws, m in streams]
-
-
-def _size_is(path, size):
-    try:
-        return os.path.getsize(str(path)) == size
-    except OSError:
-        return False
-
-
 def _stream_frames(jobs, dims, n_paths, what):
     """Frames per job from the first stream file's size; every stream file of a job must hold as many rows."""
     frames = []
     for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != n_paths or size % (4 * dims[0]):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not %s" % (j[0], size, dims[0], what))
-        frames.append(size // (4 * dims[0]))
+        frames.append(_rows_in(j, dims[0], n_paths, what))
         for path, dim in zip(j[1:len(dims)], dims[1:]):
             other = os.path.getsize(path)
             if other != 4 * dim * frames[-1]:
@@ -1007,48 +1004,30 @@ def ffo_files(jobs, streams, unvoiced_value=-1.0e10, ctx=None, max_batch_frames=
     interpolate.pl dies there and the Makefile's `-s` tests skip the utterance.  Frame counts must agree across an
     utterance's files.  Rank-sharded by frame count; with resume, utterances whose ffo file is complete are skipped.
     Returns the frames composed."""
-    import torch
     jobs = list(jobs)
     streams = _streams_arg(streams)
     ns = len(streams)
     width = ffo_layout(streams)[1]
     frames = _stream_frames(jobs, [d for d, _, _ in streams], ns + 1, "%d stream files and one output path" % ns)
-    todo = [i for i in range(len(jobs)) if frames[i] > 0 and not (resume and _size_is(jobs[i][ns], 4 * width * frames[i]))]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    mine = _my_jobs(frames, lambda i: frames[i] > 0 and not (resume and _size_is(jobs[i][ns], 4 * width * frames[i])))
     if not mine:
         return 0
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-            dev, bad = [], np.zeros(len(group), dtype=np.int32)
-            for s_, (dim, wins, msd) in enumerate(streams):
-                parts = list(pool.map(lambda i: _f32(jobs[i][s_], dim), group))
-                x = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda()
-                if msd:
-                    x, voiced, status = b.interpolate_gaps(x, unvoiced_value)
-                    bad |= status.cpu().numpy()
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                dev, bad = [], np.zeros(len(group), dtype=np.int32)
+                for s_, (dim, wins, msd) in enumerate(streams):
+                    x, voiced = stage.load([jobs[i][s_] for i in group], dim), None
+                    if msd:
+                        x, voiced, status = b.interpolate_gaps(x, unvoiced_value)
+                        bad |= status.cpu().numpy()
                     dev.append((x, wins, voiced))
-                else:
-                    dev.append((x, wins, None))
-            out = b.compose_ffo(dev).cpu().numpy()
-            fo = b.frame_offsets
-            for k, i in enumerate(group):
-                if bad[k]:
+                out = b.compose_ffo(dev).cpu().numpy()
+                for k in np.nonzero(bad)[0]:
                     print("warning: %s: a column of an msd stream holds no valid value, %s is not written" % (
-                        jobs[i][0], jobs[i][ns]), file=sys.stderr)
-                    continue
-                writes.append(pool.submit(np.ascontiguousarray(out[fo[k]:fo[k + 1]]).tofile, jobs[i][ns]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+                        jobs[group[k]][0], jobs[group[k]][ns]), file=sys.stderr)
+                stage.put(b, out, [None if bad[k] else jobs[i][ns] for k, i in enumerate(group)])
+    return stage.frames
 
 
 # ---- the acoustic model's input rows from labels (data/scripts/makefeature.pl, Training.pl:1677-1723) ----------------
@@ -1176,7 +1155,6 @@ def ffi_files(jobs, config, frame_shift, ctx=None, max_batch_frames=MAX_BATCH_FR
     Rank-sharded by frame count; with resume, utterances whose ffi file is complete are skipped.  Where the script warns,
     the utterances are counted per kind and the counts printed on stderr ("Out of range": a value was clamped to 0 or 1;
     "There is not state-level information in label").  Returns the frames written."""
-    import torch
     jobs = list(jobs)
     if any(len(j) != 2 for j in jobs):
         raise ValueError("ffi_files: a job is (label_file, ffi_out)")
@@ -1186,29 +1164,20 @@ def ffi_files(jobs, config, frame_shift, ctx=None, max_batch_frames=MAX_BATCH_FR
         raise ValueError("ffi_files: the question config holds no feature")
     labels = [read_label(j[0], frame_shift) for j in jobs]
     frames = [sum(e - s for s, e, _, _ in lines) for lines, _ in labels]
-    todo = [i for i in range(len(jobs)) if not (resume and _size_is(jobs[i][1], 4 * nf * frames[i]))]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 4 * nf * frames[i])))
     if not mine:
         return 0
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    fset = W.LabelFeatureSet(ctx, features)
-    done, clamped, no_state = 0, 0, 0
-    for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-        b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-        out, status = b.label_features(fset, [labels[i] for i in group])
-        rows, status = out.cpu().numpy(), status.cpu().numpy()
-        fo = b.frame_offsets
-        W.write_files([(jobs[i][1], np.ascontiguousarray(rows[fo[k]:fo[k + 1]])) for k, i in enumerate(group)], io_threads)
-        clamped += int((status & 1 != 0).sum())
-        no_state += int((status & 2 != 0).sum())
-        done += int(b.total_frames)
-        b.close()
-    fset.close()
-    if own_ctx:
-        ctx.close()
+    clamped, no_state = 0, 0
+    with _Stage(ctx, io_threads) as stage, contextlib.closing(W.LabelFeatureSet(stage.ctx, features)) as fset:
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                out, status = b.label_features(fset, [labels[i] for i in group])
+                rows, status = out.cpu().numpy(), status.cpu().numpy()
+                stage.put_native(b, [(rows, [jobs[i][1] for i in group])], io_threads)
+                clamped += int((status & 1 != 0).sum())
+                no_state += int((status & 2 != 0).sum())
     print("warnings: Out of range in %d utterances, no state-level information in %d" % (clamped, no_state), file=sys.stderr)
-    return done
+    return stage.frames
 
 
 def stats_files(ffo_paths, streams, out_dir, names=("mgc", "lf0", "bap", "vib"), ctx=None,
@@ -1234,31 +1203,20 @@ def stats_files(ffo_paths, streams, out_dir, names=("mgc", "lf0", "bap", "vib"),
     layout, width = ffo_layout(streams)
     if len(names) < len(streams):
         raise ValueError("stats_files: %d streams but %d names" % (len(streams), len(names)))
-    frames = []
-    for p in paths:
-        size = os.path.getsize(p)
-        if size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32" % (p, size, width))
-        frames.append(size // (4 * width))
-    some = [i for i in range(len(paths)) if frames[i] > 0]            # a batch holds no utterance without frames
-    mine = sorted(some[k] for k in _my_share([frames[i] for i in some]))
+    frames = [_rows_in((p,), width) for p in paths]
+    mine = sorted(_my_jobs(frames, lambda i: frames[i] > 0))          # a batch holds no utterance without frames
     rank, world = _rank_world()
     at = {i: k for k, i in enumerate(mine)}
     cnt = np.zeros((len(mine), width), dtype=np.int64)
     mean, m2 = np.zeros((len(mine), width)), np.zeros((len(mine), width))
     if mine:
-        own_ctx = ctx is None
-        ctx = ctx or _own_context()
-        with ThreadPoolExecutor(io_threads) as pool:
-            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-                rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(paths[i], width), group)))).cuda()
-                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-                c_, m_, s_ = (t.cpu().numpy() for t in b.column_moments(rows))
-                b.close()
+        with _Stage(ctx, io_threads) as stage:
+            for group in stage.groups(mine, frames, max_batch_frames):
+                rows = stage.load([paths[i] for i in group], width)
+                with stage.batch(f0_lengths=[frames[i] for i in group]) as b:
+                    c_, m_, s_ = (t.cpu().numpy() for t in b.column_moments(rows))
                 sel = [at[i] for i in group]
                 cnt[sel], mean[sel], m2[sel] = c_, m_, s_
-        if own_ctx:
-            ctx.close()
     corpus = W.pool_moments(cnt, mean, m2)                            # over frames
     gv = W.pool_moments(np.ones_like(cnt), m2 / np.maximum(cnt, 1), np.zeros_like(m2))     # over utterances
     if world > 1:
@@ -1304,7 +1262,6 @@ def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoic
     utterance with a column without values or a variance that is not finite is reported on stderr and not written
     (:1454-1458).  Rank-sharded by frame count; with resume, utterances whose file is complete are not computed again.
     Returns the list of written (or, with resume, complete) paths of this rank in job order: the script's scp."""
-    import torch
     jobs = [tuple(j) for j in jobs]
     streams = _streams_arg([(d, ws if ws else [[1.0]], m) for d, ws, m in streams])
     ns = len(streams)
@@ -1314,8 +1271,7 @@ def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoic
     frames = _stream_frames(jobs, dims, ns + 2, "%d stream files, a label and one output path" % ns)
     size_out = 12 + 4 * sum(dims)
     have = [resume and _size_is(j[ns + 1], size_out) for j in jobs]
-    todo = [i for i in range(len(jobs)) if not have[i]]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    mine = _my_jobs(frames, lambda i: not have[i])
     written = {i for i in range(len(jobs)) if have[i] and _rank_world()[0] == 0}
 
     def skip(i, why):
@@ -1325,10 +1281,9 @@ def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoic
         skip(i, "no frames")
     mine = [i for i in mine if frames[i] > 0]
     if mine:
-        own_ctx = ctx is None
-        ctx = ctx or _own_context()
-        with ThreadPoolExecutor(io_threads) as pool:
-            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
+        with _Stage(ctx, io_threads) as stage:
+            head = W.htk_header(1, sampling_rate, frame_shift, 4 * sum(dims), 9)
+            for group in stage.groups(mine, frames, max_batch_frames):
                 keep = []
                 for i in group:
                     if silences and jobs[i][ns]:
@@ -1343,16 +1298,14 @@ def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoic
                 if not left:
                     continue
                 off = np.concatenate([[0], np.cumsum([frames[i] for i in group])])
-                index = torch.from_numpy(np.concatenate([keep[k] + off[k] for k in left])).cuda()
-                b = W.WorldBatch(ctx, W.default_params(sampling_rate, 5.0), f0_lengths=[len(keep[k]) for k in left])
+                index = _upload(np.concatenate([keep[k] + off[k] for k in left]))
                 var, cnt = [], []
-                for s_, (dim, _, msd) in enumerate(streams):
-                    parts = list(pool.map(lambda i: _f32(jobs[i][s_], dim), group))
-                    x = torch.from_numpy(np.ascontiguousarray(np.concatenate(parts))).cuda()[index].contiguous()
-                    c_, _, s2 = b.column_moments(x, ignore_value=unvoiced_value if msd else None)
-                    cnt.append(c_.cpu().numpy())
-                    var.append(s2.cpu().numpy() / np.maximum(cnt[-1], 1))
-                b.close()
+                with stage.batch(W.default_params(sampling_rate, 5.0), f0_lengths=[len(keep[k]) for k in left]) as b:
+                    for s_, (dim, _, msd) in enumerate(streams):
+                        x = stage.load([jobs[i][s_] for i in group], dim)[index].contiguous()
+                        c_, _, s2 = b.column_moments(x, ignore_value=unvoiced_value if msd else None)
+                        cnt.append(c_.cpu().numpy())
+                        var.append(s2.cpu().numpy() / np.maximum(cnt[-1], 1))
                 cnt, var = np.concatenate(cnt, axis=1), np.concatenate(var, axis=1).astype(np.float32)
                 for r, k in enumerate(left):
                     i = group[k]
@@ -1361,12 +1314,8 @@ def gv_data_files(jobs, streams, sampling_rate, frame_shift, silences=(), unvoic
                     elif not np.isfinite(var[r]).all():
                         skip(i, "a variance that is not finite")
                     else:
-                        with open(jobs[i][ns + 1], "wb") as f:
-                            f.write(W.htk_header(1, sampling_rate, frame_shift, 4 * sum(dims), 9))
-                            f.write(var[r].tobytes())
+                        stage.submit(_put, jobs[i][ns + 1], var[r], head)
                         written.add(i)
-        if own_ctx:
-            ctx.close()
     return [jobs[i][ns + 1] for i in sorted(written)]
 
 
@@ -1381,51 +1330,27 @@ def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_ba
     The rows go to the device as float32 and are widened there; the result is rounded to float32 once, where the script
     rounds at every pipe.  Rank-sharded by frame count; with resume, utterances whose output has the input's size are
     skipped."""
-    import torch
     jobs = list(jobs)
     width = int(order) + 1
-    frames = []
-    for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 2 or size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not one output path" % (j[0], size, width))
-        frames.append(size // (4 * width))
-
-    def complete(i):
-        try:
-            return os.path.getsize(str(jobs[i][1])) == 4 * width * frames[i]
-        except OSError:
-            return False
-
-    todo = [i for i in range(len(jobs)) if not (resume and complete(i))]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    frames = [_rows_in(j, width, 2, "one output path") for j in jobs]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 4 * width * frames[i])))
     if not mine:
         return 0
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
-            out, status = b.postfilter_mel_cepstrum(rows.double(), alpha, beta, length)
-            host = out.float().cpu().numpy()
-            st = status.cpu().numpy()
-            fo = b.frame_offsets
-            for k, i in enumerate(group):
-                bad = np.nonzero(st[fo[k]:fo[k + 1]])[0]
-                if len(bad):
-                    print("warning: %s: %d frames flagged (first: frame %d, status %d), written as zeros" % (
-                        jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
-                writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][1]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                rows = stage.load([jobs[i][0] for i in group], width)
+                out, status = b.postfilter_mel_cepstrum(rows.double(), alpha, beta, length)
+                host = out.float().cpu().numpy()
+                st = status.cpu().numpy()
+                fo = b.frame_offsets
+                for k, i in enumerate(group):
+                    bad = np.nonzero(st[fo[k]:fo[k + 1]])[0]
+                    if len(bad):
+                        print("warning: %s: %d frames flagged (first: frame %d, status %d), written as zeros" % (
+                            jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
+                stage.put(b, host, [jobs[i][1] for i in group])
+    return stage.frames
 
 
 # ---- modulation-spectrum postfilter (scripts/Training.pl:2950-3038 postfiltering_mspf, :3133-3221 make_mspf) ----------
@@ -1462,30 +1387,20 @@ def mspf_stats_files(jobs, dim, out_dir, name="mgc", silences=(), frame_shift_s=
     jobs = [tuple(j) for j in jobs]
     width, K = int(dim), int(fft_length) // 2 + 1
     silences = tuple(silences)
-    frames = []
-    for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 2 or size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not one label path" % (j[0], size, width))
-        frames.append(size // (4 * width))
-    some = [i for i in range(len(jobs)) if frames[i] > 0]            # a batch holds no utterance without frames
-    mine = [some[k] for k in _my_share([frames[i] for i in some])]
+    frames = [_rows_in(j, width, 2, "one label path") for j in jobs]
+    mine = _my_jobs(frames, lambda i: frames[i] > 0)                 # a batch holds no utterance without frames
     rank, world = _rank_world()
     s1 = torch.zeros(width, K, dtype=torch.float64)
     s2 = torch.zeros(width, K, dtype=torch.float64)
     count = 0
     if mine:
-        own_ctx = ctx is None
-        ctx = ctx or _own_context()
-        with ThreadPoolExecutor(io_threads) as pool:
-            for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-                rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
-                rows = rows.double()
-                lengths = [frames[i] for i in group]
-                b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=lengths)
-                mean = None
+        with _Stage(ctx, io_threads) as stage:
+            for group in stage.groups(mine, frames, max_batch_frames):
+                rows = stage.load([jobs[i][0] for i in group], width).double()
+                lengths, mean = [frames[i] for i in group], None
                 if silences and any(jobs[i][1] for i in group):
-                    mean = b.utterance_means(rows)
+                    with stage.batch(f0_lengths=lengths) as b:
+                        mean = b.utterance_means(rows)
                     fo, keep, kept = b.frame_offsets, [], []
                     for k, i in enumerate(group):
                         if jobs[i][1]:
@@ -1495,20 +1410,17 @@ def mspf_stats_files(jobs, dim, out_dir, name="mgc", silences=(), frame_shift_s=
                             idx = np.arange(frames[i], dtype=np.int64)
                         keep.append(idx + int(fo[k]))
                         kept.append(len(idx))
-                    b.close()
                     some_left = [k for k, n_ in enumerate(kept) if n_ > 0]      # all silence: nothing to count
                     if not some_left:
                         continue
-                    rows = rows[torch.from_numpy(np.concatenate(keep)).cuda()].contiguous()
-                    mean = mean[torch.tensor(some_left, device="cuda")].contiguous()
-                    b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[kept[k] for k in some_left])
-                a1, a2, n = b.modulation_spectrum_stats(rows, frame_length, fft_length, mean)
-                s1 += a1.cpu()
-                s2 += a2.cpu()
-                count += n
-                b.close()
-        if own_ctx:
-            ctx.close()
+                    rows = rows[_upload(np.concatenate(keep))].contiguous()
+                    mean = mean[_upload(np.asarray(some_left, dtype=np.int64))].contiguous()
+                    lengths = [kept[k] for k in some_left]
+                with stage.batch(f0_lengths=lengths) as b:
+                    a1, a2, n = b.modulation_spectrum_stats(rows, frame_length, fft_length, mean)
+                    s1 += a1.cpu()
+                    s2 += a2.cpu()
+                    count += n
     if world > 1:
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()):
@@ -1540,15 +1452,9 @@ def mspf_files(jobs, dim, gen_stats_dir, nat_stats_dir, name="mgc", emphasis=1.0
     gen_stats_dir, nat_stats_dir: where mspf_stats_files wrote <name>_dim<d>.mean / .stdd for generated and natural
     parameters.  The rows are widened on the device and the result is rounded to float32 once.  Rank-sharded by frame
     count; with resume, utterances whose output has the input's size are skipped.  A flagged utterance is reported."""
-    import torch
     jobs = list(jobs)
     width, K = int(dim), int(fft_length) // 2 + 1
-    frames = []
-    for j in jobs:
-        size = os.path.getsize(j[0])
-        if len(j) != 2 or size % (4 * width):
-            raise ValueError("%s: %d bytes are no rows of %d float32, or not one output path" % (j[0], size, width))
-        frames.append(size // (4 * width))
+    frames = [_rows_in(j, width, 2, "one output path") for j in jobs]
 
     def table(directory, which):
         rows = [np.fromfile(_mspf_stat_paths(directory, name, d)[which], dtype=np.float32) for d in range(width)]
@@ -1556,45 +1462,26 @@ def mspf_files(jobs, dim, gen_stats_dir, nat_stats_dir, name="mgc", emphasis=1.0
             raise ValueError("%s: the %s statistics do not hold %d bins per dimension" % (directory, name, K))
         return np.stack(rows).astype(np.float64)
 
-    def complete(i):
-        try:
-            return os.path.getsize(str(jobs[i][1])) == 4 * width * frames[i]
-        except OSError:
-            return False
-
-    todo = [i for i in range(len(jobs)) if not (resume and complete(i))]
-    for i in [i for i in todo if frames[i] == 0]:                     # nothing to filter: the output is empty as well
+    todo = [not (resume and _size_is(j[1], 4 * width * frames[i])) for i, j in enumerate(jobs)]
+    for i in [i for i in range(len(jobs)) if todo[i] and frames[i] == 0]:    # nothing to filter: the output is empty as well
         if _rank_world()[0] == 0:
             open(jobs[i][1], "wb").close()
-    todo = [i for i in todo if frames[i] > 0]
-    mine = [todo[k] for k in _my_share([frames[i] for i in todo])]
+    mine = _my_jobs(frames, lambda i: todo[i] and frames[i] > 0)
     if not mine:
         return 0
     tabs = (table(gen_stats_dir, 0), table(gen_stats_dir, 1), table(nat_stats_dir, 0), table(nat_stats_dir, 1))
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            b = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[frames[i] for i in group])
-            rows = torch.from_numpy(np.concatenate(list(pool.map(lambda i: _f32(jobs[i][0], width), group)))).cuda()
-            out, status = b.postfilter_modulation_spectrum(rows.double(), *tabs, emphasis, frame_length, fft_length)
-            host = out.float().cpu().numpy()
-            st = status.cpu().numpy()
-            fo = b.frame_offsets
-            for k, i in enumerate(group):
-                if st[k]:
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                rows = stage.load([jobs[i][0] for i in group], width)
+                out, status = b.postfilter_modulation_spectrum(rows.double(), *tabs, emphasis, frame_length, fft_length)
+                host = out.float().cpu().numpy()
+                st = status.cpu().numpy()
+                for k in np.nonzero(st)[0]:
                     print("warning: %s: flagged (status %d), the affected columns written as zeros" % (
-                        jobs[i][0], int(st[k])), file=sys.stderr)
-                writes.append(pool.submit(np.ascontiguousarray(host[fo[k]:fo[k + 1]]).tofile, jobs[i][1]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+                        jobs[group[k]][0], int(st[k])), file=sys.stderr)
+                stage.put(b, host, [jobs[i][1] for i in group])
+    return stage.frames
 
 
 # ---- vibrato (data/scripts/Extract.py, data/Makefile.in:215) --------------------------------------------------------
@@ -1613,8 +1500,6 @@ def read_label_segments(mono_path, full_path, frame_period, n_frames):
     Extract.py reads them (:63-84, :176-187): three fields per line, times in units of 100 ns divided by 10e3 (ms),
     frames = floor(time / frame_period) clamped to [0, n_frames], the note from the `/E:<note>]` field of the
     full-context label."""
-    import math
-    import re
     with open(mono_path) as f:
         mono = f.read().split("\n")
     with open(full_path) as f:
@@ -1638,36 +1523,20 @@ def vibrato_files(jobs, frame_period, fs=48000, ctx=None, max_batch_frames=MAX_B
     """jobs: [(lf0_file, mono_label, full_label, vib_out)].  What `Extract.py <base> <frame_period>` does for every
     job: the lf0 file (float32 log f0, one column) is REWRITTEN with two columns (log f0, log(f0 - note + 500)), the
     vib file gets (log depth, log period) per frame.  fs only labels the batch (nothing here depends on it)."""
-    import torch
     jobs = list(jobs)
     frames = [os.path.getsize(j[0]) // 4 for j in jobs]
     mine = _my_share(frames)
-    own_ctx = ctx is None
-    ctx = ctx or _own_context()
-    done = 0
-    with ThreadPoolExecutor(io_threads) as pool:
-        writes = []
-        for group in _batches(sorted(mine, key=lambda i: -frames[i]), frames, max_batch_frames):
-            T = [frames[i] for i in group]
-            b = W.WorldBatch(ctx, W.default_params(fs, frame_period), f0_lengths=T)
-            lf0s = list(pool.map(lambda i: _f32(jobs[i][0]), group))
-            segs = [read_label_segments(jobs[i][1], jobs[i][2], frame_period, frames[i]) for i in group]
-            lf0 = torch.from_numpy(np.ascontiguousarray(np.concatenate(lf0s))).cuda()
-            vib, lf2, too_long = b.vibrato(lf0, segs)
-            if too_long:
-                print("warning: %d voiced run(s) longer than 3072 frames left without vibrato" % too_long, file=sys.stderr)
-            vh, lh = vib.cpu().numpy(), lf2.cpu().numpy()
-            fo = b.frame_offsets
-            for k, i in enumerate(group):
-                writes.append(pool.submit(np.ascontiguousarray(lh[fo[k]:fo[k + 1]]).tofile, jobs[i][0]))
-                writes.append(pool.submit(np.ascontiguousarray(vh[fo[k]:fo[k + 1]]).tofile, jobs[i][3]))
-            done += int(b.total_frames)
-            b.close()
-        for w_ in writes:
-            w_.result()
-    if own_ctx:
-        ctx.close()
-    return done
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames, W.default_params(fs, frame_period)):
+            with batch as b:
+                segs = [read_label_segments(jobs[i][1], jobs[i][2], frame_period, frames[i]) for i in group]
+                vib, lf2, too_long = b.vibrato(stage.load([jobs[i][0] for i in group]), segs)
+                if too_long:
+                    print("warning: %d voiced run(s) longer than 3072 frames left without vibrato" % too_long, file=sys.stderr)
+                vh, lh = vib.cpu().numpy(), lf2.cpu().numpy()
+                stage.put(b, lh, [jobs[i][0] for i in group])
+                stage.put(b, vh, [jobs[i][3] for i in group])
+    return stage.frames
 
 
 def _read_scp(path, n=4):
