@@ -51,6 +51,9 @@ scripts/Training.pl:1402-1491).  ffi_files() / `ffi` writes the other side of th
 input rows from aligned labels and a question config (make_train_data_dnn / make_gen_data_dnn, :1677-1723:
 data/scripts/makefeature.pl and x2x +af), which `dnn-train`, `dnn-forward` and `trj-eval` read.
 
+generate_files() / `generate` (generate.py) is the way back in one pass: `ffi`, `dnn-forward`, `gen-param`, the postfilter
+and `synth` on one device-resident batch, labels in and wavs out, with the staged commands' bytes.
+
 There is no CPU path: without a HIP device the library call fails.
 """
 from __future__ import annotations
@@ -1554,6 +1557,40 @@ def parse_stream(text):
     return int(dim), [w for w in wins.split(",") if w], msd not in ("0", "")
 
 
+def parse_named_stream(text):
+    """`name:dim:msd:win0,win1,...` -> (name, dim, [window files], msd): parse_stream behind the stream's name, which
+    `generate` needs (mgc, lf0 and bap feed synthesis), e.g. lf0:1:1:lf0.win1,lf0.win2,lf0.win3."""
+    name, rest = text.split(":", 1)
+    if not name:
+        raise ValueError("a stream needs a name: " + text)
+    return (name,) + parse_stream(rest)
+
+
+def generate_arguments(ap, a):
+    """generate_files' keyword arguments from `generate`'s parsed command line (ap.error where the postfilter's own
+    options are missing)."""
+    post = None
+    if a.postfilter == "mcp":
+        post = ("mcp", a.beta, a.length)
+    elif a.postfilter == "mspf":
+        if not (a.gen_stats and a.nat_stats):
+            ap.error("--postfilter mspf needs --gen-stats and --nat-stats")
+        post = ("mspf", a.gen_stats, a.nat_stats, a.emphasis, a.mspf_frame_length, a.mspf_fft_length)
+    if a.frame_shift < 1:
+        ap.error("--frame-shift must be positive")
+    return dict(config=a.config, frame_shift=a.frame_shift, model=a.model, spkr=a.spkr, streams=a.stream, fs=a.fs,
+                frame_period=a.frame_period, fft_size=a.fft_size, alpha=a.alpha, postfilter=post, edge=a.edge,
+                unvoiced_value=a.unvoiced_value, keep_dir=a.keep_dir, max_batch_frames=a.max_batch_frames, resume=a.resume)
+
+
+def __getattr__(name):
+    # the chain over the drivers above lives beside them (generate.py imports this module)
+    if name in ("Generator", "generate_files"):
+        from . import generate
+        return getattr(generate, name)
+    raise AttributeError(name)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m hts-train-world_amd.recipe", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -1682,7 +1719,39 @@ def main(argv=None):
     p.add_argument("--config", required=True, help="the question config (qconf)")
     p.add_argument("--frame-shift", type=int, required=True, help="one frame in the label's time unit of 100 ns (50000 for 5 ms)")
     p.add_argument("--resume", action="store_true", help="skip utterances whose ffi file is already complete")
+    p = sub.add_parser("generate", help="aligned labels to wavs in one pass per batch: ffi, dnn-forward, gen-param, the "
+                       "postfilter and synth without a file between them")
+    p.add_argument("--scp", required=True, help="job list: the label file, then the wav to write")
+    p.add_argument("--config", required=True, help="the question config (qconf)")
+    p.add_argument("--frame-shift", type=int, required=True, help="one frame in the label's time unit of 100 ns (50000 for 5 ms)")
+    p.add_argument("--model", required=True, help="the .npz of training.AcousticModel.save")
+    p.add_argument("--spkr", type=int, default=None, help="speaker index (default: the last, as DNNSynthesis.py)")
+    p.add_argument("--stream", action="append", required=True, type=parse_named_stream, metavar="NAME:DIM:MSD:WIN0,WIN1,...",
+                   help="one per stream in the ffo row's order; mgc, lf0 and bap feed synthesis, any other is generated only")
+    p.add_argument("--fs", type=int, required=True)
+    p.add_argument("--frame-period", type=float, default=5.0)
+    p.add_argument("--fft-size", type=int, required=True)
+    p.add_argument("--alpha", type=float, required=True, help="frequency warping of the mgc stream (the mcp postfilter's)")
+    p.add_argument("--postfilter", default="none", choices=("none", "mcp", "mspf"))
+    p.add_argument("--beta", type=float, default=1.4, help="mcp: the postfiltering coefficient (pf_mcp)")
+    p.add_argument("--length", type=int, default=4096, help="mcp: bins of the energy sums (IMPLEN)")
+    p.add_argument("--gen-stats", default=None, help="mspf: directory of the generated parameters' statistics")
+    p.add_argument("--nat-stats", default=None, help="mspf: directory of the natural parameters' statistics")
+    p.add_argument("--emphasis", type=float, default=1.0, help="mspf: mspfe")
+    p.add_argument("--mspf-frame-length", type=int, default=25, help="mspf: mspfLength")
+    p.add_argument("--mspf-fft-length", type=int, default=64, help="mspf: mspfFFTLen")
+    p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
+    p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
+    p.add_argument("--keep-dir", default=None, help="also leave the staged commands' files here: <base>.ffi, .ffo, .var, "
+                   "one file per stream and .p_mgc")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose wav is already complete")
+    p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
     a = ap.parse_args(argv)
+    if a.cmd == "generate":
+        from . import generate
+        n, flagged = generate.generate_files(_read_scp(a.scp, 2), **generate_arguments(ap, a))
+        print("complete. %d frames, %d utterances flagged" % (n, len(flagged)))
+        return 0
     if a.cmd == "ffi":
         if a.frame_shift < 1:
             ap.error("--frame-shift must be positive")
