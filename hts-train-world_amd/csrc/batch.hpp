@@ -39,9 +39,9 @@ struct NoCopy {                               // base of what frees or restores 
 };
 
 // Device blocks freed together with their owner: alloc() records what it hands out.  Every stage keeps the state it
-// builds on first use in one such struct, private to its .hip file and owned by the batch (Batch::dio ... vibrato);
-// a set-up builds it in a local and moves it into the batch only once every allocation, copy, launch and
-// synchronisation has succeeded, so a failure leaves nothing half-built behind.
+// builds in one such struct, private to its .hip file and owned by the batch (Batch::dio ... ffi); a set-up builds it
+// in a local and moves it into the batch only once every allocation, copy, launch and synchronisation has succeeded,
+// so a failure leaves nothing half-built behind.  A stage whose needs vary from call to call keeps it with grow_ws().
 struct StageWs : NoCopy {
   std::vector<void*> owned;
   template <class T> hipError_t alloc(T** p, size_t bytes) {
@@ -51,6 +51,44 @@ struct StageWs : NoCopy {
   }
   virtual ~StageWs() {
     for (void* p : owned) dev_free(p);
+  }
+};
+
+// The workspace of a stage that may need a larger one than the batch holds (a wider band, more rows, a training pass
+// after a forward pass).  The one rule, for every such stage:
+//   * a workspace that exists and fits -- fits(present) -- is used as it is;
+//   * otherwise one that exists is released first, after a wait for `st`: an earlier call's kernels, queued on the
+//     stream this call was given, may still use it.  The two never exist side by side;
+//   * the new one is built in a local -- build(fresh) -> WM_OK -- and published only when every allocation has succeeded;
+//   * a failed build returns its error and leaves the slot empty: the next call builds afresh.  (A failed wait returns
+//     its error with the slot as it was.)
+// `Held` is what the slot may hold where that is a base of Ws (the training pass finds the forward pass's DnnWs).
+template <class Ws, class Held = Ws, class Fits, class Build>
+int grow_ws(std::unique_ptr<StageWs>& slot, hipStream_t st, Ws*& out, Fits fits, Build build) {
+  out = nullptr;
+  if (slot) {
+    if (fits(static_cast<const Held&>(*slot))) {
+      out = static_cast<Ws*>(slot.get());
+      return WM_OK;
+    }
+    if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
+    slot.reset();
+  }
+  std::unique_ptr<Ws> fresh(new Ws());
+  if (const int rc = build(*fresh)) return rc;
+  out = fresh.get();
+  slot = std::move(fresh);
+  return WM_OK;
+}
+
+// Byte offsets of the sections of one allocation, 256-byte aligned and handed out one after another (an empty one
+// still takes a slot); `at` is the size so far.
+struct Sections {
+  size_t at = 0;
+  size_t operator()(size_t bytes) {
+    const size_t o = at;
+    at = (at + (bytes ? bytes : 8) + 255) & ~(size_t)255;
+    return o;
   }
 };
 
@@ -109,7 +147,9 @@ struct PulseInfo : NoCopy {
 // Driven by one thread at a time (with its batches): table, scratch, events and pulse counters are shared by all its calls.
 struct Context {
   int device = 0;
-  hipStream_t stream = nullptr;      // the CALLER's (CreateContext / SetStream); what work runs on is an argument, `st`
+  hipStream_t stream = nullptr;      // the CALLER's (CreateContext / SetStream), read by capi.cpp alone (and by
+                                     // label_set_destroy, which has no caller to take one from): every launcher is
+                                     // handed the stream it queues on as its argument `st`
   int num_cu = 256;
   int frame_grid = 256 * 8;          // upper bound on the workgroups of a grid-stride per-frame kernel
   int oversub = 6;                   // workgroups per resident slot of those kernels (persistent_grid): measured on
@@ -250,15 +290,18 @@ struct Batch {
   ~Batch() { dev_free(d_arena); }
 };
 
-// kernel launchers (one translation unit each)
-int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0);
-int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_out,
-                     double f0_lower = 0.0);
-int launch_cheaptrick(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_sp);
-int launch_d4c(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
-int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap);
-int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y);
-// the stages behind launch_d4c / launch_synthesis on the stream `st` they are given (context.cpp, the drop-in Synthesis())
+// Kernel launchers (one translation unit each).  Whatever queues device work takes the stream it queues on, `st`,
+// directly after its Batch& / Context&: the capi.cpp entry points pass the caller's (Context::stream), the one-call forms
+// fork from `st` and join back into it, and a table or workspace built inside a stage is launched on and waited for on
+// the `st` of the call that builds it.
+int launch_dio(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0);
+int launch_harvest(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0);
+int launch_stonemask(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_out);
+int launch_cheaptrick(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_sp);
+int launch_d4c(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
+int launch_analyze(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap);
+int launch_synthesis(Batch& b, hipStream_t st, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y);
+// the stages behind launch_d4c / launch_synthesis (context.cpp, the drop-in Synthesis())
 int d4c_prepare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0);
 int d4c_rare(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
 int d4c_run(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);
@@ -266,27 +309,28 @@ int synthesis_prepare(Batch& b, hipStream_t st, const double* d_f0, double* d_y)
 int synthesis_begin(Batch& b, hipStream_t st, const double* d_f0, double* d_y);      // the f0-only kernels, queued
 int synthesis_prepare_wait(Batch& b, hipStream_t st);                                 // their host round trip
 int synthesis_render(Batch& b, hipStream_t st, const double* d_sp, const double* d_ap, double* d_y);
-int launch_analyze_synthesize(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap,
-                              double* d_y);
-int launch_utterance_status(Batch& b, const double* d_x, const double* d_f0, const double* d_sp, const double* d_ap,
-                            int* d_status);
-int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const int* seg_start, const int* seg_end,
-                   const double* seg_pitch, float* d_vib, float* d_lf0_out, int* n_too_long);
-int launch_pcm16_to_samples(Batch& b, const int16_t* d_pcm, double* d_x);
-int launch_samples_to_pcm16(Batch& b, const double* d_y, int16_t* d_pcm);
+int launch_analyze_synthesize(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
+                              double* d_ap, double* d_y);
+int launch_utterance_status(Batch& b, hipStream_t st, const double* d_x, const double* d_f0, const double* d_sp,
+                            const double* d_ap, int* d_status);
+int launch_vibrato(Batch& b, hipStream_t st, const float* d_lf0, const int* seg_utt_off, const int* seg_start,
+                   const int* seg_end, const double* seg_pitch, float* d_vib, float* d_lf0_out, int* n_too_long);
+int launch_pcm16_to_samples(Batch& b, hipStream_t st, const int16_t* d_pcm, double* d_x);
+int launch_samples_to_pcm16(Batch& b, hipStream_t st, const double* d_y, int16_t* d_pcm);
 int codec_num_aperiodicities(int fs);
-int launch_code_spectral_envelope(Batch& b, const double* d_sp, int ndim, double* d_coded);
-int launch_decode_spectral_envelope(Batch& b, const double* d_coded, int ndim, double* d_sp);
-int launch_code_aperiodicity(Batch& b, const double* d_ap, double* d_coded);
-int launch_decode_aperiodicity(Batch& b, const double* d_coded, double* d_ap);
+int launch_code_spectral_envelope(Batch& b, hipStream_t st, const double* d_sp, int ndim, double* d_coded);
+int launch_decode_spectral_envelope(Batch& b, hipStream_t st, const double* d_coded, int ndim, double* d_sp);
+int launch_code_aperiodicity(Batch& b, hipStream_t st, const double* d_ap, double* d_coded);
+int launch_decode_aperiodicity(Batch& b, hipStream_t st, const double* d_coded, double* d_ap);
 int check_compose_cmp(int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
                       const double* const* const* windows, const int* const* window_sizes, const float* d_out);
-int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
-                       const double* const* const* windows, const int* const* window_sizes, float* d_out);
-int launch_recipe_features(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, int spec_dim,
-                           int ap_dim, float* d_lf0, float* d_mgc, float* d_bap);
-int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const float* d_bap, int spec_dim,
-                         int ap_dim, double* d_f0, double* d_sp, double* d_ap);
+int launch_compose_cmp(Batch& b, hipStream_t st, int n_streams, const float* const* d_data, const int* dims,
+                       const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                       float* d_out);
+int launch_recipe_features(Batch& b, hipStream_t st, const double* d_f0, const double* d_sp, const double* d_ap,
+                           int spec_dim, int ap_dim, float* d_lf0, float* d_mgc, float* d_bap);
+int launch_recipe_decode(Batch& b, hipStream_t st, const float* d_lf0, const float* d_mgc, const float* d_bap,
+                         int spec_dim, int ap_dim, double* d_f0, double* d_sp, double* d_ap);
 int check_mel_cepstrum(const Batch& b, const double* d_spec, const WorldMi355McepOption& opt, const double* d_mc);
 int launch_mel_cepstrum(Batch& b, hipStream_t st, const double* d_spec, const WorldMi355McepOption& opt, double* d_mc,
                         int* d_status);

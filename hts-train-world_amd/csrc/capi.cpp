@@ -29,7 +29,6 @@
 namespace wm {
 const char* last_error();
 void set_error(const char* msg);
-int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0);
 #ifdef WM_PHASE
 int phase_read_d4c(unsigned long long* out32);
 int phase_read_cheaptrick(unsigned long long* out32);
@@ -53,6 +52,15 @@ static WorldMi355ErrorHandler error_handler(void** user) {
 
 struct WorldMi355Context { Context c; };
 struct WorldMi355Batch { Batch b; };
+
+// How every batched entry point ends: a NULL batch is WM_ERR_BAD_ARG; otherwise on the batch's device, the launcher
+// with the batch and its context's stream, the caller's.  Host-only checks (check_*) come before it, so a refused
+// argument set makes no device call, hipGetDevice included.
+template <class Launch, class... Args> static int on_batch(WorldMi355Batch* b, Launch launch, Args&&... args) {
+  if (!b) return WM_ERR_BAD_ARG;
+  OnDevice dev_(*b->b.ctx);
+  return launch(b->b, b->b.ctx->stream, std::forward<Args>(args)...);
+}
 
 template <typename T> static int alloc_items(T** p, size_t count) {
   *p = nullptr;
@@ -187,12 +195,11 @@ int WorldMi355CreateBatch(WorldMi355Context* h, const WorldMi355Params* params, 
   // copies were most of its cost).  Layout: 256-byte aligned sections; the first `init_bytes` are initialised
   // from a host image, the rest is scratch.
   const size_t n1 = (size_t)n_utt + 1, nf = (size_t)b.total_f;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = (at + (bytes ? bytes : 8) + 255) & ~(size_t)255; return o; };
+  Sections take;
   const size_t o_xoff = take(8 * n1), o_foff = take(8 * n1), o_yoff = take(8 * n1);
   const size_t o_xlen = take(4 * (size_t)n_utt), o_flen = take(4 * (size_t)n_utt), o_ylen = take(4 * (size_t)n_utt);
   const size_t o_futt = take(4 * nf);
-  const size_t init_bytes = at;
+  const size_t init_bytes = take.at;
   const size_t o_rng = take(4 * nf), o_rng2 = take(4 * nf), o_ap0 = take(8 * nf), o_f0t = take(8 * nf);
   const size_t o_perm = take(4 * nf), o_pcnt = take(4 * (nf / 1024 + 2)), o_pn = take(4 * 4);
   const size_t o_rng_d = take(4 * nf), o_perm_d = take(4 * nf), o_pcnt_d = take(4 * (nf / 1024 + 2)), o_pn_d = take(4 * 4);
@@ -209,7 +216,7 @@ int WorldMi355CreateBatch(WorldMi355Context* h, const WorldMi355Params* params, 
       for (int64_t i = b.f_off[u]; i < b.f_off[u + 1]; ++i) fu[i] = u;
   }
   unsigned char* base = nullptr;
-  int rc = wm_check(wm::dev_alloc(&base, at));
+  int rc = wm_check(wm::dev_alloc(&base, take.at));
   if (!rc) b.d_arena = base;                     // freed with the batch
   if (!rc) rc = wm_check(hipMemcpy(base, img.data(), init_bytes, hipMemcpyHostToDevice));
   if (rc) {
@@ -245,55 +252,44 @@ const int64_t* WorldMi355BatchFrameOffsets(const WorldMi355Batch* b) { return b-
 const int64_t* WorldMi355BatchOutputOffsets(const WorldMi355Batch* b) { return b->b.y_off.data(); }
 
 int WorldMi355Dio(WorldMi355Batch* b, const double* x, double* t, double* f0) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_dio(b->b, x, t, f0);
+  return on_batch(b, launch_dio, x, t, f0);
 }
 int WorldMi355StoneMask(WorldMi355Batch* b, const double* x, const double* t, const double* f0,
                         double* refined_f0) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_stonemask(b->b, x, t, f0, refined_f0);
+  return on_batch(b, launch_stonemask, x, t, f0, refined_f0);
 }
 int WorldMi355CheapTrick(WorldMi355Batch* b, const double* x, const double* t, const double* f0,
                          double* sp) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_cheaptrick(b->b, x, t, f0, sp);
+  return on_batch(b, launch_cheaptrick, x, t, f0, sp);
 }
 int WorldMi355D4C(WorldMi355Batch* b, const double* x, const double* t, const double* f0, double* ap) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_d4c(b->b, x, t, f0, ap);
+  return on_batch(b, launch_d4c, x, t, f0, ap);
 }
 int WorldMi355Synthesis(WorldMi355Batch* b, const double* f0, const double* sp, const double* ap,
                         double* y) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_synthesis(b->b, f0, sp, ap, y);
+  return on_batch(b, launch_synthesis, f0, sp, ap, y);
 }
 int WorldMi355GetNumberOfAperiodicities(int fs) { return codec_num_aperiodicities(fs); }
 int WorldMi355CodeSpectralEnvelope(WorldMi355Batch* b, const double* sp, int number_of_dimensions, double* coded) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_code_spectral_envelope(b->b, sp, number_of_dimensions, coded);
+  return on_batch(b, launch_code_spectral_envelope, sp, number_of_dimensions, coded);
 }
 int WorldMi355DecodeSpectralEnvelope(WorldMi355Batch* b, const double* coded, int number_of_dimensions,
                                      double* sp) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_decode_spectral_envelope(b->b, coded, number_of_dimensions, sp);
+  return on_batch(b, launch_decode_spectral_envelope, coded, number_of_dimensions, sp);
 }
 int WorldMi355CodeAperiodicity(WorldMi355Batch* b, const double* ap, double* coded) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_code_aperiodicity(b->b, ap, coded);
+  return on_batch(b, launch_code_aperiodicity, ap, coded);
 }
 int WorldMi355DecodeAperiodicity(WorldMi355Batch* b, const double* coded, double* ap) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_decode_aperiodicity(b->b, coded, ap);
+  return on_batch(b, launch_decode_aperiodicity, coded, ap);
 }
 int WorldMi355RecipeFeatures(WorldMi355Batch* b, const double* f0, const double* sp, const double* ap,
                              int spec_dim, int ap_dim, float* lf0, float* mgc, float* bap) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_recipe_features(b->b, f0, sp, ap, spec_dim, ap_dim, lf0, mgc, bap);
+  return on_batch(b, launch_recipe_features, f0, sp, ap, spec_dim, ap_dim, lf0, mgc, bap);
 }
 int WorldMi355RecipeDecode(WorldMi355Batch* b, const float* lf0, const float* mgc, const float* bap, int spec_dim,
                            int ap_dim, double* f0, double* sp, double* ap) {
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_recipe_decode(b->b, lf0, mgc, bap, spec_dim, ap_dim, f0, sp, ap);
+  return on_batch(b, launch_recipe_decode, lf0, mgc, bap, spec_dim, ap_dim, f0, sp, ap);
 }
 void WorldMi355DefaultMcepOption(WorldMi355McepOption* o) {                     // SPTK's mcep / mgcep defaults
   if (!o) return;
@@ -311,8 +307,7 @@ int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const Worl
                           int* status) {
   if (!b || !opt) return WM_ERR_BAD_ARG;
   if (const int rc = check_mel_cepstrum(b->b, spectrum, *opt, mc)) return rc;   // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mel_cepstrum(b->b, b->b.ctx->stream, spectrum, *opt, mc, status);
+  return on_batch(b, launch_mel_cepstrum, spectrum, *opt, mc, status);
 }
 void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* o) {                 // SPTK's mgc2sp defaults, ln |H| out
   if (!o) return;
@@ -325,16 +320,13 @@ int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const 
                                     double* spectrum, double* phase, int* status) {
   if (!b || !opt) return WM_ERR_BAD_ARG;
   if (const int rc = check_mgc2sp(b->b, mc, *opt, spectrum)) return rc;         // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mgc2sp(b->b, b->b.ctx->stream, mc, *opt, spectrum, phase, status);
+  return on_batch(b, launch_mgc2sp, mc, *opt, spectrum, phase, status);
 }
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {
   if (const int rc = check_compose_cmp(n_streams, streams, dims, n_windows, windows, window_sizes, out)) return rc;
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_compose_cmp(b->b, n_streams, streams, dims, n_windows, windows, window_sizes, out);
+  return on_batch(b, launch_compose_cmp, n_streams, streams, dims, n_windows, windows, window_sizes, out);
 }
 void WorldMi355DefaultMlpgOption(WorldMi355MlpgOption* o) {                     // SPTK's mlpg: taps beyond the ends dropped
   if (!o) return;
@@ -351,9 +343,8 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
   if (!b) return WM_ERR_BAD_ARG;
   if (const int rc = check_mlpg(n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, opt, out))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mlpg(b->b, b->b.ctx->stream, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows,
-                     window_sizes, msd, *opt, out, status);
+  return on_batch(b, launch_mlpg, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, msd,
+                  *opt, out, status);
 }
 void WorldMi355DefaultTrajectoryOption(WorldMi355TrajectoryOption* o) {         // DNNDefine.py:248-249
   if (!o) return;
@@ -372,10 +363,8 @@ int WorldMi355TrajectoryCost(WorldMi355Batch* b, int n_streams, const float* con
   if (const int rc = check_trj(n_streams, pred, obs, ld, var, gv_var, dims, n_windows, windows, window_sizes, msd_pred,
                                msd_obs, msd_var, opt, cost, grad_pred, grad_msd, ld_grad))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_trj(b->b, b->b.ctx->stream, n_streams, pred, obs, ld, var, gv_var, dims, n_windows, windows,
-                    window_sizes, msd_pred, msd_obs, msd_var, *opt, cost, c, grad_pred, grad_msd, ld_grad, grad_var,
-                    status);
+  return on_batch(b, launch_trj, n_streams, pred, obs, ld, var, gv_var, dims, n_windows, windows, window_sizes,
+                  msd_pred, msd_obs, msd_var, *opt, cost, c, grad_pred, grad_msd, ld_grad, grad_var, status);
 }
 int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const float* x, int64_t ld_x,
                                    const int* spkr, float* out, int64_t ld_out, const float* obs, int64_t ld_obs,
@@ -383,8 +372,7 @@ int WorldMi355AcousticModelForward(WorldMi355Batch* b, const WorldMi355AcousticM
   if (!b) return WM_ERR_BAD_ARG;
   if (const int rc = check_dnn(b->b.n_utt, m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_dnn(b->b, b->b.ctx->stream, *m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, status);
+  return on_batch(b, launch_dnn, *m, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, status);
 }
 int WorldMi355AcousticModelTrainForward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
                                         const float* x, int64_t ld_x, const int* spkr, float* out, int64_t ld_out,
@@ -394,9 +382,8 @@ int WorldMi355AcousticModelTrainForward(WorldMi355Batch* b, const WorldMi355Acou
   if (const int rc = check_dnn_train_forward(b->b.n_utt, m, drop, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, grad_out,
                                              ld_grad, grad_var))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_dnn_train_forward(b->b, b->b.ctx->stream, *m, drop, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, grad_out,
-                                  ld_grad, grad_var, status);
+  return on_batch(b, launch_dnn_train_forward, *m, drop, x, ld_x, spkr, out, ld_out, obs, ld_obs, cost, grad_out,
+                  ld_grad, grad_var, status);
 }
 int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355AcousticModel* m, const WorldMi355Dropout* drop,
                                     const float* x, int64_t ld_x, const int* spkr, const float* grad_out, int64_t ld_grad,
@@ -406,9 +393,8 @@ int WorldMi355AcousticModelBackward(WorldMi355Batch* b, const WorldMi355Acoustic
   if (const int rc = check_dnn_backward(b->b.n_utt, m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
                                         grad_spkr_weights))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_dnn_backward(b->b, b->b.ctx->stream, *m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
-                             grad_spkr_weights, status);
+  return on_batch(b, launch_dnn_backward, *m, drop, x, ld_x, spkr, grad_out, ld_grad, grad_weights, grad_biases,
+                  grad_spkr_weights, status);
 }
 void WorldMi355DefaultOptimizerOption(int rule, WorldMi355OptimizerOption* o) {   // tf.train.*Optimizer's defaults (TF 1.x)
   if (!o) return;
@@ -441,8 +427,7 @@ int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const 
                                     double* gain, int* status) {
   if (!b) return WM_ERR_BAD_ARG;
   if (const int rc = check_mcpf(mc, opt, out)) return rc;                       // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mcpf(b->b, b->b.ctx->stream, mc, *opt, out, gain, status);
+  return on_batch(b, launch_mcpf, mc, *opt, out, gain, status);
 }
 void WorldMi355DefaultMspfOption(WorldMi355MspfOption* o) {                     // the recipe's $mspfLength, $mspfFFTLen, $mspfe{'mgc'}
   if (!o) return;
@@ -453,46 +438,34 @@ void WorldMi355DefaultMspfOption(WorldMi355MspfOption* o) {                     
 int WorldMi355MspfSegmentFrames(void) { return mspf_segment_frames(); }
 int WorldMi355ColumnMeans(WorldMi355Batch* b, const double* x, int dim, double* mean) {
   if (const int rc = check_column_means(x, dim, mean)) return rc;               // refused before any device call
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_column_means(b->b, b->b.ctx->stream, x, dim, mean);
+  return on_batch(b, launch_column_means, x, dim, mean);
 }
 int WorldMi355ModulationSpectrumPostfilter(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
                                            const double* mean_gen, const double* std_gen, const double* mean_nat,
                                            const double* std_nat, double* out, int* status) {
   if (const int rc = check_mspf(x, dim, opt, mean_gen, std_gen, mean_nat, std_nat, out)) return rc;
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mspf(b->b, b->b.ctx->stream, x, dim, *opt, mean_gen, std_gen, mean_nat, std_nat, out, status);
+  return on_batch(b, launch_mspf, x, dim, *opt, mean_gen, std_gen, mean_nat, std_nat, out, status);
 }
 int WorldMi355ModulationSpectrumStats(WorldMi355Batch* b, const double* x, int dim, const WorldMi355MspfOption* opt,
                                       const double* mean, double* sum, double* sumsq, int64_t* n_frames) {
   if (const int rc = check_mspf_stats(x, dim, opt, sum, sumsq, n_frames)) return rc;
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_mspf_stats(b->b, b->b.ctx->stream, x, dim, *opt, mean, sum, sumsq, n_frames);
+  return on_batch(b, launch_mspf_stats, x, dim, *opt, mean, sum, sumsq, n_frames);
 }
 int WorldMi355InterpolateGaps(WorldMi355Batch* b, const float* x, int dim, double ignore_value, float* out, float* voiced,
                                int* status) {
   if (const int rc = check_interpolate_gaps(x, dim, ignore_value, out)) return rc;   // refused before any device call
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_interpolate_gaps(b->b, b->b.ctx->stream, x, dim, ignore_value, out, voiced, status);
+  return on_batch(b, launch_interpolate_gaps, x, dim, ignore_value, out, voiced, status);
 }
 int WorldMi355ComposeFfo(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
                          const float* const* msd, float* out) {
   if (const int rc = check_compose_ffo(n_streams, streams, dims, n_windows, windows, window_sizes, out)) return rc;
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_compose_ffo(b->b, b->b.ctx->stream, n_streams, streams, dims, n_windows, windows, window_sizes, msd, out);
+  return on_batch(b, launch_compose_ffo, n_streams, streams, dims, n_windows, windows, window_sizes, msd, out);
 }
 int WorldMi355ColumnMoments(WorldMi355Batch* b, const float* x, int64_t ld, int width, const double* ignore_value,
                             int64_t* count, double* mean, double* m2) {
   if (const int rc = check_column_moments(x, ld, width, ignore_value, count, mean, m2)) return rc;
-  if (!b) return WM_ERR_BAD_ARG;
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_column_moments(b->b, b->b.ctx->stream, x, ld, width, ignore_value, count, mean, m2);
+  return on_batch(b, launch_column_moments, x, ld, width, ignore_value, count, mean, m2);
 }
 int WorldMi355CreateLabelFeatureSet(WorldMi355Context* h, int n_features, const WorldMi355LabelFeature* features,
                                     WorldMi355LabelFeatureSet** out) {
@@ -518,9 +491,8 @@ int WorldMi355LabelFeatures(WorldMi355Batch* b, const WorldMi355LabelFeatureSet*
   const LabelSet* s = reinterpret_cast<const LabelSet*>(set);
   if (const int rc = check_label_features(b->b, s, line_off, start, end, state_index, name, state_level, out, ld_out))
     return rc;                                                                  // refused before any device call
-  OnDevice dev_(b->b.ctx[0]);
-  return launch_label_features(b->b, b->b.ctx->stream, *s, line_off, start, end, state_index, name, state_level, out,
-                               ld_out, status);
+  return on_batch(b, launch_label_features, *s, line_off, start, end, state_index, name, state_level, out, ld_out,
+                  status);
 }
 void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_samples, int bytes_per_frame,
                          int htk_type, unsigned char out12[12]) {              // addhtkheader.pl:60-75
@@ -532,36 +504,29 @@ void WorldMi355HtkHeader(int n_frames, int sampling_rate, int frame_shift_sample
   memcpy(out12 + 10, &d, 2);
 }
 int WorldMi355SamplesFromPcm16(WorldMi355Batch* b, const int16_t* pcm, double* x) {
-  OnDevice dev_(b->b.ctx[0]);
-  return wm::launch_pcm16_to_samples(b->b, pcm, x);
+  return on_batch(b, launch_pcm16_to_samples, pcm, x);
 }
 int WorldMi355SamplesToPcm16(WorldMi355Batch* b, const double* y, int16_t* pcm) {
-  OnDevice dev_(b->b.ctx[0]);
-  return wm::launch_samples_to_pcm16(b->b, y, pcm);
+  return on_batch(b, launch_samples_to_pcm16, y, pcm);
 }
 int WorldMi355Harvest(WorldMi355Batch* b, const double* x, double* t, double* f0) {
-  OnDevice dev_(b->b.ctx[0]);
-  return wm::launch_harvest(b->b, x, t, f0);
+  return on_batch(b, launch_harvest, x, t, f0);
 }
 int WorldMi355Analyze(WorldMi355Batch* hb, const double* x, double* t, double* f0, double* sp,
                       double* ap) {
-  OnDevice dev_(hb->b.ctx[0]);
-  return launch_analyze(hb->b, x, t, f0, sp, ap);
+  return on_batch(hb, launch_analyze, x, t, f0, sp, ap);
 }
 int WorldMi355AnalyzeSynthesize(WorldMi355Batch* hb, const double* x, double* t, double* f0, double* sp,
                                 double* ap, double* y) {
-  OnDevice dev_(hb->b.ctx[0]);
-  return launch_analyze_synthesize(hb->b, x, t, f0, sp, ap, y);
+  return on_batch(hb, launch_analyze_synthesize, x, t, f0, sp, ap, y);
 }
 int WorldMi355Vibrato(WorldMi355Batch* hb, const float* lf0, const int* seg_utt_off, const int* seg_start,
                       const int* seg_end, const double* seg_pitch, float* vib, float* lf0_out, int* n_too_long) {
-  OnDevice dev_(hb->b.ctx[0]);
-  return launch_vibrato(hb->b, lf0, seg_utt_off, seg_start, seg_end, seg_pitch, vib, lf0_out, n_too_long);
+  return on_batch(hb, launch_vibrato, lf0, seg_utt_off, seg_start, seg_end, seg_pitch, vib, lf0_out, n_too_long);
 }
 int WorldMi355UtteranceStatus(WorldMi355Batch* hb, const double* x, const double* f0, const double* sp,
                               const double* ap, int* status) {
-  OnDevice dev_(hb->b.ctx[0]);
-  return launch_utterance_status(hb->b, x, f0, sp, ap, status);
+  return on_batch(hb, launch_utterance_status, x, f0, sp, ap, status);
 }
 #ifdef WM_PHASE
 // debug builds only (make EXTRA=-DWM_PHASE): the shader-clock totals of the phase marks of one translation unit
@@ -744,6 +709,17 @@ void drop_in_failed(const DropInError& e) {
   e.handler(e.where, e.code, WorldMi355LastError(), e.user);
 }
 
+// A drop-in entry point's body: one call at a time, and a failure that unwinds from it (die() with a handler installed)
+// ends in that handler.
+template <class Body> void drop_in(Body body) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  try {
+    body();
+  } catch (const DropInError& e) {
+    drop_in_failed(e);
+  }
+}
+
 hipStream_t ws_stream() { return default_context()->c.stream; }
 
 // the upload stream of Synthesis(): its sp / ap rows travel beside the f0-only kernels, not behind them
@@ -858,8 +834,7 @@ void InitializeDioOption(DioOption* option) {                           // dio.c
 }
 void Dio(const double* x, int x_length, int fs, const DioOption* option, double* temporal_positions,
          double* f0) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, option->frame_period, &p);
     p.f0_floor = option->f0_floor; p.f0_ceil = option->f0_ceil;
@@ -881,9 +856,7 @@ void Dio(const double* x, int x_length, int fs, const DioOption* option, double*
     get(df, f0, nf);
     g_ws.finish();
     tr.mark("back");
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 int GetSamplesForHarvest(int fs, int x_length, double frame_period) {  // harvest.cpp:1219-1221
@@ -896,8 +869,7 @@ void InitializeHarvestOption(HarvestOption* option) {                   // harve
 }
 void Harvest(const double* x, int x_length, int fs, const HarvestOption* option,
              double* temporal_positions, double* f0) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, option->frame_period, &p);
     p.f0_floor = option->f0_floor; p.f0_ceil = option->f0_ceil;
@@ -911,15 +883,12 @@ void Harvest(const double* x, int x_length, int fs, const HarvestOption* option,
     get(dt, temporal_positions, nf);
     get(df, f0, nf);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 void StoneMask(const double* x, int x_length, int fs, const double* temporal_positions, const double* f0,
                int f0_length, double* refined_f0) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, 5.0, &p);
     p.fft_size = 1024;   // unused by StoneMask
@@ -931,9 +900,7 @@ void StoneMask(const double* x, int x_length, int fs, const double* temporal_pos
     run_or_die("StoneMask", WorldMi355StoneMask(b, dx, dt, df, dr));
     get(dr, refined_f0, (size_t)f0_length);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 int GetFFTSizeForCheapTrick(int fs, const CheapTrickOption* option) {   // cheaptrick.cpp:191-194
@@ -949,8 +916,7 @@ void InitializeCheapTrickOption(int fs, CheapTrickOption* option) {      // chea
 }
 void CheapTrick(const double* x, int x_length, int fs, const double* temporal_positions, const double* f0,
                 int f0_length, const CheapTrickOption* option, double** spectrogram) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, 5.0, &p);
     p.q1 = option->q1;
@@ -970,16 +936,13 @@ void CheapTrick(const double* x, int x_length, int fs, const double* temporal_po
     get_rows(ds, spectrogram, f0_length, w);
     g_ws.finish();
     tr.mark("back");
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 void InitializeD4COption(D4COption* option) { option->threshold = 0.85; }   // d4c.cpp:399-401
 void D4C(const double* x, int x_length, int fs, const double* temporal_positions, const double* f0,
          int f0_length, int fft_size, const D4COption* option, double** aperiodicity) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, 5.0, &p);
     p.fft_size = fft_size;
@@ -997,9 +960,7 @@ void D4C(const double* x, int x_length, int fs, const double* temporal_positions
     get_rows(da, aperiodicity, f0_length, w);
     g_ws.finish();
     tr.mark("back");
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 // ---- world/codec.h --------------------------------------------------------------------------------
@@ -1017,8 +978,7 @@ static WorldMi355Batch* codec_batch(int fs, int fft_size, int f0_length) {   // 
 
 void CodeSpectralEnvelope(const double* const* spectrogram, int f0_length, int fs, int fft_size,
                           int number_of_dimensions, double** coded_spectral_envelope) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     const int w = fft_size / 2 + 1;
     WorldMi355Batch* b = codec_batch(fs, fft_size, f0_length);
     double* ds = put_rows(kSp, spectrogram, f0_length, w);
@@ -1026,15 +986,12 @@ void CodeSpectralEnvelope(const double* const* spectrogram, int f0_length, int f
     run_or_die("CodeSpectralEnvelope", WorldMi355CodeSpectralEnvelope(b, ds, number_of_dimensions, dc));
     get_rows(dc, coded_spectral_envelope, f0_length, number_of_dimensions);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 void DecodeSpectralEnvelope(const double* const* coded_spectral_envelope, int f0_length, int fs, int fft_size,
                             int number_of_dimensions, double** spectrogram) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     const int w = fft_size / 2 + 1;
     WorldMi355Batch* b = codec_batch(fs, fft_size, f0_length);
     double* dc = put_rows(kCoded, coded_spectral_envelope, f0_length, number_of_dimensions);
@@ -1042,15 +999,12 @@ void DecodeSpectralEnvelope(const double* const* coded_spectral_envelope, int f0
     run_or_die("DecodeSpectralEnvelope", WorldMi355DecodeSpectralEnvelope(b, dc, number_of_dimensions, ds));
     get_rows(ds, spectrogram, f0_length, w);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 void CodeAperiodicity(const double* const* aperiodicity, int f0_length, int fs, int fft_size,
                       int number_of_aperiodicities, double** coded_aperiodicity) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     if (number_of_aperiodicities != codec_num_aperiodicities(fs))
       die("CodeAperiodicity: number_of_aperiodicities must be GetNumberOfAperiodicities(fs)", WM_ERR_BAD_ARG);
     const int w = fft_size / 2 + 1;
@@ -1060,17 +1014,14 @@ void CodeAperiodicity(const double* const* aperiodicity, int f0_length, int fs, 
     run_or_die("CodeAperiodicity", WorldMi355CodeAperiodicity(b, da, dc));
     get_rows(dc, coded_aperiodicity, f0_length, number_of_aperiodicities);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 // Positional meaning of the reference's DEFINITION (codec.cpp:237-238): the 4th argument is the number
 // of aperiodicities and the 5th the FFT size, whatever the header calls them.
 void DecodeAperiodicity(const double* const* coded_aperiodicity, int f0_length, int fs, int arg4_number_of_aperiodicities,
                         int arg5_fft_size, double** aperiodicity) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     const int nap = arg4_number_of_aperiodicities, fft_size = arg5_fft_size;
     if (nap != codec_num_aperiodicities(fs))
       die("DecodeAperiodicity: 4th argument must be GetNumberOfAperiodicities(fs) (codec.cpp:237-238)", WM_ERR_BAD_ARG);
@@ -1081,16 +1032,13 @@ void DecodeAperiodicity(const double* const* coded_aperiodicity, int f0_length, 
     run_or_die("DecodeAperiodicity", WorldMi355DecodeAperiodicity(b, dc, da));
     get_rows(da, aperiodicity, f0_length, w);
     g_ws.finish();
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 void Synthesis(const double* f0, int f0_length, const double* const* spectrogram,
                const double* const* aperiodicity, int fft_size, double frame_period, int fs, int y_length,
                double* y) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  try {
+  drop_in([&] {
     WorldMi355Params p;
     WorldMi355DefaultParams(fs, frame_period, &p);
     p.fft_size = fft_size;
@@ -1131,9 +1079,7 @@ void Synthesis(const double* f0, int f0_length, const double* const* spectrogram
     get(dy, y, (size_t)y_length);
     g_ws.finish();
     tr.mark("back");
-  } catch (const DropInError& e_) {
-    drop_in_failed(e_);
-  }
+  });
 }
 
 }  // extern "C"

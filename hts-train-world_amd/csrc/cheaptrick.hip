@@ -204,8 +204,7 @@ __global__ __launch_bounds__(64, F >= 4096 ? 1 : (F >= 2048 ? 2 : 3)) void cheap
   WM_PHASE_FLUSH(0)
 }
 
-int launch_cheaptrick(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_sp) {
-  hipStream_t st = b.ctx->stream;
+int launch_cheaptrick(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_sp) {
   const int F = b.p.fft_size;
   int rc = b.ctx->ensure_rng(b.rng_bound_cheaptrick(), st);
   if (rc) return rc;

@@ -262,17 +262,17 @@ __global__ __launch_bounds__(256) void samples_to_pcm16_kernel(const double* __r
     pcm[i] = (int16_t)(v != v ? 0.0 : fmin(32767.0, fmax(-32768.0, v)));
   }
 }
-int launch_pcm16_to_samples(Batch& b, const int16_t* d_pcm, double* d_x) {
+int launch_pcm16_to_samples(Batch& b, hipStream_t st, const int16_t* d_pcm, double* d_x) {
   if (b.total_x <= 0) return WM_OK;
   const int64_t blocks = (b.total_x + 1023) / 1024;
-  hipLaunchKernelGGL(pcm16_to_samples_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, b.ctx->stream,
+  hipLaunchKernelGGL(pcm16_to_samples_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st,
                      d_pcm, b.total_x, d_x);
   return wm_check(hipGetLastError());
 }
-int launch_samples_to_pcm16(Batch& b, const double* d_y, int16_t* d_pcm) {
+int launch_samples_to_pcm16(Batch& b, hipStream_t st, const double* d_y, int16_t* d_pcm) {
   if (b.total_y <= 0) return WM_OK;
   const int64_t blocks = (b.total_y + 1023) / 1024;
-  hipLaunchKernelGGL(samples_to_pcm16_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, b.ctx->stream,
+  hipLaunchKernelGGL(samples_to_pcm16_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st,
                      d_y, b.total_y, d_pcm);
   return wm_check(hipGetLastError());
 }
@@ -357,7 +357,7 @@ int codec_num_aperiodicities(int fs) {                              // codec.cpp
 }
 
 template <class OUT>
-static int code_sp(Batch& b, const double* d_in, int ndim, CodeOpts o, OUT* d_out, const char* name) {
+static int code_sp(Batch& b, hipStream_t st, const double* d_in, int ndim, CodeOpts o, OUT* d_out, const char* name) {
   const int F = b.p.fft_size;
   if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
   if (ndim < 1 || ndim > F / 4 + 1) return WM_ERR_BAD_ARG;      // the reference reads spectrum[i], i <= fft_size/4
@@ -366,7 +366,6 @@ static int code_sp(Batch& b, const double* d_in, int ndim, CodeOpts o, OUT* d_ou
   const CodecTables& T = static_cast<const CodecTables&>(*b.codec);
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
-  hipStream_t st = b.ctx->stream;
   TimedScope ts_(b.ctx, st, name);
 #define WM_CODE_CASE(FF)                                                                                     \
   case FF: {                                                                                                 \
@@ -384,13 +383,13 @@ static int code_sp(Batch& b, const double* d_in, int ndim, CodeOpts o, OUT* d_ou
   return wm_check(hipGetLastError());
 }
 
-int launch_code_spectral_envelope(Batch& b, const double* d_sp, int ndim, double* d_coded) {
+int launch_code_spectral_envelope(Batch& b, hipStream_t st, const double* d_sp, int ndim, double* d_coded) {
   const CodeOpts o = {1.0, 0.0, 0.0, 0};
-  return code_sp<double>(b, d_sp, ndim, o, d_coded, "codec_code_sp_kernel");
+  return code_sp<double>(b, st, d_sp, ndim, o, d_coded, "codec_code_sp_kernel");
 }
 
 template <class IN>
-static int decode_sp(Batch& b, const IN* d_coded, int ndim, DecodeOpts o, double* d_sp) {
+static int decode_sp(Batch& b, hipStream_t st, const IN* d_coded, int ndim, DecodeOpts o, double* d_sp) {
   const int F = b.p.fft_size;
   if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
   if (ndim < 1 || ndim > F / 2) return WM_ERR_BAD_ARG;
@@ -399,7 +398,6 @@ static int decode_sp(Batch& b, const IN* d_coded, int ndim, DecodeOpts o, double
   const CodecTables& T = static_cast<const CodecTables&>(*b.codec);
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
-  hipStream_t st = b.ctx->stream;
   TimedScope ts_(b.ctx, st, "codec_decode_sp_kernel");
 #define WM_DEC_CASE(FF)                                                                                      \
   case FF: {                                                                                                 \
@@ -417,27 +415,27 @@ static int decode_sp(Batch& b, const IN* d_coded, int ndim, DecodeOpts o, double
   return wm_check(hipGetLastError());
 }
 
-int launch_decode_spectral_envelope(Batch& b, const double* d_coded, int ndim, double* d_sp) {
-  return decode_sp<double>(b, d_coded, ndim, DecodeOpts{0.0, 0.0}, d_sp);
+int launch_decode_spectral_envelope(Batch& b, hipStream_t st, const double* d_coded, int ndim, double* d_sp) {
+  return decode_sp<double>(b, st, d_coded, ndim, DecodeOpts{0.0, 0.0}, d_sp);
 }
 
-int launch_code_aperiodicity(Batch& b, const double* d_ap, double* d_coded) {
+int launch_code_aperiodicity(Batch& b, hipStream_t st, const double* d_ap, double* d_coded) {
   const int nap = codec_num_aperiodicities(b.p.fs);
   const int64_t n = b.total_f * nap;
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, b.ctx->stream, "codec_code_ap_kernel");
-  hipLaunchKernelGGL(codec_code_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, d_ap,
+  TimedScope ts_(b.ctx, st, "codec_code_ap_kernel");
+  hipLaunchKernelGGL(codec_code_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_ap,
                      b.p.fft_size / 2 + 1, b.p.fs, b.p.fft_size, nap, b.total_f, d_coded);
   return wm_check(hipGetLastError());
 }
 
-int launch_decode_aperiodicity(Batch& b, const double* d_coded, double* d_ap) {
+int launch_decode_aperiodicity(Batch& b, hipStream_t st, const double* d_coded, double* d_ap) {
   const int nap = codec_num_aperiodicities(b.p.fs);
   if (nap < 1) return WM_ERR_UNSUPPORTED;
   const int64_t n = b.total_f * (b.p.fft_size / 2 + 1);
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, b.ctx->stream, "codec_decode_ap_kernel");
-  hipLaunchKernelGGL(codec_decode_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, d_coded,
+  TimedScope ts_(b.ctx, st, "codec_decode_ap_kernel");
+  hipLaunchKernelGGL(codec_decode_ap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_coded,
                      nap, b.p.fs, b.p.fft_size, b.total_f, d_ap);
   return wm_check(hipGetLastError());
 }
@@ -448,16 +446,16 @@ int launch_decode_aperiodicity(Batch& b, const double* d_coded, double* d_ap) {
 //   bap = CodeSpectralEnvelope(ap * 1e4)[ap_dim], coefficient 0 - 9.210340, (0, 1e-4) -> 0
 //         (the mcep result computed just before is overwritten by the reference, :332-341)
 //   lf0 = log f0, 0 where unvoiced
-int launch_recipe_features(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, int spec_dim,
-                           int ap_dim, float* d_lf0, float* d_mgc, float* d_bap) {
+int launch_recipe_features(Batch& b, hipStream_t st, const double* d_f0, const double* d_sp, const double* d_ap,
+                           int spec_dim, int ap_dim, float* d_lf0, float* d_mgc, float* d_bap) {
   const CodeOpts osp = {1e4, 0.0001, 12.0, 0};
-  int rc = code_sp<float>(b, d_sp, spec_dim, osp, d_mgc, "codec_code_sp_kernel");
+  int rc = code_sp<float>(b, st, d_sp, spec_dim, osp, d_mgc, "codec_code_sp_kernel");
   if (rc) return rc;
   const CodeOpts oap = {1e4, 0.0, -9.210340, 1};
-  rc = code_sp<float>(b, d_ap, ap_dim, oap, d_bap, "codec_code_sp_kernel");
+  rc = code_sp<float>(b, st, d_ap, ap_dim, oap, d_bap, "codec_code_sp_kernel");
   if (rc) return rc;
   if (b.total_f > 0)
-    hipLaunchKernelGGL(codec_lf0_kernel, dim3((unsigned)((b.total_f + 255) / 256)), dim3(256), 0, b.ctx->stream, d_f0,
+    hipLaunchKernelGGL(codec_lf0_kernel, dim3((unsigned)((b.total_f + 255) / 256)), dim3(256), 0, st, d_f0,
                        b.total_f, d_lf0);
   return wm_check(hipGetLastError());
 }
@@ -541,17 +539,16 @@ __global__ __launch_bounds__(256) void codec_f0_from_lf0_kernel(const float* __r
   f0[i] = l != 0 ? exp(l) : 0;                                 // ToF0, synth.cpp:80-88
 }
 
-int launch_recipe_decode(Batch& b, const float* d_lf0, const float* d_mgc, const float* d_bap, int spec_dim,
-                         int ap_dim, double* d_f0, double* d_sp, double* d_ap) {
+int launch_recipe_decode(Batch& b, hipStream_t st, const float* d_lf0, const float* d_mgc, const float* d_bap,
+                         int spec_dim, int ap_dim, double* d_f0, double* d_sp, double* d_ap) {
   const int F = b.p.fft_size;
   if (F != 512 && F != 1024 && F != 2048 && F != 4096) return WM_ERR_UNSUPPORTED_FFT;
   const int order = (ap_dim % 2 == 1) ? ap_dim - 1 : ap_dim;   // synth.cpp:233-235
   if (ap_dim < 1 || order < 1 || order > 63) return WM_ERR_BAD_ARG;
-  int rc = decode_sp<float>(b, d_mgc, spec_dim, DecodeOpts{-12.0, 1e4}, d_sp);
+  int rc = decode_sp<float>(b, st, d_mgc, spec_dim, DecodeOpts{-12.0, 1e4}, d_sp);
   if (rc) return rc;
   const int64_t tf = b.total_f;
   if (tf <= 0) return WM_OK;
-  hipStream_t st = b.ctx->stream;
   {
     TimedScope ts_(b.ctx, st, "codec_bap_decode_kernel");
     const int64_t cap = (int64_t)b.ctx->num_cu * 16;
@@ -619,15 +616,16 @@ int check_compose_cmp(int n_streams, const float* const* d_data, const int* dims
   return WM_OK;
 }
 
-int launch_compose_cmp(Batch& b, int n_streams, const float* const* d_data, const int* dims, const int* n_windows,
-                       const double* const* const* windows, const int* const* window_sizes, float* d_out) {
+int launch_compose_cmp(Batch& b, hipStream_t st, int n_streams, const float* const* d_data, const int* dims,
+                       const int* n_windows, const double* const* const* windows, const int* const* window_sizes,
+                       float* d_out) {
   if (const int rc = check_compose_cmp(n_streams, d_data, dims, n_windows, windows, window_sizes, d_out)) return rc;
   CmpMeta m;
   cmp_fill_meta(m, n_streams, d_data, dims, n_windows, windows, window_sizes);
   const int64_t n = b.total_f * m.total_cols;
   if (n <= 0) return WM_OK;
-  TimedScope ts_(b.ctx, b.ctx->stream, "cmp_compose_kernel");
-  hipLaunchKernelGGL(cmp_compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b.ctx->stream, m,
+  TimedScope ts_(b.ctx, st, "cmp_compose_kernel");
+  hipLaunchKernelGGL(cmp_compose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m,
                      b.d_frame_utt, b.d_f_off, b.total_f, d_out);
   return wm_check(hipGetLastError());
 }

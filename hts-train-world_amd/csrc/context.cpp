@@ -252,10 +252,10 @@ int Context::ensure_split() {
   return rc;
 }
 
-// D4C around CheapTrick in the one-call forms, after ev_f0 has been recorded on the caller's stream and the second
+// D4C around CheapTrick in the one-call forms, after ev_f0 has been recorded on the call's stream `st` and the second
 // stream waits for it: the preparation on the second stream, the RARE launch on the third (its waves wait for whole
 // SIMDs, i.e. for CheapTrick to drain, and would hold up whatever came behind them on a shared stream); d4c_after()
-// queues the usual kernel behind the preparation and makes the caller's stream wait for the RARE launch.
+// queues the usual kernel behind the preparation and makes `st` wait for the RARE launch.
 static int d4c_beside(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
   const SideStreams& s = *b.ctx->fork;
   int rc = d4c_prepare(b, s.side, d_x, d_t, d_f0);
@@ -264,39 +264,41 @@ static int d4c_beside(Batch& b, const double* d_x, const double* d_t, const doub
   rc = rc ? rc : d4c_rare(b, s.aux, d_x, d_t, d_f0, d_ap);
   return rc ? rc : wm_check(hipEventRecord(s.ev_rare, s.aux));
 }
-static int d4c_after(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
-  Context& c = *b.ctx;
-  int rc = wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_d4c, 0));
-  rc = rc ? rc : d4c_run(b, c.stream, d_x, d_t, d_f0, d_ap);
-  return rc ? rc : wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_rare, 0));
+static int d4c_after(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
+  const SideStreams& s = *b.ctx->fork;
+  int rc = wm_check(hipStreamWaitEvent(st, s.ev_d4c, 0));
+  rc = rc ? rc : d4c_run(b, st, d_x, d_t, d_f0, d_ap);
+  return rc ? rc : wm_check(hipStreamWaitEvent(st, s.ev_rare, 0));
 }
 
-// Dio -> StoneMask -> CheapTrick -> D4C, one behind the other on the caller's stream
-static int analyze_in_order(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
-  int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
-  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-  return rc ? rc : launch_d4c(b, d_x, d_t, d_f0, d_ap);
+// Dio -> StoneMask -> CheapTrick -> D4C, one behind the other on `st`
+static int analyze_in_order(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
+                            double* d_ap) {
+  int rc = launch_dio(b, st, d_x, d_t, b.d_f0_tmp);
+  rc = rc ? rc : launch_stonemask(b, st, d_x, d_t, b.d_f0_tmp, d_f0);
+  rc = rc ? rc : launch_cheaptrick(b, st, d_x, d_t, d_f0, d_sp);
+  return rc ? rc : launch_d4c(b, st, d_x, d_t, d_f0, d_ap);
 }
 // The same with D4C's preparation on the second stream beside CheapTrick, from f0 (ev_f0) on.
-static int analyze_forked(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
+static int analyze_forked(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
+                          double* d_ap) {
   Context& c = *b.ctx;
-  int rc = launch_dio(b, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, d_x, d_t, b.d_f0_tmp, d_f0, b.p.f0_floor);
+  int rc = launch_dio(b, st, d_x, d_t, b.d_f0_tmp);
+  rc = rc ? rc : launch_stonemask(b, st, d_x, d_t, b.d_f0_tmp, d_f0);
   rc = rc ? rc : c.ensure_side();
   // the randn table must not move under two streams (it may be reallocated when it grows): settle its size first
-  rc = rc ? rc : c.ensure_rng(std::max(b.rng_bound_cheaptrick(), b.rng_bound_d4c()), c.stream);
-  rc = rc ? rc : wm_check(hipEventRecord(c.fork->ev_f0, c.stream));
+  rc = rc ? rc : c.ensure_rng(std::max(b.rng_bound_cheaptrick(), b.rng_bound_d4c()), st);
+  rc = rc ? rc : wm_check(hipEventRecord(c.fork->ev_f0, st));
   rc = rc ? rc : wm_check(hipStreamWaitEvent(c.fork->side, c.fork->ev_f0, 0));
   rc = rc ? rc : d4c_beside(b, d_x, d_t, d_f0, d_ap);
-  rc = rc ? rc : launch_cheaptrick(b, d_x, d_t, d_f0, d_sp);
-  return rc ? rc : d4c_after(b, d_x, d_t, d_f0, d_ap);
+  rc = rc ? rc : launch_cheaptrick(b, st, d_x, d_t, d_f0, d_sp);
+  return rc ? rc : d4c_after(b, st, d_x, d_t, d_f0, d_ap);
 }
 
 // Dio -> StoneMask -> CheapTrick -> D4C as one call: D4C's preparation runs on the second stream beside CheapTrick
 // once the batch has its D4C tables (the first use allocates them, in the plain order).
-int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
-  return b.d4c ? analyze_forked(b, d_x, d_t, d_f0, d_sp, d_ap) : analyze_in_order(b, d_x, d_t, d_f0, d_sp, d_ap);
+int launch_analyze(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
+  return b.d4c ? analyze_forked(b, st, d_x, d_t, d_f0, d_sp, d_ap) : analyze_in_order(b, st, d_x, d_t, d_f0, d_sp, d_ap);
 }
 
 // Analysis followed by Synthesis of the same features (BASELINE.json's metric), as one call.  Identical
@@ -304,27 +306,27 @@ int launch_analyze(Batch& b, const double* d_x, double* d_t, double* d_f0, doubl
 // stream, as soon as StoneMask has produced f0, beside CheapTrick and D4C.  Its kernels are latency chains on
 // one wavefront per utterance (the phase accumulation) plus a host round trip for the pulse count, which would
 // otherwise sit between D4C and the pulse kernel with the machine idle.
-int launch_analyze_synthesize(Batch& b, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap,
-                              double* d_y) {
+int launch_analyze_synthesize(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
+                              double* d_ap, double* d_y) {
   Context& c = *b.ctx;
   int rc = c.ensure_side();
   // Synthesis reads the randn table too: the size is settled here for all three stages, in one growth
-  rc = rc ? rc : c.ensure_rng(std::max({b.rng_bound_cheaptrick(), b.rng_bound_d4c(), b.rng_bound_synthesis()}), c.stream);
+  rc = rc ? rc : c.ensure_rng(std::max({b.rng_bound_cheaptrick(), b.rng_bound_d4c(), b.rng_bound_synthesis()}), st);
   if (rc) return rc;
   if (!b.syn_warm) {
     // first use of this batch: Synthesis allocates its work arrays and sizes the response scratch, and a
     // hipMalloc of gigabytes stalls kernels running beside it -- take the plain order once
-    rc = analyze_in_order(b, d_x, d_t, d_f0, d_sp, d_ap);
-    rc = rc ? rc : launch_synthesis(b, d_f0, d_sp, d_ap, d_y);
+    rc = analyze_in_order(b, st, d_x, d_t, d_f0, d_sp, d_ap);
+    rc = rc ? rc : launch_synthesis(b, st, d_f0, d_sp, d_ap, d_y);
     b.syn_warm = !rc;                                          // a failed first use is made again in this order
     return rc;
   }
   // second stream, from f0 on: D4C's preparation (offsets, LoveTrain, frame lists), then Synthesis's
-  rc = analyze_forked(b, d_x, d_t, d_f0, d_sp, d_ap);
+  rc = analyze_forked(b, st, d_x, d_t, d_f0, d_sp, d_ap);
   rc = rc ? rc : synthesis_prepare(b, c.fork->side, d_f0, d_y);
   rc = rc ? rc : wm_check(hipEventRecord(c.fork->ev_prep, c.fork->side));
-  rc = rc ? rc : wm_check(hipStreamWaitEvent(c.stream, c.fork->ev_prep, 0));
-  return rc ? rc : synthesis_render(b, c.stream, d_sp, d_ap, d_y);
+  rc = rc ? rc : wm_check(hipStreamWaitEvent(st, c.fork->ev_prep, 0));
+  return rc ? rc : synthesis_render(b, st, d_sp, d_ap, d_y);
 }
 
 void Context::timing_clear() {

@@ -811,8 +811,7 @@ int d4c_run(Batch& b, hipStream_t st, const double* d_x, const double* d_t, cons
   return wm_check(hipGetLastError());
 }
 
-int launch_d4c(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
-  const hipStream_t st = b.ctx->stream;
+int launch_d4c(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap) {
   int rc = d4c_prepare(b, st, d_x, d_t, d_f0);
   rc = rc ? rc : d4c_rare(b, st, d_x, d_t, d_f0, d_ap);
   return rc ? rc : d4c_run(b, st, d_x, d_t, d_f0, d_ap);

@@ -500,7 +500,7 @@ struct DioWs : StageWs {
 
 // Taps and windows as the reference designs them, and the filter spectra of the FFT-convolution path: [0] low-cut
 // (block lc_conv), [1 .. nb] bands (block band_conv).  t.d = {low-cut taps, windows, spectra or null}.
-static int dio_filters(Context& c, const DioMeta& m, const std::vector<double>& lowcut, const std::vector<double>& win,
+static int dio_filters(hipStream_t st, const DioMeta& m, const std::vector<double>& lowcut, const std::vector<double>& win,
                        Table& t) {
   int rc = WM_OK;
   auto up = [&](StageWs& o, void** dst, const void* src, size_t bytes) {
@@ -528,7 +528,6 @@ static int dio_filters(Context& c, const DioMeta& m, const std::vector<double>& 
   const double* d_lowcut = (const double*)t.d[0];
   const double* d_win = (const double*)t.d[1];
   cpx* Hs = (cpx*)t.d[2];
-  hipStream_t st = c.stream;
   if (m.lc_conv == 2048)
     hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(1), dim3(64), 0, st, d_lowcut, d_desc, d_desc + n1,
                        d_desc + 2 * n1, Hs);
@@ -546,7 +545,7 @@ static int dio_filters(Context& c, const DioMeta& m, const std::vector<double>& 
   return rc;
 }
 
-static int dio_setup(Batch& b) {
+static int dio_setup(Batch& b, hipStream_t st) {
   if (b.dio) return WM_OK;
   const WorldMi355Params& p = b.p;
   std::unique_ptr<DioWs> W(new DioWs());
@@ -663,7 +662,7 @@ static int dio_setup(Batch& b) {
   const Table* f = nullptr;
   if (!rc)
     rc = b.ctx->table({kDioFilters, {(double)p.fs, (double)m.ratio, p.f0_floor, p.f0_ceil, p.channels_in_octave}}, f,
-                      [&](Table& t) { return dio_filters(*b.ctx, m, lowcut, win, t); });
+                      [&](Table& t) { return dio_filters(st, m, lowcut, win, t); });
   if (rc) return rc;
   W->d_lowcut = (const double*)f->d[0];
   W->d_win = (const double*)f->d[1];
@@ -672,11 +671,9 @@ static int dio_setup(Batch& b) {
   return WM_OK;
 }
 
-int launch_dio(Batch& b, const double* d_x, double* d_t, double* d_f0) {
-  int rc = dio_setup(b);
+int launch_dio(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0) {
+  int rc = dio_setup(b, st);
   if (rc) return rc;
-  Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   DioWs& W = static_cast<DioWs&>(*b.dio);
   const DioMeta& m = W.meta;
   // speed > 1: decimate first (dio.cpp:68-70); the rest of the chain then reads the decimated signal

@@ -291,23 +291,19 @@ int launch_dnn(Batch& b, hipStream_t st, const WorldMi355AcousticModel& m, const
   }
   const int n_buf = m.n_layers >= 2 ? 2 : m.n_layers;
   const int64_t need = chunk * (int64_t)max_units;
-  DnnWs* W = static_cast<DnnWs*>(b.dnn.get());
-  if (W == nullptr || W->cap < need || W->n_buf < n_buf || W->cap_utt < b.n_utt) {
-    if (W != nullptr) {                                  // an earlier call's kernels may still use the smaller block;
-      if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-      b.dnn.reset();                                     // released first: the two never exist side by side
-    }
-    std::unique_ptr<DnnWs> Nw(new DnnWs());
-    for (int k = 0; k < n_buf; ++k)
-      if (const int rc = wm_check(Nw->alloc(&Nw->h[k], sizeof(float) * (size_t)need))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->spk, sizeof(int) * (size_t)b.n_utt))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->status, sizeof(int) * (size_t)b.n_utt))) return rc;
-    Nw->cap = need;
-    Nw->n_buf = n_buf;
-    Nw->cap_utt = b.n_utt;
-    b.dnn = std::move(Nw);
-    W = static_cast<DnnWs*>(b.dnn.get());
-  }
+  DnnWs* W = nullptr;                                    // (a training pass's DnnTrainWs serves as well)
+  if (const int rc = grow_ws(b.dnn, st, W,
+                             [&](const DnnWs& w) { return w.cap >= need && w.n_buf >= n_buf && w.cap_utt >= b.n_utt; },
+                             [&](DnnWs& n) {
+                               n.cap = need;
+                               n.n_buf = n_buf;
+                               n.cap_utt = b.n_utt;
+                               for (int k = 0; k < n_buf; ++k)
+                                 if (const int rc = wm_check(n.alloc(&n.h[k], sizeof(float) * (size_t)need))) return rc;
+                               if (const int rc = wm_check(n.alloc(&n.spk, sizeof(int) * (size_t)b.n_utt))) return rc;
+                               return wm_check(n.alloc(&n.status, sizeof(int) * (size_t)b.n_utt));
+                             }))
+    return rc;
   W->h_spk.resize((size_t)b.n_utt);
   for (int u = 0; u < b.n_utt; ++u) W->h_spk[(size_t)u] = spkr != nullptr ? spkr[u] : m.n_spkrs - 1;   // DNNSynthesis.py:139
   if (const int rc = wm_check(hipMemcpyAsync(W->spk, W->h_spk.data(), sizeof(int) * (size_t)b.n_utt, hipMemcpyHostToDevice, st)))

@@ -537,42 +537,35 @@ struct DnnTrainWs : DnnWs {
 };
 
 static int dnn_train_ws(Batch& b, hipStream_t st, int64_t rows, int max_w, int n_act, int n_hd, int n_spk, DnnTrainWs** out) {
-  DnnWs* W0 = static_cast<DnnWs*>(b.dnn.get());
-  DnnTrainWs* W = W0 != nullptr && W0->train ? static_cast<DnnTrainWs*>(W0) : nullptr;
-  if (W == nullptr || W->rows < rows || W->max_w < max_w || W->n_act < n_act || W->n_hd < n_hd || W->n_spk < n_spk ||
-      W->cap_utt < b.n_utt) {
-    if (W0 != nullptr) {
-      if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-      b.dnn.reset();
-    }
-    std::unique_ptr<DnnTrainWs> Nw(new DnnTrainWs());
+  auto fits = [&](const DnnWs& held) {                   // a forward pass's plain DnnWs never does
+    if (!held.train) return false;
+    const DnnTrainWs& w = static_cast<const DnnTrainWs&>(held);
+    return w.rows >= rows && w.max_w >= max_w && w.n_act >= n_act && w.n_hd >= n_hd && w.n_spk >= n_spk && w.cap_utt >= b.n_utt;
+  };
+  return grow_ws<DnnTrainWs, DnnWs>(b.dnn, st, *out, fits, [&](DnnTrainWs& n) {
+    n.train = true;
+    n.cap = rows * (int64_t)max_w;
+    n.n_buf = 2;
+    n.cap_utt = b.n_utt;
+    n.rows = rows;
+    n.max_w = max_w;
+    n.n_act = n_act;
+    n.n_hd = n_hd;
+    n.n_spk = n_spk;
     const size_t buf = sizeof(float) * (size_t)rows * (size_t)max_w;
     for (int k = 0; k < 2; ++k)
-      if (const int rc = wm_check(Nw->alloc(&Nw->h[k], buf))) return rc;
+      if (const int rc = wm_check(n.alloc(&n.h[k], buf))) return rc;
     for (int k = 0; k < n_act; ++k)
-      if (const int rc = wm_check(Nw->alloc(&Nw->act[k], buf))) return rc;
+      if (const int rc = wm_check(n.alloc(&n.act[k], buf))) return rc;
     for (int k = 0; k < n_hd; ++k)
-      if (const int rc = wm_check(Nw->alloc(&Nw->hd[k], buf))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->spk, sizeof(int) * (size_t)b.n_utt))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->status, sizeof(int) * (size_t)b.n_utt))) return rc;
+      if (const int rc = wm_check(n.alloc(&n.hd[k], buf))) return rc;
+    if (const int rc = wm_check(n.alloc(&n.spk, sizeof(int) * (size_t)b.n_utt))) return rc;
+    if (const int rc = wm_check(n.alloc(&n.status, sizeof(int) * (size_t)b.n_utt))) return rc;
     const size_t wd = sizeof(double) * (size_t)max_w;
-    if (const int rc = wm_check(Nw->alloc(&Nw->U, wd * (size_t)b.n_utt))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->state, wd * 16 * (size_t)(kDnnMaxLayers + 1)))) return rc;
-    if (const int rc = wm_check(Nw->alloc(&Nw->acc, wd * (size_t)(1 + n_spk) * (size_t)(kDnnMaxLayers + 1)))) return rc;
-    Nw->train = true;
-    Nw->cap = rows * (int64_t)max_w;
-    Nw->n_buf = 2;
-    Nw->cap_utt = b.n_utt;
-    Nw->rows = rows;
-    Nw->max_w = max_w;
-    Nw->n_act = n_act;
-    Nw->n_hd = n_hd;
-    Nw->n_spk = n_spk;
-    b.dnn = std::move(Nw);
-    W = static_cast<DnnTrainWs*>(b.dnn.get());
-  }
-  *out = W;
-  return WM_OK;
+    if (const int rc = wm_check(n.alloc(&n.U, wd * (size_t)b.n_utt))) return rc;
+    if (const int rc = wm_check(n.alloc(&n.state, wd * 16 * (size_t)(kDnnMaxLayers + 1)))) return rc;
+    return wm_check(n.alloc(&n.acc, wd * (size_t)(1 + n_spk) * (size_t)(kDnnMaxLayers + 1)));
+  });
 }
 
 static DnnOperand dnn_operand(const float* p, int64_t ld) {

@@ -345,26 +345,26 @@ int launch_label_features(Batch& b, hipStream_t st, const LabelSet& set, const i
     }
   }
   // one image, one upload: 256-byte aligned sections
-  size_t at = 0;
-  auto take = [&](size_t n) { const size_t o = at; at = (at + (n ? n : 8) + 255) & ~(size_t)255; return o; };
+  Sections take;
   const size_t nl = (size_t)n_lines, nu = (size_t)b.n_utt;
   const size_t o_row = take(8 * (nl + 1)), o_start = take(4 * nl), o_end = take(4 * nl), o_sidx = take(4 * nl);
   const size_t o_phs = take(4 * nl), o_phe = take(4 * nl), o_nid = take(4 * nl), o_loff = take(4 * (nu + 1));
   const size_t o_sl = take(4 * nu), o_ncl = take(4 * (size_t)nd), o_noff = take(4 * ((size_t)nd + 1));
   const size_t o_bytes = take(bytes.size()), o_flt = take(4 * floats.size());
-  const size_t init_bytes = at;
+  const size_t init_bytes = take.at;
   const size_t o_ans = take((size_t)nd * (size_t)nb);
-  FfiWs* W = static_cast<FfiWs*>(b.ffi.get());
-  if (W != nullptr)                                 // an earlier call's copy and kernels may still use the image and the block
+  const size_t need = take.at;
+  // A workspace that is kept has its host image rewritten below: an earlier call's copy may still read it, so this
+  // call waits for `st` itself.  One that is replaced is waited for by grow_ws(): one wait per call either way.
+  const bool kept = b.ffi && static_cast<const FfiWs&>(*b.ffi).cap >= need;
+  if (kept)
     if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-  if (W == nullptr || W->cap < at) {
-    b.ffi.reset();                                  // released first: the two never exist side by side
-    std::unique_ptr<FfiWs> Nw(new FfiWs());
-    if (const int rc = wm_check(Nw->alloc(&Nw->d, at))) return rc;
-    Nw->cap = at;
-    b.ffi = std::move(Nw);
-    W = static_cast<FfiWs*>(b.ffi.get());
-  }
+  FfiWs* W = nullptr;
+  if (const int rc = grow_ws(b.ffi, st, W, [&](const FfiWs&) { return kept; }, [&](FfiWs& n) {
+        n.cap = need;
+        return wm_check(n.alloc(&n.d, need));
+      }))
+    return rc;
   W->image.assign(init_bytes, 0);
   unsigned char* img = W->image.data();
   auto put = [&](size_t o, const void* src, size_t n) { if (n) memcpy(img + o, src, n); };

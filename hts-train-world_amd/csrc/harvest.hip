@@ -1335,7 +1335,7 @@ __global__ __launch_bounds__(kCtThreads) void hv_contour_kernel(
 
 // ---- host side ------------------------------------------------------------------------------
 
-static int hv_setup(Batch& b) {
+static int hv_setup(Batch& b, hipStream_t st) {
   if (b.harvest) return WM_OK;
   std::unique_ptr<HarvestWs> W(new HarvestWs());
   HvMeta& m = W->m;
@@ -1455,7 +1455,7 @@ static int hv_setup(Batch& b) {
   al((void**)&W->d_sm, sizeof(double) * (size_t)W->tot_sm);
   al((void**)&W->d_twid, sizeof(cpx) * (size_t)kHvTwid);
   if (!rc) {
-    hipLaunchKernelGGL(hv_twiddle_kernel, dim3(kHvTwid / 256), dim3(256), 0, b.ctx->stream, W->d_twid);
+    hipLaunchKernelGGL(hv_twiddle_kernel, dim3(kHvTwid / 256), dim3(256), 0, st, W->d_twid);
     rc = wm_check(hipGetLastError());
   }
   if (!rc && m.conv) {
@@ -1470,10 +1470,10 @@ static int hv_setup(Batch& b) {
     up((void**)&d_dl, dl.data(), sizeof(int) * dl.size());
     al((void**)&W->d_H, sizeof(cpx) * (size_t)m.nch * ((size_t)m.conv / 2 + 1));
     if (!rc) {
-      hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(m.nch), dim3(64), 0, b.ctx->stream, W->d_taps, W->d_tapoff,
+      hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(m.nch), dim3(64), 0, st, W->d_taps, W->d_tapoff,
                          d_nt, d_dl, (cpx*)W->d_H);
       rc = wm_check(hipGetLastError());
-      if (!rc) rc = wm_check(hipStreamSynchronize(b.ctx->stream));
+      if (!rc) rc = wm_check(hipStreamSynchronize(st));
     }
   }
   if (rc) return rc;
@@ -1481,14 +1481,13 @@ static int hv_setup(Batch& b) {
   return WM_OK;
 }
 
-int launch_harvest(Batch& b, const double* d_x, double* d_t, double* d_f0) {
+int launch_harvest(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0) {
   if (b.total_x <= 0) return WM_ERR_BAD_ARG;
-  int rc = hv_setup(b);
+  int rc = hv_setup(b, st);
   if (rc) return rc;
   HarvestWs& W = static_cast<HarvestWs&>(*b.harvest);
   const HvMeta& m = W.m;
   Context& c = *b.ctx;
-  hipStream_t st = c.stream;
   const int n_utt = b.n_utt;
   if (m.r > 1) {
     const int len_max = b.max_x_len + 2 * m.lag + 18;

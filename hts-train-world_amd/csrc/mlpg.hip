@@ -247,17 +247,14 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
   if (const int rc = band_plan(plan, n_streams, dims, n_windows, window_sizes, b.total_f, b.n_utt,
                                [](int B) { return B > 0 ? B + 1 : 0; }))
     return rc;
-  const int64_t need = plan.need;
+  const int64_t need = plan.need;                        // 0: no stream has a band, the kernels take no workspace
   MlpgWs* W = static_cast<MlpgWs*>(b.mlpg.get());
-  if (need > 0 && (W == nullptr || W->cap < need)) {
-    std::unique_ptr<MlpgWs> N(new MlpgWs());
-    if (const int rc = wm_check(N->alloc(&N->d, sizeof(double) * (size_t)need))) return rc;
-    N->cap = need;
-    if (W != nullptr)                                    // an earlier call's kernel may still use the smaller block
-      if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-    b.mlpg = std::move(N);
-    W = static_cast<MlpgWs*>(b.mlpg.get());
-  }
+  if (need > 0)
+    if (const int rc = grow_ws(b.mlpg, st, W, [&](const MlpgWs& w) { return w.cap >= need; }, [&](MlpgWs& n) {
+          n.cap = need;
+          return wm_check(n.alloc(&n.d, sizeof(double) * (size_t)need));
+        }))
+      return rc;
   if (d_status != nullptr)
     if (const int rc = wm_check(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)b.n_utt, st))) return rc;
   TimedScope ts_(b.ctx, st, "mlpg_kernel");

@@ -448,29 +448,23 @@ struct MspfWs : StageWs {
   std::vector<double> h_tab;                      // the tables as uploaded: the copy's source lives as long as the batch
 };
 
-// the batch's workspace with room for `need` (mean, tab, part, flag); a larger one replaces it once the stream is idle
+// the batch's workspace with room for `need` (mean, tab, part, flag): the postfilter and the statistics share it, so a
+// replacement keeps what either had -- every block is max(old, need)
 static int mspf_ws(Batch& b, hipStream_t st, const int64_t (&need)[4], MspfWs** out) {
-  MspfWs* W = static_cast<MspfWs*>(b.mspf.get());
-  bool fits = W != nullptr;
-  for (int i = 0; i < 4 && fits; ++i) fits = W->cap[i] >= need[i];
-  if (!fits) {
-    std::unique_ptr<MspfWs> N(new MspfWs());
-    for (int i = 0; i < 4; ++i) N->cap[i] = W != nullptr && W->cap[i] > need[i] ? W->cap[i] : need[i];
-    if (N->cap[0] > 0)
-      if (const int rc = wm_check(N->alloc(&N->mean, sizeof(double) * (size_t)N->cap[0]))) return rc;
-    if (N->cap[1] > 0)
-      if (const int rc = wm_check(N->alloc(&N->tab, sizeof(double) * (size_t)N->cap[1]))) return rc;
-    if (N->cap[2] > 0)
-      if (const int rc = wm_check(N->alloc(&N->part, sizeof(double) * (size_t)N->cap[2]))) return rc;
-    if (N->cap[3] > 0)
-      if (const int rc = wm_check(N->alloc(&N->flag, sizeof(int) * (size_t)N->cap[3]))) return rc;
-    if (W != nullptr)                                    // an earlier call's kernel may still use the smaller blocks
-      if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-    b.mspf = std::move(N);
-    W = static_cast<MspfWs*>(b.mspf.get());
-  }
-  *out = W;
-  return WM_OK;
+  int64_t cap[4];
+  const MspfWs* old = static_cast<const MspfWs*>(b.mspf.get());
+  for (int i = 0; i < 4; ++i) cap[i] = old != nullptr && old->cap[i] > need[i] ? old->cap[i] : need[i];
+  auto fits = [&](const MspfWs& w) { return w.cap[0] >= need[0] && w.cap[1] >= need[1] && w.cap[2] >= need[2] && w.cap[3] >= need[3]; };
+  return grow_ws(b.mspf, st, *out, fits, [&](MspfWs& n) {
+    for (int i = 0; i < 4; ++i) n.cap[i] = cap[i];
+    if (cap[0] > 0)
+      if (const int rc = wm_check(n.alloc(&n.mean, sizeof(double) * (size_t)cap[0]))) return rc;
+    if (cap[1] > 0)
+      if (const int rc = wm_check(n.alloc(&n.tab, sizeof(double) * (size_t)cap[1]))) return rc;
+    if (cap[2] > 0)
+      if (const int rc = wm_check(n.alloc(&n.part, sizeof(double) * (size_t)cap[2]))) return rc;
+    return cap[3] > 0 ? wm_check(n.alloc(&n.flag, sizeof(int) * (size_t)cap[3])) : WM_OK;
+  });
 }
 
 static void mspf_args(const WorldMi355MspfOption& opt, int dim, int max_len, MspfArgs* a) {

@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256) void utterance_status_kernel(
   if (threadIdx.x == 0) status[u] = flags;
 }
 
-int launch_utterance_status(Batch& b, const double* d_x, const double* d_f0, const double* d_sp, const double* d_ap,
-                            int* d_status) {
+int launch_utterance_status(Batch& b, hipStream_t st, const double* d_x, const double* d_f0, const double* d_sp,
+                            const double* d_ap, int* d_status) {
   if (!d_status) return WM_ERR_BAD_ARG;
   const int vrm = (int)(0.5 + 1000.0 / b.p.frame_period / b.p.f0_floor) * 2 + 1;   // dio.cpp:263-264
   // fft_size_d4c (d4c.cpp:344-346); the rare-frame kernel exists up to 4096 points
@@ -69,7 +69,7 @@ int launch_utterance_status(Batch& b, const double* d_x, const double* d_f0, con
   // flagged here; d4c_wide_kernel analyses them now, so WM_UTT_D4C_DEFAULT_ROWS is never set any more)
   const int bin_limit = 0;
   (void)fd;
-  hipLaunchKernelGGL(utterance_status_kernel, dim3(b.n_utt), dim3(256), 0, b.ctx->stream, b.total_x > 0 ? d_x : nullptr,
+  hipLaunchKernelGGL(utterance_status_kernel, dim3(b.n_utt), dim3(256), 0, st, b.total_x > 0 ? d_x : nullptr,
                      b.d_x_off, b.d_x_len, b.d_f_off, d_f0, d_sp, d_ap, b.p.fft_size / 2 + 1, vrm, (double)fd / b.p.fs,
                      bin_limit, d_status);
   return wm_check(hipGetLastError());

@@ -244,11 +244,7 @@ __global__ __launch_bounds__(256) void stonemask_kernel(
   }
 }
 
-// f0_lower is the caller's guarantee that every non-zero f0 is at least this (behind Dio: its floor); the kernel no
-// longer sizes anything by it.
-int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const double* d_f0, double* d_out,
-                     double f0_lower) {
-  (void)f0_lower;
+int launch_stonemask(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_out) {
   Context& c = *b.ctx;
   const int fs = b.p.fs;
   const int64_t tf = b.total_f;
@@ -257,9 +253,9 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
   int rc = c.table({kSmTwiddles, {}}, twid, [&](Table& t) {
     int r = wm_check(t.alloc(&t.d[0], sizeof(cpx) * (size_t)kSmTwid));
     if (r) return r;
-    hipLaunchKernelGGL(sm_twiddle_kernel, dim3(kSmTwid / 256), dim3(256), 0, c.stream, (cpx*)t.d[0]);
+    hipLaunchKernelGGL(sm_twiddle_kernel, dim3(kSmTwid / 256), dim3(256), 0, st, (cpx*)t.d[0]);
     r = wm_check(hipGetLastError());
-    return r ? r : wm_check(hipStreamSynchronize(c.stream));   // later calls may come on other streams
+    return r ? r : wm_check(hipStreamSynchronize(st));   // later calls may come on other streams
   });
   if (rc) return rc;
   // The output is cleared before the list is made from d_f0: the two must not be the same array (the reference's
@@ -268,13 +264,13 @@ int launch_stonemask(Batch& b, const double* d_x, const double* d_t, const doubl
     set_error("StoneMask: refined_f0 must not alias f0");
     return WM_ERR_BAD_ARG;
   }
-  rc = wm_check(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)tf, c.stream));    // stonemask.cpp:186-187
+  rc = wm_check(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)tf, st));    // stonemask.cpp:186-187
   if (rc) return rc;
-  TimedScope ts_(b.ctx, c.stream, "stonemask_kernel");
-  launch_partition(c.stream, StoneMaskPred{d_f0, fs / 12.0}, (int)tf, b.d_part_cnt, b.d_perm, b.d_part_n);
+  TimedScope ts_(b.ctx, st, "stonemask_kernel");
+  launch_partition(st, StoneMaskPred{d_f0, fs / 12.0}, (int)tf, b.d_part_cnt, b.d_perm, b.d_part_n);
   const int64_t chunks = (tf + kSmChunk - 1) / kSmChunk;
   const int64_t cap = (int64_t)c.num_cu * 64;
-  hipLaunchKernelGGL(stonemask_kernel, dim3((unsigned)(chunks < cap ? chunks : cap)), dim3(256), 0, c.stream, d_x, b.d_x_off,
+  hipLaunchKernelGGL(stonemask_kernel, dim3((unsigned)(chunks < cap ? chunks : cap)), dim3(256), 0, st, d_x, b.d_x_off,
                      b.d_x_len, b.d_frame_utt, d_t, d_f0, fs, (const int*)b.d_perm, (const int*)b.d_part_n,
                      (const cpx*)twid->d[0], d_out);
   return wm_check(hipGetLastError());

@@ -995,8 +995,7 @@ static int synthesis_arena(Batch& b, hipStream_t st) {
   // one allocation for the work arrays of this batch (sections aligned to 256 bytes)
   const size_t ny = (size_t)b.total_y, nu = (size_t)b.n_utt;
   const size_t tiles = (size_t)((b.max_y_len + kSearchTile - 1) / kSearchTile + 1);
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = (at + (bytes ? bytes : 8) + 255) & ~(size_t)255; return o; };
+  Sections take;
   const size_t o_idx = take(4 * ny), o_shift = take(8 * ny), o_vuv = take(8 * ny), o_phase = take(8 * ny);
   const size_t o_cnt = take(4 * nu), o_tile = take(4 * nu * tiles), o_off = take(8 * (nu + 1));
   const size_t o_first = take(4 * (ny / kOlaStep + 2 * nu + 4));
@@ -1012,7 +1011,7 @@ static int synthesis_arena(Batch& b, hipStream_t st) {
   if (rc) return rc;
   std::unique_ptr<SynWs> W(new SynWs());
   unsigned char* base = nullptr;
-  rc = wm_check(W->alloc(&base, at));
+  rc = wm_check(W->alloc(&base, take.at));
   if (rc) return rc;
   if (!c.pulse) {                   // per context: two pinned, device-visible integers
     std::unique_ptr<PulseInfo> pi(new PulseInfo());
@@ -1261,9 +1260,8 @@ int synthesis_render(Batch& b, hipStream_t st, const double* d_sp, const double*
 }
 
 // ---- Synthesis alone: the batch in two parts (see the top of this section) ----
-int launch_synthesis(Batch& b, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y) {
+int launch_synthesis(Batch& b, hipStream_t st, const double* d_f0, const double* d_sp, const double* d_ap, double* d_y) {
   Context& c = *b.ctx;
-  const hipStream_t st = c.stream;
   // worth it from a few hundred thousand output samples per part on: below, the parts do not fill the machine
   if (b.n_utt < 16 || b.total_y < (int64_t)4 << 20) {
     int rc = synthesis_prepare(b, st, d_f0, d_y);

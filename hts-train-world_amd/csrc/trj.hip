@@ -523,20 +523,15 @@ int launch_trj(Batch& b, hipStream_t st, int n_streams, const float* const* pred
   }
   const int64_t tab_off = need;
   need += (int64_t)b.n_utt * D * kTrjTerms;
-  TrjWs* W = static_cast<TrjWs*>(b.trj.get());
-  if (W == nullptr || W->cap < need || W->cap_utt < b.n_utt) {
-    if (W != nullptr) {                                  // an earlier call's kernels may still use the smaller block;
-      if (const int rc = wm_check(hipStreamSynchronize(st))) return rc;
-      b.trj.reset();                                     // released first: the two never exist side by side
-    }
-    std::unique_ptr<TrjWs> N(new TrjWs());
-    if (const int rc = wm_check(N->alloc(&N->d, sizeof(double) * (size_t)need))) return rc;
-    if (const int rc = wm_check(N->alloc(&N->status, sizeof(int) * (size_t)b.n_utt))) return rc;
-    N->cap = need;
-    N->cap_utt = b.n_utt;
-    b.trj = std::move(N);
-    W = static_cast<TrjWs*>(b.trj.get());
-  }
+  TrjWs* W = nullptr;
+  if (const int rc = grow_ws(b.trj, st, W, [&](const TrjWs& w) { return w.cap >= need && w.cap_utt >= b.n_utt; },
+                             [&](TrjWs& n) {
+                               n.cap = need;
+                               n.cap_utt = b.n_utt;
+                               if (const int rc = wm_check(n.alloc(&n.d, sizeof(double) * (size_t)need))) return rc;
+                               return wm_check(n.alloc(&n.status, sizeof(int) * (size_t)b.n_utt));
+                             }))
+    return rc;
   if (d_status == nullptr) d_status = W->status;
   if (const int rc = wm_check(hipMemsetAsync(d_status, 0, sizeof(int) * (size_t)b.n_utt, st))) return rc;
   TimedScope ts_(b.ctx, st, "trj_kernel");

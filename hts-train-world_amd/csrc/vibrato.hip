@@ -266,10 +266,9 @@ struct VibWs : StageWs {           // the batch's Vibrato state (Batch::vibrato)
   int64_t total_slots = 0;
 };
 
-int launch_vibrato(Batch& b, const float* d_lf0, const int* seg_utt_off, const int* seg_start, const int* seg_end,
-                   const double* seg_pitch, float* d_vib, float* d_lf0_out, int* n_too_long) {
+int launch_vibrato(Batch& b, hipStream_t st, const float* d_lf0, const int* seg_utt_off, const int* seg_start,
+                   const int* seg_end, const double* seg_pitch, float* d_vib, float* d_lf0_out, int* n_too_long) {
   if (!d_lf0 || !seg_utt_off || !d_vib || !d_lf0_out) return WM_ERR_BAD_ARG;
-  hipStream_t st = b.ctx->stream;
   int rc = WM_OK;
   if (!b.vibrato) {
     std::unique_ptr<VibWs> W(new VibWs());

@@ -26,6 +26,8 @@ extern "C" long HipStubLaunches();
 extern "C" long HipStubCreations();
 extern "C" long HipStubDevPtrs();
 extern "C" void HipStubNextPulses(long index);
+extern "C" void HipStubFailMallocAfter(long n);
+namespace wm { void dev_cache_trim(size_t keep_bytes); }     // the library's block cache (csrc/batch.hpp)
 extern "C" void HipStubTraceMark(const char* text);
 extern "C" void HipStubTraceStream(const char* label, void* stream);
 
@@ -438,9 +440,150 @@ static int stream_sequence() {
   return 0;
 }
 
+// `capi_harness grow`: the six stages that replace their batch workspace when a call needs a larger one (parameter
+// generation, the trajectory cost, the acoustic model's forward and training passes, the modulation-spectrum postfilter,
+// label features), each on a batch of its own, on a context whose stream is not the default one: a small call; a larger
+// one whose device allocations fail (the block cache is emptied first, so the request reaches the stub's hipMalloc, which
+// refuses from there on: HIP_STUB_FAIL_MALLOC_AFTER set mid-run) and which must return WM_ERR_HIP; the same call again,
+// which must succeed; the small call again.  The larger sizes are at least four times the smaller, i.e. another size
+// class of the cache.  No per-utterance status array is passed: a stage clears the caller's before it looks at its
+// workspace, and the trace is read for "the wait comes before the call's first work" (tests/test_sanitizers.py).
+template <class Small, class Large> static bool grow_case(const char* stage, Small small, Large large) {
+  auto run = [&](const char* what, int want, auto& call) {
+    char mark[96];
+    snprintf(mark, sizeof(mark), "step %s: %s", stage, what);
+    HipStubTraceMark(mark);
+    const int rc = call();
+    printf("%s: rc %d\n", mark, rc);
+    return rc == want;
+  };
+  if (!run("small", WM_OK, small)) return false;
+  wm::dev_cache_trim(0);
+  HipStubFailMallocAfter(HipStubMallocs());
+  const bool refused = run("larger, allocation fails", WM_ERR_HIP, large);
+  HipStubFailMallocAfter(-1);
+  return refused && run("larger again", WM_OK, large) && run("small again", WM_OK, small);
+}
+static int grow_sequence() {
+  hipStream_t U = nullptr;
+  if (hipStreamCreateWithFlags(&U, hipStreamNonBlocking) != hipSuccess || !U) return 60;
+  HipStubTraceStream("null", nullptr);
+  HipStubTraceStream("U", U);
+  WorldMi355Params p;
+  WorldMi355DefaultParams(16000, 5.0, &p);
+  WorldMi355Context* ctx = nullptr;
+  if (WorldMi355CreateContext(-1, U, &ctx) != 0 || !ctx) return 61;
+  HipStubTraceMark("caller U");
+  std::vector<std::vector<unsigned char>> pool;
+  const int frames[3] = {5, 64, 33}, nu = 3, tf = 5 + 64 + 33;
+  WorldMi355Batch* bs[6] = {};
+  for (auto& b : bs)
+    if (WorldMi355CreateBatch(ctx, &p, nu, nullptr, frames, nullptr, &b) != 0) return 62;
+  // windows: static, delta, delta-delta; the delta window with 15 taps for the wider band
+  std::vector<double> w0{1.0}, w1{-0.5, 0.0, 0.5}, w2{1.0, -2.0, 1.0}, w15(15, 0.0);
+  for (int i = 0; i < 15; ++i) w15[(size_t)i] = (i - 7) / 28.0;
+  const double *wins[3] = {w0.data(), w1.data(), w2.data()}, *wins15[3] = {w0.data(), w15.data(), w2.data()};
+  const int sizes3[3] = {1, 3, 3}, sizes15[3] = {1, 15, 3};
+  const double* const* windows[1] = {wins};
+  const double* const* windows15[1] = {wins15};
+  const int *sizes[1] = {sizes3}, *sizes_15[1] = {sizes15};
+  const int nwin[1] = {3}, dims2[1] = {2}, dims8[1] = {8};
+  float* data = dev(pool, (size_t)tf * 24, 0.5f);                          // rows of up to 8 columns x 3 windows
+  float *var = dev(pool, 24, 1.0f), *gv = dev(pool, 8, 1.0f), *traj = dev(pool, (size_t)tf * 8, 0.0f);
+  float* gpred = dev(pool, (size_t)tf * 24, 0.0f);
+  const float *means[1] = {data}, *vars[1] = {var}, *gvs[1] = {gv};
+  float *outs[1] = {traj}, *gpreds[1] = {gpred};
+  bool ok = true;
+  {  // parameter generation: 3 taps, then 15 (the shapes of `streams`)
+    WorldMi355MlpgOption lo;
+    WorldMi355DefaultMlpgOption(&lo);
+    ok = ok && grow_case("ParameterGeneration", [&] {
+           return WorldMi355ParameterGeneration(bs[0], 1, means, 6, vars, 0, dims2, nwin, windows, sizes, nullptr, &lo, outs, nullptr);
+         }, [&] {
+           return WorldMi355ParameterGeneration(bs[0], 1, means, 6, vars, 0, dims2, nwin, windows15, sizes_15, nullptr, &lo, outs, nullptr);
+         });
+  }
+  {  // the trajectory cost: 2 columns, then 8
+    WorldMi355TrajectoryOption to;
+    WorldMi355DefaultTrajectoryOption(&to);
+    double *cost3 = dev(pool, (size_t)nu * 3, 0.0), *gvar = dev(pool, (size_t)nu * 24, 0.0);
+    auto call = [&](const int* dims, int row) {
+      return WorldMi355TrajectoryCost(bs[1], 1, means, means, row, vars, gvs, dims, nwin, windows, sizes, nullptr, nullptr, nullptr,
+                                      &to, cost3, outs, gpreds, nullptr, row, gvar, nullptr);
+    };
+    ok = ok && grow_case("TrajectoryCost", [&] { return call(dims2, 6); }, [&] { return call(dims8, 24); });
+  }
+  {  // the acoustic model, forward and training forward: one hidden layer of 4 units, then of 64
+    const int n_in = 3, n_out = 2, units4[1] = {4}, units64[1] = {64};
+    float *W0 = dev(pool, (size_t)n_in * 64, 0.1f), *W1 = dev(pool, (size_t)64 * n_out, 0.1f);
+    float *B0 = dev(pool, 64, 0.0f), *B1 = dev(pool, (size_t)n_out, 0.0f), *mvar = dev(pool, (size_t)n_out, 1.0f);
+    const float *weights[2] = {W0, W1}, *biases[2] = {B0, B1};
+    WorldMi355AcousticModel am;
+    memset(&am, 0, sizeof(am));
+    am.n_layers = 1; am.n_inputs = n_in; am.n_outputs = n_out; am.n_spkrs = 1;
+    am.hidden_activation = 2; am.output_activation = 0;
+    am.weights = weights; am.biases = biases; am.variances = mvar;
+    float *ax = dev(pool, (size_t)tf * n_in, 0.5f), *aout = dev(pool, (size_t)tf * n_out, 0.0f), *aobs = dev(pool, (size_t)tf * n_out, 0.25f);
+    float* gout = dev(pool, (size_t)tf * n_out, 0.0f);
+    double *acost = dev(pool, (size_t)nu, 0.0), *agvar = dev(pool, (size_t)nu * n_out, 0.0);
+    WorldMi355Dropout drop = {0.8f, 1u, 0u};
+    auto forward = [&](const int* units) {
+      am.units = units;
+      return WorldMi355AcousticModelForward(bs[2], &am, ax, n_in, nullptr, aout, n_out, aobs, n_out, acost, nullptr);
+    };
+    auto train = [&](const int* units) {
+      am.units = units;
+      return WorldMi355AcousticModelTrainForward(bs[3], &am, &drop, ax, n_in, nullptr, aout, n_out, aobs, n_out, acost, gout, n_out,
+                                                 agvar, nullptr);
+    };
+    ok = ok && grow_case("AcousticModelForward", [&] { return forward(units4); }, [&] { return forward(units64); });
+    ok = ok && grow_case("AcousticModelTrainForward", [&] { return train(units4); }, [&] { return train(units64); });
+  }
+  {  // the modulation-spectrum postfilter: 2 columns, then 64
+    WorldMi355MspfOption so;
+    WorldMi355DefaultMspfOption(&so);
+    const int K = 33;
+    std::vector<double> tab_mean((size_t)64 * K, 0.0), tab_std((size_t)64 * K, 1.0);
+    double *x64 = dev(pool, (size_t)tf * 64, 0.25), *o64 = dev(pool, (size_t)tf * 64, 0.0);
+    auto call = [&](int dim) {
+      return WorldMi355ModulationSpectrumPostfilter(bs[4], x64, dim, &so, tab_mean.data(), tab_std.data(), tab_mean.data(),
+                                                    tab_std.data(), o64, nullptr);
+    };
+    ok = ok && grow_case("ModulationSpectrumPostfilter", [&] { return call(2); }, [&] { return call(64); });
+  }
+  {  // label features: four lines over the three utterances, then a line per frame
+    const WorldMi355LabelFeature feats[4] = {{0, "*-a+*", 0, 0}, {0, "*-b+*,*-c+*", 0, 0}, {1, "*/A:%d_*", 0, 10}, {6, nullptr, 0, 70}};
+    WorldMi355LabelFeatureSet* set = nullptr;
+    if (WorldMi355CreateLabelFeatureSet(ctx, 4, feats, &set) != 0) return 63;
+    const char* names[4] = {"x^x-a+b=c/A:3_1", "x^a-b+c=x/A:12_2", "a^b-c+x=x/A:0_3", "x^x-a+b=c/A:3_1"};
+    const int line_off[4] = {0, 1, 3, 4}, lstart[4] = {0, 0, 30, 0}, lend[4] = {5, 30, 64, 33}, lstate[4] = {0, 0, 0, 0};
+    const int level[3] = {0, 0, 0}, line_off_f[4] = {0, 5, 5 + 64, tf};
+    std::vector<int> fstart((size_t)tf), fend((size_t)tf), fstate((size_t)tf, 0);
+    std::vector<const char*> fnames((size_t)tf);
+    for (int u = 0, i = 0; u < nu; ++u)
+      for (int k = 0; k < frames[u]; ++k, ++i) { fstart[(size_t)i] = k; fend[(size_t)i] = k + 1; fnames[(size_t)i] = names[i % 3]; }
+    float* ffi = dev(pool, (size_t)tf * 4, 0.0f);
+    ok = ok && grow_case("LabelFeatures", [&] {
+           return WorldMi355LabelFeatures(bs[5], set, line_off, lstart, lend, lstate, names, level, ffi, 4, nullptr);
+         }, [&] {
+           return WorldMi355LabelFeatures(bs[5], set, line_off_f, fstart.data(), fend.data(), fstate.data(), fnames.data(), level, ffi, 4, nullptr);
+         });
+    HipStubTraceMark("step the feature set goes");
+    WorldMi355DestroyLabelFeatureSet(set);
+  }
+  HipStubTraceMark("step teardown");
+  if (!ok || WorldMi355Synchronize(ctx) != 0) return 65;
+  for (auto b : bs) WorldMi355DestroyBatch(b);
+  WorldMi355DestroyContext(ctx);
+  (void)hipStreamDestroy(U);
+  printf("capi grow ok: %ld device allocations, %ld launches\n", HipStubMallocs(), HipStubLaunches());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && strcmp(argv[1], "batched") == 0) return batched_sequence();
   if (argc > 1 && strcmp(argv[1], "streams") == 0) return stream_sequence();
+  if (argc > 1 && strcmp(argv[1], "grow") == 0) return grow_sequence();
   int last_code = 0;
   if (getenv("HIP_STUB_DEVICES") && atoi(getenv("HIP_STUB_DEVICES")) == 0) {
     // no device: the drop-in entry points report to the handler and return (reference entry points are void)
@@ -483,6 +626,21 @@ int main(int argc, char** argv) {
     InitializeDioOption(&dopt);
     Dio(x.data(), 0, 16000, &dopt, t.data(), f0.data());    // empty
     if (g_handler_calls == before) { printf("refusals did not reach the handler\n"); return 4; }
+    // a NULL batch is refused by every batched entry point, the older ones (Dio ... UtteranceStatus) included
+    double* d = x.data();
+    float* q = nullptr;
+    const int null_batch[] = {
+        WorldMi355Dio(nullptr, d, d, d), WorldMi355Harvest(nullptr, d, d, d), WorldMi355StoneMask(nullptr, d, d, d, d),
+        WorldMi355CheapTrick(nullptr, d, d, d, d), WorldMi355D4C(nullptr, d, d, d, d), WorldMi355Synthesis(nullptr, d, d, d, d),
+        WorldMi355Analyze(nullptr, d, d, d, d, d), WorldMi355AnalyzeSynthesize(nullptr, d, d, d, d, d, d),
+        WorldMi355CodeSpectralEnvelope(nullptr, d, 20, d), WorldMi355DecodeSpectralEnvelope(nullptr, d, 20, d),
+        WorldMi355CodeAperiodicity(nullptr, d, d), WorldMi355DecodeAperiodicity(nullptr, d, d),
+        WorldMi355RecipeFeatures(nullptr, d, d, d, 20, 5, q, q, q), WorldMi355RecipeDecode(nullptr, q, q, q, 20, 5, d, d, d),
+        WorldMi355SamplesFromPcm16(nullptr, nullptr, d), WorldMi355SamplesToPcm16(nullptr, d, nullptr),
+        WorldMi355Vibrato(nullptr, q, nullptr, nullptr, nullptr, d, q, q, nullptr),
+        WorldMi355UtteranceStatus(nullptr, d, d, d, d, nullptr)};
+    for (int rc : null_batch)
+      if (rc != WM_ERR_BAD_ARG) { printf("a NULL batch was answered with %d\n", rc); return 4; }
   }
   // the batched API: create, analyze into caller buffers, destroy -- and a context torn down with work behind it
   {

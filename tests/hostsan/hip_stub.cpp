@@ -92,6 +92,10 @@ long HipStubLaunches() { return g_launches.load(); }
 long HipStubCreations() { return g_creations.load(); }       // streams and untimed events asked for so far
 long HipStubDevPtrs() { return g_devptrs.load(); }
 void HipStubNextPulses(long index) { g_pulse_launches = index; }   // which entry of HIP_STUB_PULSES comes next
+void HipStubFailMallocAfter(long n) {                        // HIP_STUB_FAIL_MALLOC_AFTER, set by the harness mid-run; n < 0: off
+  g_fail_malloc_after_set = n >= 0;
+  g_fail_malloc_after = n;
+}
 void HipStubTraceMark(const char* text) {                    // a line of the harness's own in the trace ("# ...")
   if (!g_trace) return;
   std::lock_guard<std::mutex> g(g_trace_mu);

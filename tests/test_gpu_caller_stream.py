@@ -636,6 +636,34 @@ def test_acoustic_model_regrows_its_workspace_behind_a_pending_call(env):
     b.close()
 
 
+def test_training_pass_replaces_the_forward_workspace_behind_a_pending_call(env):
+    """A forward pass (max_chunk_frames 16) pending, then a training forward pass at keep_prob 1 at once on the same batch:
+    the forward pass's workspace is replaced by the training pass's larger one (dnn_train.hip, dnn_train_ws), which must
+    wait for the pending kernels first.  The same utterances (LENGTHS) and 3-layer SD case (65 -> 129 -> 31 units) as the
+    test above; the forward pass within test_gpu_dnn.py's bound, the training pass within test_gpu_dnn_train.py's."""
+    torch = env.torch
+    hidden, output = "tanh", "linear"
+    params, x, spkr, ref, e = DR.cached_case(3, "sd", hidden, output, LENGTHS)
+    last = params["variance.variances"].shape[0] - 1                 # spkr None: every utterance is the last speaker's
+    sr = DR.spkr_rows(LENGTHS, spkr if spkr is not None else [last] * len(LENGTHS))
+    fw = DT.train_forward(params, x, sr, hidden, output, 1.0, T_TRAIN.SEED, T_TRAIN.OFFSET)
+    model = T_DNN.model_dict(torch, params, hidden, output)
+    b = raw_frames_batch(env, LENGTHS)
+    xd, fresh = torch.from_numpy(np.roll(x, 1, axis=0).copy()).cuda(), torch.from_numpy(np.array(x)).cuda()
+    x2 = fresh.clone()
+    env.U.synchronize()
+    (o1, _, s1), done, pending = env.behind_delay([xd], [fresh], lambda: b.acoustic_model_forward(model, xd, spkr, None, 16))
+    o2, _, s2 = b.acoustic_model_train_forward(model, x2, spkr, None, 1.0, T_TRAIN.SEED, T_TRAIN.OFFSET)
+    waited = done.query()
+    g1, g2 = o1.clone(), o2.clone()
+    env.U.synchronize()
+    assert pending and waited
+    assert (np.abs(host(g1).astype(np.float64) - ref) <= e).all()
+    assert (np.abs(host(g2).astype(np.float64) - fw["out"]) <= fw["e_out"]).all()
+    assert (host(s1) == 0).all() and (host(s2) == 0).all()
+    b.close()
+
+
 def test_vibrato_twice_with_other_pitches(env, oracle):
     torch = env.torch
     l, segs = T_VIB.synth_lf0(700, 4, T_VIB.NOTES)

@@ -284,3 +284,55 @@ def test_every_entry_point_keeps_to_the_callers_stream(tmp_path, capi_harness):
     assert any("hipDeviceSynchronize" in l for l in lines)                  # the split Synthesis's third piece
     assert bad == [], bad[:10]
     assert stats["unforked"] == 0                                           # no step needed the upload rule
+
+
+GROW_STAGES = ("ParameterGeneration", "TrajectoryCost", "AcousticModelForward", "AcousticModelTrainForward",
+               "ModulationSpectrumPostfilter", "LabelFeatures")
+
+
+def test_a_workspace_that_must_grow_is_replaced_by_one_rule(tmp_path, capi_harness):
+    """`capi_harness grow` (a stand-alone program under AddressSanitizer + UBSan + LeakSanitizer, against the stub
+    runtime): each of the six stages that keep their workspace with grow_ws() (csrc/batch.hpp), on a context whose
+    stream U is not the default one, makes a small call, a larger call whose device allocations fail (the block cache
+    is emptied first, so the request reaches the stub), the same call again and the small call again.  The harness
+    itself checks the return codes: WM_OK, WM_ERR_HIP, WM_OK, WM_OK.  Nothing may leak or touch freed memory.  In the
+    trace, per stage: the first build waits for nothing; the replacement waits for U exactly once, before anything is
+    queued, and the failed attempt queues nothing at all; the retry finds the slot empty and builds afresh without a
+    wait; the small call fits what is there.  Label features alone wait on every call that keeps its workspace (the
+    host image of its upload is reused): once, and first.  The whole trace obeys tests/stream_rules.py."""
+    trace_file = tmp_path / "grow.txt"
+    p = subprocess.run([str(capi_harness), "grow"], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, HIP_STUB_TRACE=str(trace_file), **SAN_ENV))
+    text = p.stdout + p.stderr
+    assert p.returncode == 0 and "capi grow ok" in text, text[-4000:]
+    assert "AddressSanitizer" not in text and "LeakSanitizer" not in text and "runtime error" not in text, text[-4000:]
+    lines = trace_file.read_text().splitlines()
+    assert lines[:3] == ["# stream null s0", "# stream U s1", "# caller U"]
+    body = {}
+    for l in lines[3:]:
+        if l.startswith("# step "):
+            cur = body.setdefault(l[len("# step "):], [])
+        else:
+            cur.append(l)
+    want = [f"{s}: {w}" for s in GROW_STAGES for w in ("small", "larger, allocation fails", "larger again", "small again")]
+    assert list(body)[:len(want)] == want
+
+    def is_work(call):
+        return call.startswith(("launch ", "hipMemcpyAsync", "hipMemsetAsync"))
+    for stage in GROW_STAGES:
+        first, failed, again, small = (body[f"{stage}: {w}"] for w in ("small", "larger, allocation fails", "larger again",
+                                                                        "small again"))
+        assert not any("Synchronize" in c for c in first) and any(is_work(c) for c in first), stage
+        assert failed == ["hipStreamSynchronize s1"], (stage, failed)
+        assert not any("Synchronize" in c for c in again) and any(is_work(c) for c in again), stage
+        # the replacement as a whole: one wait for the caller's stream, before the first work
+        grown = failed + again
+        assert [c for c in grown if "Synchronize" in c] == ["hipStreamSynchronize s1"], stage
+        assert grown.index("hipStreamSynchronize s1") < min(i for i, c in enumerate(grown) if is_work(c)), stage
+        kept_waits = ["hipStreamSynchronize s1"] if stage == "LabelFeatures" else []
+        assert [c for c in small if "Synchronize" in c] == kept_waits and small[:len(kept_waits)] == kept_waits, stage
+        assert [c for c in small if is_work(c)] == [c for c in first if is_work(c)], stage
+    bad, stats = _violations(lines)
+    print("grow trace: %d lines," % len(lines), stats)
+    assert bad == [], bad[:10]
+    assert stats["unforked"] == 0 and stats["side_streams"] == 0
