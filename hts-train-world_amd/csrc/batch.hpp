@@ -30,6 +30,7 @@ void set_error(const char* msg);
 hipError_t dev_alloc_bytes(void** p, size_t bytes);
 void dev_free(void* p);
 void dev_cache_trim(size_t keep_bytes);       // hipFree cached blocks until at most keep_bytes stay cached
+size_t dev_alloc_size(size_t bytes);          // what a request of `bytes` takes from the device: its size class (host only)
 template <class T> inline hipError_t dev_alloc(T** p, size_t bytes) { return dev_alloc_bytes((void**)p, bytes); }
 
 struct NoCopy {                               // base of what frees or restores something in its destructor
@@ -283,6 +284,10 @@ struct Batch {
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
   std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn, ffi;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
+  // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
+  // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
+  int f0_estimator = WM_F0_DIO;
+  int f0_refine = 1;
 
   int64_t rng_bound_cheaptrick() const;
   int64_t rng_bound_d4c() const;
@@ -296,6 +301,11 @@ struct Batch {
 // the `st` of the call that builds it.
 int launch_dio(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0);
 int launch_harvest(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0);
+// What Harvest's set-up takes from the device for a batch of these sample counts (harvest.hip, HvPlan: the sizes the set-up
+// itself allocates from).  Host only.  WM_ERR_UNSUPPORTED where the set-up would refuse the f0 range.
+int harvest_workspace_bytes(const WorldMi355Params& p, int n_utt, const int* x_len, int64_t* bytes);
+// the f0 front end of the one-call forms: the batch's estimator, and StoneMask behind it when the batch says so (context.cpp)
+int launch_f0(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0);
 int launch_stonemask(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_out);
 int launch_cheaptrick(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_sp);
 int launch_d4c(Batch& b, hipStream_t st, const double* d_x, const double* d_t, const double* d_f0, double* d_ap);

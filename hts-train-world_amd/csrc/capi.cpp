@@ -520,6 +520,30 @@ int WorldMi355AnalyzeSynthesize(WorldMi355Batch* hb, const double* x, double* t,
                                 double* ap, double* y) {
   return on_batch(hb, launch_analyze_synthesize, x, t, f0, sp, ap, y);
 }
+int WorldMi355BatchSetF0Estimator(WorldMi355Batch* hb, int estimator, int refine) {
+  if (!hb || (estimator != WM_F0_DIO && estimator != WM_F0_HARVEST) || (refine != 0 && refine != 1) || hb->b.total_x <= 0) {
+    wm::set_error("BatchSetF0Estimator: a batch with x_lengths, WM_F0_DIO or WM_F0_HARVEST, refine 0 or 1");
+    return WM_ERR_BAD_ARG;
+  }
+  hb->b.f0_estimator = estimator;                // host state only: the next one-call form reads it (launch_f0)
+  hb->b.f0_refine = refine;
+  return WM_OK;
+}
+int WorldMi355BatchGetF0Estimator(const WorldMi355Batch* hb, int* estimator, int* refine) {
+  if (!hb || !estimator || !refine) return WM_ERR_BAD_ARG;
+  *estimator = hb->b.f0_estimator;
+  *refine = hb->b.f0_refine;
+  return WM_OK;
+}
+int WorldMi355HarvestWorkspaceBytes(const WorldMi355Params* p, int n_utt, const int* x_lengths, int64_t* bytes) {
+  bool ok = p && x_lengths && bytes && n_utt > 0 && p->fs > 0 && p->f0_floor > 0.0 && p->f0_ceil > p->f0_floor;
+  for (int u = 0; ok && u < n_utt; ++u) ok = x_lengths[u] > 0;
+  if (!ok) {
+    wm::set_error("HarvestWorkspaceBytes: bad argument");
+    return WM_ERR_BAD_ARG;
+  }
+  return harvest_workspace_bytes(*p, n_utt, x_lengths, bytes);
+}
 int WorldMi355Vibrato(WorldMi355Batch* hb, const float* lf0, const int* seg_utt_off, const int* seg_start,
                       const int* seg_end, const double* seg_pitch, float* vib, float* lf0_out, int* n_too_long) {
   return on_batch(hb, launch_vibrato, lf0, seg_utt_off, seg_start, seg_end, seg_pitch, vib, lf0_out, n_too_long);

@@ -48,6 +48,9 @@ size_t size_class(size_t bytes) {
   const size_t step = p2 >> 4;                       // p2/2 < bytes <= p2: steps of p2/16
   return (bytes + step - 1) / step * step;
 }
+}  // namespace
+size_t dev_alloc_size(size_t bytes) { return size_class(bytes); }
+namespace {
 int current_device() {
   int d = 0;
   (void)hipGetDevice(&d);
@@ -271,11 +274,19 @@ static int d4c_after(Batch& b, hipStream_t st, const double* d_x, const double* 
   return rc ? rc : wm_check(hipStreamWaitEvent(st, s.ev_rare, 0));
 }
 
-// Dio -> StoneMask -> CheapTrick -> D4C, one behind the other on `st`
+// The f0 front end of the one-call forms on `st`: the batch's estimator (Dio unless WorldMi355BatchSetF0Estimator said
+// Harvest), into d_f0_tmp with StoneMask behind it, or straight into d_f0 where the batch asks for no refinement.
+int launch_f0(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0) {
+  double* raw = b.f0_refine ? b.d_f0_tmp : d_f0;
+  int rc = b.f0_estimator == WM_F0_HARVEST ? launch_harvest(b, st, d_x, d_t, raw) : launch_dio(b, st, d_x, d_t, raw);
+  if (rc || !b.f0_refine) return rc;
+  return launch_stonemask(b, st, d_x, d_t, raw, d_f0);
+}
+
+// f0 (launch_f0) -> CheapTrick -> D4C, one behind the other on `st`
 static int analyze_in_order(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
                             double* d_ap) {
-  int rc = launch_dio(b, st, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, st, d_x, d_t, b.d_f0_tmp, d_f0);
+  int rc = launch_f0(b, st, d_x, d_t, d_f0);
   rc = rc ? rc : launch_cheaptrick(b, st, d_x, d_t, d_f0, d_sp);
   return rc ? rc : launch_d4c(b, st, d_x, d_t, d_f0, d_ap);
 }
@@ -283,8 +294,7 @@ static int analyze_in_order(Batch& b, hipStream_t st, const double* d_x, double*
 static int analyze_forked(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,
                           double* d_ap) {
   Context& c = *b.ctx;
-  int rc = launch_dio(b, st, d_x, d_t, b.d_f0_tmp);
-  rc = rc ? rc : launch_stonemask(b, st, d_x, d_t, b.d_f0_tmp, d_f0);
+  int rc = launch_f0(b, st, d_x, d_t, d_f0);
   rc = rc ? rc : c.ensure_side();
   // the randn table must not move under two streams (it may be reallocated when it grows): settle its size first
   rc = rc ? rc : c.ensure_rng(std::max(b.rng_bound_cheaptrick(), b.rng_bound_d4c()), st);
@@ -295,7 +305,7 @@ static int analyze_forked(Batch& b, hipStream_t st, const double* d_x, double* d
   return rc ? rc : d4c_after(b, st, d_x, d_t, d_f0, d_ap);
 }
 
-// Dio -> StoneMask -> CheapTrick -> D4C as one call: D4C's preparation runs on the second stream beside CheapTrick
+// f0 -> CheapTrick -> D4C as one call: D4C's preparation runs on the second stream beside CheapTrick
 // once the batch has its D4C tables (the first use allocates them, in the plain order).
 int launch_analyze(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp, double* d_ap) {
   return b.d4c ? analyze_forked(b, st, d_x, d_t, d_f0, d_sp, d_ap) : analyze_in_order(b, st, d_x, d_t, d_f0, d_sp, d_ap);
@@ -303,7 +313,7 @@ int launch_analyze(Batch& b, hipStream_t st, const double* d_x, double* d_t, dou
 
 // Analysis followed by Synthesis of the same features (BASELINE.json's metric), as one call.  Identical
 // launches and results; the only difference is where the f0-only first part of Synthesis runs: on a second
-// stream, as soon as StoneMask has produced f0, beside CheapTrick and D4C.  Its kernels are latency chains on
+// stream, as soon as the f0 front end has produced f0, beside CheapTrick and D4C.  Its kernels are latency chains on
 // one wavefront per utterance (the phase accumulation) plus a host round trip for the pulse count, which would
 // otherwise sit between D4C and the pulse kernel with the machine idle.
 int launch_analyze_synthesize(Batch& b, hipStream_t st, const double* d_x, double* d_t, double* d_f0, double* d_sp,

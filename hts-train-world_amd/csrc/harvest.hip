@@ -1335,11 +1335,37 @@ __global__ __launch_bounds__(kCtThreads) void hv_contour_kernel(
 
 // ---- host side ------------------------------------------------------------------------------
 
-static int hv_setup(Batch& b, hipStream_t st) {
-  if (b.harvest) return WM_OK;
-  std::unique_ptr<HarvestWs> W(new HarvestWs());
-  HvMeta& m = W->m;
-  const WorldMi355Params& p = b.p;
+// The device blocks of a batch's Harvest state, in the order hv_setup makes them.
+enum HvBlock {
+  kHbYlen, kHbNb1, kHbYoff, kHbToff, kHbEvoff, kHbBoff, kHbMdoff, kHbSmoff, kHbFrameUtt, kHbRunUtt, kHbRunFirst, kHbBf, kHbHalf,
+  kHbTapoff, kHbTaps, kHbY, kHbMeanPart, kHbTmp, kHbEvcnt, kHbTileCnt, kHbSlotOff, kHbSlots, kHbRaw, kHbOffc, kHbCnt, kHbNcand1,
+  kHbRc, kHbRs, kHbRc2, kHbRs2, kHbWork, kHbBl, kHbMd, kHbMds, kHbSec, kHbSm, kHbTwid, kHbNtaps, kHbDelay, kHbSpectra, kHbCount
+};
+
+// Everything about a batch's Harvest state that follows from the parameters and the sample counts alone: the constants of
+// the f0 range, the per-utterance offsets, and the size of every device block.  hv_setup can only allocate through it
+// (by HvBlock), and harvest_workspace_bytes adds the same entries up, so the figure a caller plans with is the one the
+// set-up takes.  Host only: no device call.
+struct HvPlan {
+  HvMeta m;
+  std::vector<double> bf;                                     // per channel, centre frequency (:1155-1157)
+  std::vector<int> half;                                      // per channel, half window length (:101)
+  size_t n_taps = 0;                                          // taps of all channels
+  std::vector<int> ylen, nb1;
+  std::vector<int64_t> yoff, toff, evoff, boff, mdoff, smoff, soff;
+  int64_t n_runs = 0;
+  int tiles_max = 0;
+  int64_t bytes[kHbCount];                                    // of each block; -1: not made (for this decimation ratio / filter bank)
+  int make(const WorldMi355Params& p, int n_utt, const int* x_len);
+  int64_t total() const {                                     // what the blocks take from the device (dev_alloc_size)
+    int64_t sum = 0;
+    for (int i = 0; i < kHbCount; ++i)
+      if (bytes[i] >= 0) sum += (int64_t)dev_alloc_size(bytes[i] ? (size_t)bytes[i] : 8);
+    return sum;
+  }
+};
+
+int HvPlan::make(const WorldMi355Params& p, int n_utt, const int* x_len) {
   const double adj_floor = p.f0_floor * 0.9, adj_ceil = p.f0_ceil * 1.1;
   m.nch = 1 + (int)(log(adj_ceil / adj_floor) / kLog2 * 40);                 // :1151-1153
   m.r = imax(imin(matlab_round(p.fs / 8000.0), 12), 1);                      // :1227, :1160
@@ -1347,14 +1373,96 @@ static int hv_setup(Batch& b, hipStream_t st) {
   m.lag = m.r == 1 ? 0 : (int)(ceil(140.0 / m.r) * m.r);
   m.cpf = matlab_round(m.nch / 10.0);
   m.maxc = m.cpf * kHvOverlap;
-  if (m.maxc > 64 * kSelPer) return WM_ERR_UNSUPPORTED;   // hv_select_wave: candidates over lanes
-  std::vector<double> bf((size_t)m.nch), taps;
-  std::vector<int> half((size_t)m.nch), tapoff((size_t)m.nch);
+  if (m.nch < 1 || m.maxc > 64 * kSelPer) return WM_ERR_UNSUPPORTED;   // hv_select_wave: candidates over lanes
+  bf.resize((size_t)m.nch); half.resize((size_t)m.nch);
   m.ntap_max = 0;
+  n_taps = 0;
   for (int i = 0; i < m.nch; ++i) {
     bf[(size_t)i] = adj_floor * pow(2.0, (i + 1) / 40.0);                    // :1155-1157
-    const int hf = matlab_round(m.afs / bf[(size_t)i] * 2.0);               // :101
-    half[(size_t)i] = hf;
+    half[(size_t)i] = matlab_round(m.afs / bf[(size_t)i] * 2.0);             // :101
+    const int n = 2 * half[(size_t)i] + 1;
+    n_taps += (size_t)n;
+    m.ntap_max = imax(m.ntap_max, n);
+  }
+  m.half0 = (m.ntap_max - 1) / 2;
+  m.conv = m.ntap_max <= 1024 ? 2048 : 0;        // block FFT convolution where the longest filter fits half a block
+  m.step = m.conv ? imin(m.conv - m.ntap_max + 1 - 2, 64 * kHvConvC) : kZcStep;
+  const size_t nu = (size_t)n_utt;
+  ylen.resize(nu); nb1.resize(nu);
+  for (std::vector<int64_t>* v : {&yoff, &toff, &evoff, &boff, &mdoff, &smoff, &soff}) v->assign(nu + 1, 0);
+  int ymax = 1;
+  n_runs = 0;
+  for (size_t u = 0; u < nu; ++u) {
+    const int n = x_len[u];
+    const int yl = (int)ceil((double)n / m.r);                               // :1161-1162
+    const int nb = (int)(1000.0 * n / p.fs / 1) + 1;                         // GetSamplesForHarvest, 1 ms
+    ylen[u] = yl; nb1[u] = nb;
+    yoff[u + 1] = yoff[u] + yl;
+    toff[u + 1] = toff[u] + n + 2 * m.lag + 18;
+    evoff[u + 1] = evoff[u] + (int64_t)m.nch * 4 * (yl / 2 + 2);
+    boff[u + 1] = boff[u] + nb;
+    mdoff[u + 1] = mdoff[u] + 28LL * nb + 512;
+    smoff[u + 1] = smoff[u] + (int64_t)kSmPar * (nb + 2 * kSmLag);
+    soff[u + 1] = soff[u] + (int64_t)m.nch * 4 * hv_tiles(yl, m.step) * kZcSlot;   // the staged events of every tile
+    n_runs += (nb + kRawRun - 1) / kRawRun;
+    ymax = imax(ymax, yl);
+  }
+  tiles_max = hv_tiles(ymax, m.step);
+  const int64_t tot_b = boff[nu], i4 = sizeof(int), i8 = sizeof(int64_t), f8 = sizeof(double), n1 = (int64_t)nu + 1;
+  for (int i = 0; i < kHbCount; ++i) bytes[i] = -1;
+  bytes[kHbYlen] = bytes[kHbNb1] = i4 * (int64_t)nu;
+  for (int id : {kHbYoff, kHbToff, kHbEvoff, kHbBoff, kHbMdoff, kHbSmoff, kHbSlotOff}) bytes[id] = i8 * n1;
+  bytes[kHbFrameUtt] = i4 * tot_b;
+  bytes[kHbRunUtt] = bytes[kHbRunFirst] = i4 * n_runs;
+  bytes[kHbBf] = f8 * m.nch;
+  bytes[kHbHalf] = bytes[kHbTapoff] = i4 * (int64_t)m.nch;
+  bytes[kHbTaps] = f8 * (int64_t)n_taps;
+  bytes[kHbY] = f8 * yoff[nu];
+  bytes[kHbMeanPart] = f8 * (int64_t)nu * kHvMeanTiles;
+  if (m.r > 1) bytes[kHbTmp] = f8 * toff[nu];
+  // (the compacted event lists are gone: 0.58 GB at configs[2] that nobody reads any more)
+  bytes[kHbEvcnt] = i4 * (int64_t)nu * m.nch * 4;
+  bytes[kHbTileCnt] = i4 * (int64_t)nu * m.nch * 4 * ((int64_t)tiles_max + 1);
+  bytes[kHbSlots] = f8 * soff[nu];
+  bytes[kHbRaw] = f8 * tot_b * m.nch;
+  bytes[kHbOffc] = f8 * tot_b * m.cpf;
+  bytes[kHbCnt] = i4 * tot_b;
+  bytes[kHbNcand1] = i4 * (int64_t)nu;
+  bytes[kHbRc] = bytes[kHbRs] = bytes[kHbRc2] = bytes[kHbRs2] = f8 * tot_b * m.maxc;
+  bytes[kHbWork] = f8 * 4 * tot_b;
+  bytes[kHbBl] = i4 * 2 * (tot_b + 8 * (int64_t)nu);
+  bytes[kHbMd] = bytes[kHbMds] = f8 * mdoff[nu];
+  bytes[kHbSec] = i4 * 3 * (tot_b / 4 + 8 * (int64_t)nu + 8);
+  bytes[kHbSm] = f8 * smoff[nu];
+  bytes[kHbTwid] = (int64_t)sizeof(cpx) * kHvTwid;
+  if (m.conv) {
+    bytes[kHbNtaps] = bytes[kHbDelay] = i4 * (int64_t)m.nch;
+    bytes[kHbSpectra] = (int64_t)sizeof(cpx) * m.nch * (m.conv / 2 + 1);
+  }
+  return WM_OK;
+}
+
+int harvest_workspace_bytes(const WorldMi355Params& p, int n_utt, const int* x_len, int64_t* bytes) {
+  HvPlan plan;
+  const int rc = plan.make(p, n_utt, x_len);
+  if (!rc) *bytes = plan.total();
+  return rc;
+}
+
+static int hv_setup(Batch& b, hipStream_t st) {
+  if (b.harvest) return WM_OK;
+  HvPlan plan;
+  if (const int bad = plan.make(b.p, b.n_utt, b.x_len.data())) return bad;
+  std::unique_ptr<HarvestWs> W(new HarvestWs());
+  HvMeta& m = W->m;
+  m = plan.m;
+  const std::vector<double>& bf = plan.bf;
+  const std::vector<int>& half = plan.half;
+  std::vector<double> taps;
+  std::vector<int> tapoff((size_t)m.nch);
+  taps.reserve(plan.n_taps);
+  for (int i = 0; i < m.nch; ++i) {
+    const int hf = half[(size_t)i];
     tapoff[(size_t)i] = (int)taps.size();
     const int n = 2 * hf + 1;
     for (int k = 0; k < n; ++k) {                                            // :103-106
@@ -1363,97 +1471,72 @@ static int hv_setup(Batch& b, hipStream_t st) {
                        0.012604 * cos(6.0 * kPi * tmp);
       taps.push_back(w * cos(2 * kPi * bf[(size_t)i] * (k - hf) / m.afs));
     }
-    m.ntap_max = imax(m.ntap_max, n);
   }
-  m.half0 = (m.ntap_max - 1) / 2;
-  m.conv = m.ntap_max <= 1024 ? 2048 : 0;        // block FFT convolution where the longest filter fits half a block
-  m.step = m.conv ? imin(m.conv - m.ntap_max + 1 - 2, 64 * kHvConvC) : kZcStep;
   const int n_utt = b.n_utt;
-  W->ylen.resize((size_t)n_utt); W->nb1.resize((size_t)n_utt);
-  W->yoff.assign((size_t)n_utt + 1, 0); W->toff.assign((size_t)n_utt + 1, 0); W->evoff.assign((size_t)n_utt + 1, 0);
-  W->boff.assign((size_t)n_utt + 1, 0); W->mdoff.assign((size_t)n_utt + 1, 0); W->smoff.assign((size_t)n_utt + 1, 0);
-  for (int u = 0; u < n_utt; ++u) {
-    const int n = b.x_len[(size_t)u];
-    const int yl = (int)ceil((double)n / m.r);                               // :1161-1162
-    const int nb1 = (int)(1000.0 * n / p.fs / 1) + 1;                        // GetSamplesForHarvest, 1 ms
-    W->ylen[(size_t)u] = yl; W->nb1[(size_t)u] = nb1;
-    W->yoff[(size_t)u + 1] = W->yoff[(size_t)u] + yl;
-    W->toff[(size_t)u + 1] = W->toff[(size_t)u] + n + 2 * m.lag + 18;
-    W->evoff[(size_t)u + 1] = W->evoff[(size_t)u] + (int64_t)m.nch * 4 * (yl / 2 + 2);
-    W->boff[(size_t)u + 1] = W->boff[(size_t)u] + nb1;
-    W->mdoff[(size_t)u + 1] = W->mdoff[(size_t)u] + 28LL * nb1 + 512;
-    W->smoff[(size_t)u + 1] = W->smoff[(size_t)u] + (int64_t)kSmPar * (nb1 + 2 * kSmLag);
-  }
+  W->ylen = plan.ylen; W->nb1 = plan.nb1;
+  W->yoff = plan.yoff; W->toff = plan.toff; W->evoff = plan.evoff;
+  W->boff = plan.boff; W->mdoff = plan.mdoff; W->smoff = plan.smoff;
   W->tot_y = W->yoff[(size_t)n_utt]; W->tot_t = W->toff[(size_t)n_utt]; W->tot_ev = W->evoff[(size_t)n_utt];
   W->tot_b = W->boff[(size_t)n_utt]; W->tot_md = W->mdoff[(size_t)n_utt]; W->tot_sm = W->smoff[(size_t)n_utt];
+  W->n_runs = plan.n_runs;
+  W->tiles_max = plan.tiles_max;
   std::vector<int> bfu((size_t)W->tot_b);
   for (int u = 0; u < n_utt; ++u)
     for (int64_t i = W->boff[(size_t)u]; i < W->boff[(size_t)u + 1]; ++i) bfu[(size_t)i] = u;
+  std::vector<int> ru, rf;
+  for (int u = 0; u < n_utt; ++u)
+    for (int k = 0; k < W->nb1[(size_t)u]; k += kRawRun) { ru.push_back(u); rf.push_back(k); }
 
+  // every block is made by its HvBlock id, with the plan's size: `up` also fills it from `count` items at src
   int rc = WM_OK;
-  auto up = [&](void** dst, const void* src, size_t bytes) {
+  auto al = [&](auto** dst, HvBlock id) {
     if (rc) return;
-    rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
-    if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    const int64_t bytes = plan.bytes[id];
+    rc = bytes < 0 ? WM_ERR_BAD_ARG : wm_check(W->alloc(dst, bytes ? (size_t)bytes : 8));
   };
-  auto al = [&](void** dst, size_t bytes) {
-    if (rc) return;
-    rc = wm_check(W->alloc(dst, bytes ? bytes : 8));
+  auto up = [&](auto** dst, HvBlock id, const auto& src) {
+    const size_t bytes = sizeof(src[0]) * src.size();
+    if (!rc && (int64_t)bytes != plan.bytes[id]) rc = WM_ERR_BAD_ARG;      // the plan and the host image disagree: a bug
+    al(dst, id);
+    if (!rc && bytes) rc = wm_check(hipMemcpy(*dst, src.data(), bytes, hipMemcpyHostToDevice));
   };
-  up((void**)&W->d_ylen, W->ylen.data(), sizeof(int) * (size_t)n_utt);
-  up((void**)&W->d_nb1, W->nb1.data(), sizeof(int) * (size_t)n_utt);
-  up((void**)&W->d_yoff, W->yoff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_toff, W->toff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_evoff, W->evoff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_boff, W->boff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_mdoff, W->mdoff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_smoff, W->smoff.data(), sizeof(int64_t) * ((size_t)n_utt + 1));
-  up((void**)&W->d_bframe_utt, bfu.data(), sizeof(int) * bfu.size());
-  {
-    std::vector<int> ru, rf;
-    for (int u = 0; u < n_utt; ++u)
-      for (int k = 0; k < W->nb1[(size_t)u]; k += kRawRun) { ru.push_back(u); rf.push_back(k); }
-    W->n_runs = (int64_t)ru.size();
-    up((void**)&W->d_run_utt, ru.data(), sizeof(int) * ru.size());
-    up((void**)&W->d_run_first, rf.data(), sizeof(int) * rf.size());
-  }
-  up((void**)&W->d_bf, bf.data(), sizeof(double) * bf.size());
-  up((void**)&W->d_half, half.data(), sizeof(int) * half.size());
-  up((void**)&W->d_tapoff, tapoff.data(), sizeof(int) * tapoff.size());
-  up((void**)&W->d_taps, taps.data(), sizeof(double) * taps.size());
-  al((void**)&W->d_y, sizeof(double) * (size_t)W->tot_y);
-  al((void**)&W->d_mean_part, sizeof(double) * (size_t)n_utt * kHvMeanTiles);
-  if (m.r > 1) al((void**)&W->d_tmp, sizeof(double) * (size_t)W->tot_t);
-  // (W->d_events, the compacted lists, is gone: 0.58 GB at configs[2] that nobody reads any more)
-  al((void**)&W->d_evcnt, sizeof(int) * (size_t)n_utt * m.nch * 4);
-  {
-    int ymax = 1;
-    for (int u = 0; u < n_utt; ++u) ymax = imax(ymax, W->ylen[(size_t)u]);
-    W->tiles_max = hv_tiles(ymax, m.step);
-  }
-  al((void**)&W->d_tile_cnt, sizeof(int) * (size_t)n_utt * m.nch * 4 * ((size_t)W->tiles_max + 1));
-  {
-    std::vector<int64_t> soff((size_t)n_utt + 1, 0);
-    for (int u = 0; u < n_utt; ++u)
-      soff[(size_t)u + 1] = soff[(size_t)u] + (int64_t)m.nch * 4 * hv_tiles(W->ylen[(size_t)u], m.step) * kZcSlot;
-    up((void**)&W->d_slot_off, soff.data(), sizeof(int64_t) * soff.size());
-    al((void**)&W->d_slots, sizeof(double) * (size_t)soff[(size_t)n_utt]);
-  }
-  al((void**)&W->d_raw, sizeof(double) * (size_t)W->tot_b * m.nch);
-  al((void**)&W->d_offc, sizeof(double) * (size_t)W->tot_b * m.cpf);
-  al((void**)&W->d_cnt, sizeof(int) * (size_t)W->tot_b);
-  al((void**)&W->d_ncand1, sizeof(int) * (size_t)n_utt);
-  al((void**)&W->d_rc, sizeof(double) * (size_t)W->tot_b * m.maxc);
-  al((void**)&W->d_rs, sizeof(double) * (size_t)W->tot_b * m.maxc);
-  al((void**)&W->d_rc2, sizeof(double) * (size_t)W->tot_b * m.maxc);
-  al((void**)&W->d_rs2, sizeof(double) * (size_t)W->tot_b * m.maxc);
-  al((void**)&W->d_work, sizeof(double) * 4 * (size_t)W->tot_b);
-  al((void**)&W->d_bl, sizeof(int) * 2 * ((size_t)W->tot_b + 8 * (size_t)n_utt));
-  al((void**)&W->d_md, sizeof(double) * (size_t)W->tot_md);
-  al((void**)&W->d_mds, sizeof(double) * (size_t)W->tot_md);
-  al((void**)&W->d_sec, sizeof(int) * 3 * ((size_t)W->tot_b / 4 + 8 * (size_t)n_utt + 8));
-  al((void**)&W->d_sm, sizeof(double) * (size_t)W->tot_sm);
-  al((void**)&W->d_twid, sizeof(cpx) * (size_t)kHvTwid);
+  up(&W->d_ylen, kHbYlen, W->ylen);
+  up(&W->d_nb1, kHbNb1, W->nb1);
+  up(&W->d_yoff, kHbYoff, W->yoff);
+  up(&W->d_toff, kHbToff, W->toff);
+  up(&W->d_evoff, kHbEvoff, W->evoff);
+  up(&W->d_boff, kHbBoff, W->boff);
+  up(&W->d_mdoff, kHbMdoff, W->mdoff);
+  up(&W->d_smoff, kHbSmoff, W->smoff);
+  up(&W->d_bframe_utt, kHbFrameUtt, bfu);
+  up(&W->d_run_utt, kHbRunUtt, ru);
+  up(&W->d_run_first, kHbRunFirst, rf);
+  up(&W->d_bf, kHbBf, bf);
+  up(&W->d_half, kHbHalf, half);
+  up(&W->d_tapoff, kHbTapoff, tapoff);
+  up(&W->d_taps, kHbTaps, taps);
+  al(&W->d_y, kHbY);
+  al(&W->d_mean_part, kHbMeanPart);
+  if (m.r > 1) al(&W->d_tmp, kHbTmp);
+  al(&W->d_evcnt, kHbEvcnt);
+  al(&W->d_tile_cnt, kHbTileCnt);
+  up(&W->d_slot_off, kHbSlotOff, plan.soff);
+  al(&W->d_slots, kHbSlots);
+  al(&W->d_raw, kHbRaw);
+  al(&W->d_offc, kHbOffc);
+  al(&W->d_cnt, kHbCnt);
+  al(&W->d_ncand1, kHbNcand1);
+  al(&W->d_rc, kHbRc);
+  al(&W->d_rs, kHbRs);
+  al(&W->d_rc2, kHbRc2);
+  al(&W->d_rs2, kHbRs2);
+  al(&W->d_work, kHbWork);
+  al(&W->d_bl, kHbBl);
+  al(&W->d_md, kHbMd);
+  al(&W->d_mds, kHbMds);
+  al(&W->d_sec, kHbSec);
+  al(&W->d_sm, kHbSm);
+  al(&W->d_twid, kHbTwid);
   if (!rc) {
     hipLaunchKernelGGL(hv_twiddle_kernel, dim3(kHvTwid / 256), dim3(256), 0, st, W->d_twid);
     rc = wm_check(hipGetLastError());
@@ -1466,9 +1549,9 @@ static int hv_setup(Batch& b, hipStream_t st) {
       dl[(size_t)i] = m.half0 - half[(size_t)i];
     }
     int *d_nt = nullptr, *d_dl = nullptr;
-    up((void**)&d_nt, nt.data(), sizeof(int) * nt.size());
-    up((void**)&d_dl, dl.data(), sizeof(int) * dl.size());
-    al((void**)&W->d_H, sizeof(cpx) * (size_t)m.nch * ((size_t)m.conv / 2 + 1));
+    up(&d_nt, kHbNtaps, nt);
+    up(&d_dl, kHbDelay, dl);
+    al(&W->d_H, kHbSpectra);
     if (!rc) {
       hipLaunchKernelGGL(conv_spectrum_kernel<2048>, dim3(m.nch), dim3(64), 0, st, W->d_taps, W->d_tapoff,
                          d_nt, d_dl, (cpx*)W->d_H);

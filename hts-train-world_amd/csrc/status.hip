@@ -7,7 +7,8 @@
 // workgroup per utterance scans its input and outputs:
 //   WM_UTT_INPUT_NONFINITE   a NaN / Inf sample in x
 //   WM_UTT_TOO_SHORT         f0_length <= voice_range_minimum: Dio has no contour to fix (the reference returns
-//                            with f0 unwritten, dio.cpp:266; here f0 is all zero)
+//                            with f0 unwritten, dio.cpp:266; here f0 is all zero).  Dio's rule: not set for a batch
+//                            whose f0 estimator is Harvest, which has no such minimum
 //   WM_UTT_OUTPUT_NONFINITE  a NaN / Inf in the utterance's f0 / sp / ap rows (arrays given as NULL are skipped)
 //   WM_UTT_D4C_DEFAULT_ROWS  kept for ABI compatibility, never set since round 5 (it marked frames with f0 >= fs / 16 at
 //                            fs above 48.1 kHz, which kept D4C's default row until d4c_wide.hpp analysed them)
@@ -62,7 +63,8 @@ __global__ __launch_bounds__(256) void utterance_status_kernel(
 int launch_utterance_status(Batch& b, hipStream_t st, const double* d_x, const double* d_f0, const double* d_sp,
                             const double* d_ap, int* d_status) {
   if (!d_status) return WM_ERR_BAD_ARG;
-  const int vrm = (int)(0.5 + 1000.0 / b.p.frame_period / b.p.f0_floor) * 2 + 1;   // dio.cpp:263-264
+  // dio.cpp:263-264; no utterance has fewer than one frame, so -1 never flags (a batch whose estimator is Harvest)
+  const int vrm = b.f0_estimator == WM_F0_HARVEST ? -1 : (int)(0.5 + 1000.0 / b.p.frame_period / b.p.f0_floor) * 2 + 1;
   // fft_size_d4c (d4c.cpp:344-346); the rare-frame kernel exists up to 4096 points
   const int fd = (int)pow(2.0, 1.0 + (int)(log(4.0 * b.p.fs / 47.0 + 1) / log(2.0)));
   // (until round 5 frames with f0 >= fs / 16 kept D4C's default row where its transform has 8192 points, and were

@@ -39,10 +39,11 @@ class HostPipeline:
 
     SLOTS = 2
 
-    def __init__(self, ctx, params, x_lengths, synthesis=True, coded=None):
+    def __init__(self, ctx, params, x_lengths, synthesis=True, coded=None, f0_estimator="dio", refine=True):
+        """f0_estimator, refine: the f0 front end of every step's analysis (WorldBatch.set_f0_estimator)."""
         import torch
         self.torch = torch
-        self.batch = b = W.WorldBatch(ctx, params, x_lengths=x_lengths)
+        self.batch = b = W.WorldBatch(ctx, params, x_lengths=x_lengths, f0_estimator=f0_estimator, refine=refine)
         self.synthesis = synthesis
         self.coded = coded
         T, bins, n, ny = int(b.total_frames), b.bins, int(b.total_samples), int(b.total_out)

@@ -15,7 +15,8 @@ launches per batch, and written back in the CLIs' own file formats (SURVEY.md 8(
     wav out     16-bit mono PCM, s = clip(int(y * 32767))                 (test/audioio.cpp:160-167)
 
 Settings are the CLI's: Dio(71-800 Hz, speed 1, allowed_range 0.1) + StoneMask, CheapTrick(q1 -0.15),
-D4C(threshold 0) (analysis.cpp:93-203).  With several ranks (torch.distributed initialised, or WORLD_SIZE in
+D4C(threshold 0) (analysis.cpp:93-203).  `--f0 harvest` puts Harvest in Dio's place (`--no-refine`: without StoneMask
+behind it), `--f0-floor` / `--f0-ceil` set the estimator's search range; the files keep their layout.  With several ranks (torch.distributed initialised, or WORLD_SIZE in
 the environment) the list is sharded by frame count (sharding.lpt_shards; the counts come from the wav headers, a rank decodes only
 its own utterances) and every rank writes its own files, or -- `--gather`, BASELINE.json configs[3] -- the float32
 features travel to rank 0, which writes them all.
@@ -125,10 +126,11 @@ def _own_context():
     return W.Context()
 
 
-def _batches(order, frames, limit):
+def _batches(order, frames, limit, fits=None):
+    """Groups of `order` within `limit` frames and, where given, fits(group) (sweep.batches: the same rule)."""
     cur, tot = [], 0
     for i in order:
-        if cur and tot + frames[i] > limit:
+        if cur and (tot + frames[i] > limit or (fits is not None and not fits(cur + [i]))):
             yield cur
             cur, tot = [], 0
         cur.append(i)
@@ -264,10 +266,41 @@ def outputs_complete(job, n_frames, fs, spec_dim=0, ap_dim=24):
     return all(_size_is(p, w) for p, w in zip(job[1:4], want))
 
 
+def analysis_params(fs, frame_period, f0_floor=71.0, f0_ceil=800.0):
+    """The analysis parameters of the recipe: the CLI's, with the f0 estimator's search range.  CheapTrick keeps the
+    size the CLI gives it (GetFFTSizeForCheapTrick at its own 71 Hz, analysis.cpp:157-179): the files' row widths do not
+    move with the search range."""
+    if (float(f0_floor), float(f0_ceil)) == (71.0, 800.0):
+        return W.default_params(fs, frame_period)
+    if not 0.0 < f0_floor < f0_ceil:
+        raise ValueError("f0 range %g - %g Hz" % (f0_floor, f0_ceil))
+    return W.default_params(fs, frame_period, f0_floor=float(f0_floor), f0_ceil=float(f0_ceil),
+                            fft_size=capi.cheaptrick_fft_size(fs))
+
+
+def analysis_plan(order, frames, samples, max_batch_frames, params=None, f0_estimator="dio",
+                  harvest_batch_bytes=None):
+    """The batches of one sampling rate's utterances `order` (indices into frames and samples), in descending frame order
+    as every driver's plan (_Stage.groups): closed at max_batch_frames, and with Harvest also at harvest_batch_bytes (sweep.HARVEST_BATCH_BYTES) of its workspace,
+    whichever comes first; one utterance over a cap is a batch of its own.  Sample counts and parameters alone decide it."""
+    from . import sweep
+    W.f0_estimator_code(f0_estimator)
+    fits = None
+    if f0_estimator == "harvest":
+        fits = sweep.harvest_fits(params, samples, sweep.HARVEST_BATCH_BYTES if harvest_batch_bytes is None
+                                  else harvest_batch_bytes)
+    return list(_batches(sorted(order, key=lambda i: -frames[i]), frames, max_batch_frames, fits))
+
+
 def analysis_files(jobs, frame_period=5.0, fft_size=0, spec_dim=0, ap_dim=24, ctx=None,
-                   max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, gather=False, resume=False):
+                   max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, gather=False, resume=False,
+                   f0_estimator="dio", refine=True, f0_floor=71.0, f0_ceil=800.0, harvest_batch_bytes=None):
     """jobs: [(wav, f0_out, sp_out, ap_out)].  Writes what `analysis wav f0 sp ap frame_period fft_size
     [spec_dim [ap_dim]]` writes for every job; returns the number of frames analysed by this rank.
+
+    f0_estimator "harvest": Harvest -> [StoneMask, with refine ->] CheapTrick -> D4C, the composition of the reference's
+    functions that its CLI never made, in the same files; f0_floor / f0_ceil: the estimator's search range (analysis_params).
+    With Harvest a batch also closes at harvest_batch_bytes of its workspace (None: sweep.HARVEST_BATCH_BYTES; analysis_plan).
 
     Every rank reads the wav HEADERS of the whole list (the partition needs the frame counts), but decodes only the
     utterances of its own shard, one batch at a time.  gather=False: every rank writes the files of its shard.
@@ -280,6 +313,7 @@ def analysis_files(jobs, frame_period=5.0, fft_size=0, spec_dim=0, ap_dim=24, ct
     jobs = list(jobs)
     if gather and resume:
         raise ValueError("resume goes with every rank writing its own shard (gather=False)")
+    W.f0_estimator_code(f0_estimator)
     with ThreadPoolExecutor(io_threads) as pool:
         heads = list(pool.map(lambda j: wav_header(j[0]), jobs))
     frames = [sharding.frame_count(n, fs, frame_period) for n, fs in heads]
@@ -291,15 +325,17 @@ def analysis_files(jobs, frame_period=5.0, fft_size=0, spec_dim=0, ap_dim=24, ct
             raise ValueError("fft_size %d is not CheapTrick's size for %d Hz (%d)" % (fft_size, fs, own_size))
     with _Stage(ctx, io_threads) as stage:
         if gather:
-            return _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, stage.ctx, max_batch_frames, io_threads)
+            return _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, stage.ctx, max_batch_frames, io_threads,
+                                      f0_estimator, refine, f0_floor, f0_ceil, harvest_batch_bytes)
         mine = _my_share(frames)
         if resume:
             mine = [i for i in mine if not outputs_complete(jobs[i], frames[i], heads[i][1], spec_dim, ap_dim)]
         for fs in sorted({heads[i][1] for i in mine}):
-            params = W.default_params(fs, frame_period)
-            for group in stage.groups([i for i in mine if heads[i][1] == fs], frames, max_batch_frames):
+            params = analysis_params(fs, frame_period, f0_floor, f0_ceil)
+            for group in analysis_plan([i for i in mine if heads[i][1] == fs], frames, [h[0] for h in heads],
+                                       max_batch_frames, params, f0_estimator, harvest_batch_bytes):
                 xs = [x for x, _ in stage.pool.map(lambda i: read_wav(jobs[i][0]), group)]   # this batch only, dropped after it
-                with stage.batch(params, x_lengths=[len(x) for x in xs]) as b:
+                with stage.batch(params, x_lengths=[len(x) for x in xs], f0_estimator=f0_estimator, refine=refine) as b:
                     x = _upload(np.concatenate(xs), pinned=True)
                     del xs
                     t, f0, sp, ap = b.analyze(x)
@@ -325,7 +361,8 @@ def _rank_world():
     return rank, world
 
 
-def _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, ctx, max_batch_frames, io_threads):
+def _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, ctx, max_batch_frames, io_threads,
+                       f0_estimator="dio", refine=True, f0_floor=71.0, f0_ceil=800.0, harvest_batch_bytes=None):
     """configs[3]'s flow for a file list: shard, analyse, gather-v to rank 0, rank 0 writes (needs an initialised
     process group when there is more than one rank)."""
     import torch.distributed as dist
@@ -338,7 +375,9 @@ def _analysis_gathered(jobs, heads, frame_period, spec_dim, ap_dim, ctx, max_bat
     for fs in sorted({h[1] for h in heads}):
         sel = [i for i, h in enumerate(heads) if h[1] == fs]
         sw = sweep.ShardedSweep(ctx, fs, frame_period, [heads[i][0] for i in sel], rank, world, spec_dim, ap_dim,
-                                max_batch_frames, backend)
+                                max_batch_frames, backend, f0_estimator=f0_estimator, refine=refine, f0_floor=f0_floor,
+                                f0_ceil=f0_ceil, harvest_batch_bytes=sweep.HARVEST_BATCH_BYTES if harvest_batch_bytes is None
+                                else harvest_batch_bytes)
         sw.load(lambda k: read_wav(jobs[sel[k]][0])[0], io_threads)
         sw.run(sweep.file_sink([jobs[i][1:4] for i in sel]) if rank == 0 else None, io_threads)
         done += sw.my_frames
@@ -1606,6 +1645,10 @@ def main(argv=None):
                            help="several ranks (torchrun): gather the features to rank 0, which writes every file")
             p.add_argument("--resume", action="store_true",
                            help="skip utterances whose three output files are already complete (a run that was cut short)")
+            p.add_argument("--f0", choices=W.F0_ESTIMATORS, default="dio", help="the f0 estimator in front of the chain")
+            p.add_argument("--no-refine", action="store_true", help="the estimator's contour as it is: no StoneMask behind it")
+            p.add_argument("--f0-floor", type=float, default=71.0, help="lower end of the estimator's search range in Hz")
+            p.add_argument("--f0-ceil", type=float, default=800.0, help="upper end of the estimator's search range in Hz")
         if name == "synth":
             p.add_argument("--fs", type=int, required=True)
     p = sub.add_parser("gen-param", help="gen_param: mlpg on every stream of a list of ffo files")
@@ -1832,7 +1875,8 @@ def main(argv=None):
             import torch.distributed as dist
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
             dist.init_process_group(os.environ.get("WM_BACKEND", "nccl"))
-        n = analysis_files(jobs, a.frame_period, a.fft_size, a.spec_dim, a.ap_dim, gather=a.gather, resume=a.resume)
+        n = analysis_files(jobs, a.frame_period, a.fft_size, a.spec_dim, a.ap_dim, gather=a.gather, resume=a.resume,
+                           f0_estimator=a.f0, refine=not a.no_refine, f0_floor=a.f0_floor, f0_ceil=a.f0_ceil)
     else:
         n = synth_files(jobs, a.frame_period, a.fft_size, a.fs, a.spec_dim, a.ap_dim)
     print("complete. %d frames" % n)

@@ -5,7 +5,8 @@ call site :214).  Utterances are independent, so here
 
   1. every rank derives the same longest-processing-time partition of the utterance list from the frame counts
      alone (sharding.lpt_shards; a frame count needs the sample count only -- the wav header, not the samples);
-  2. a rank loads and analyses ITS utterances only, in HBM-resident batches (Dio -> StoneMask -> CheapTrick -> D4C),
+  2. a rank loads and analyses ITS utterances only, in HBM-resident batches (Dio -> StoneMask -> CheapTrick -> D4C, or
+     with f0_estimator="harvest" Harvest in Dio's place: then a batch is also closed by the bytes of Harvest's workspace),
      and turns the features into the on-disk float32 form of the CLI (test/analysis.cpp:360-390 raw f0 / sp / ap,
      or :292-366 coded lf0 / mgc / bap when spec_dim is given);
   3. the only exchange: a gather-v of those float32 slabs to rank 0 (grouped send/recv: RCCL over xGMI with the
@@ -30,11 +31,23 @@ from . import capi, sharding, world as W
 MAX_BATCH_FRAMES = 1_500_000          # about 12.3 GB of fp64 sp + ap at F = 1024; far inside 288 GB
 
 
-def batches(order, frames, limit):
-    """Consecutive groups of `order` whose frame counts stay within `limit` (a single larger utterance is its own group)."""
+HARVEST_BATCH_BYTES = 32 << 30        # of Harvest's workspace per batch (about 1 M frames of 1 ms: 33 KB each); a setting
+
+
+def harvest_fits(params, samples, byte_cap=HARVEST_BATCH_BYTES):
+    """The second cap of a plan whose estimator is Harvest, as batches() takes it: fits(group) is true while Harvest's
+    workspace for the utterances `group` (indices into the sample counts `samples`) stays within byte_cap.  It reads
+    sample counts and parameters alone (W.harvest_workspace_bytes, host only): every rank derives the same plan."""
+    return lambda group: W.harvest_workspace_bytes(params, [samples[i] for i in group]) <= byte_cap
+
+
+def batches(order, frames, limit, fits=None):
+    """Consecutive groups of `order` whose frame counts stay within `limit` (a single larger utterance is its own group);
+    with fits(group) -> bool a group is also closed ahead of the utterance with which it would no longer fit (again a
+    single utterance that does not fit is its own group)."""
     cur, tot = [], 0
     for i in order:
-        if cur and tot + frames[i] > limit:
+        if cur and (tot + frames[i] > limit or (fits is not None and not fits(cur + [i]))):
             yield cur
             cur, tot = [], 0
         cur.append(i)
@@ -43,9 +56,9 @@ def batches(order, frames, limit):
         yield cur
 
 
-def tapered_batches(order, frames, rounds, limit, ratio=0.65):
+def tapered_batches(order, frames, rounds, limit, ratio=0.65, fits=None):
     """`order` cut into `rounds` consecutive groups whose frame counts fall off geometrically (ratio per round), each
-    within `limit`.  A pass is a pipeline -- round k + 1 is analysed while round k travels to the host and round k - 1
+    within `limit` (and fits(group), as in batches()).  A pass is a pipeline -- round k + 1 is analysed while round k travels to the host and round k - 1
     is written -- so what no compute hides is the LAST round's transfer and file writes: the smaller that round, the
     shorter the tail (equal rounds: a quarter of the pass's copy + write time exposed at four rounds; tapered: a
     tenth).  Too small a round does not fill the GPU, hence the gentle ratio (profiles/r04_sweep_taper.txt)."""
@@ -57,7 +70,8 @@ def tapered_batches(order, frames, rounds, limit, ratio=0.65):
         cum.append(total * acc / sum(w))
     groups, cur, tot, done, k = [], [], 0, 0, 0
     for i in order:
-        if cur and (tot + frames[i] > limit or (k < rounds - 1 and done + tot >= cum[k])):
+        if cur and (tot + frames[i] > limit or (k < rounds - 1 and done + tot >= cum[k])
+                    or (fits is not None and not fits(cur + [i]))):
             groups.append(cur)
             done += tot
             cur, tot = [], 0
@@ -75,12 +89,18 @@ class ShardedSweep:
     waveforms into HBM; `run()` is one pass: analyse, gather to rank 0, write."""
 
     def __init__(self, ctx, fs, frame_period, sample_counts, rank=0, world=1, spec_dim=0, ap_dim=24,
-                 max_batch_frames=MAX_BATCH_FRAMES, backend="nccl", rounds=1, writers="rank0"):
+                 max_batch_frames=MAX_BATCH_FRAMES, backend="nccl", rounds=1, writers="rank0",
+                 f0_estimator="dio", refine=True, f0_floor=71.0, f0_ceil=800.0, harvest_batch_bytes=HARVEST_BATCH_BYTES):
         """rounds > 1 splits every shard into about that many batches, so that rank 0 copies and writes the
         features of one round while the next is being analysed.  writers="all": no gather -- every rank copies its
         own features to the host and writes its own files (what the rank-0 funnel of configs[3] costs is the
-        difference between the two)."""
+        difference between the two).  f0_estimator, refine: the f0 front end of every batch (WorldBatch.set_f0_estimator);
+        f0_floor, f0_ceil: its search range (CheapTrick keeps the size the CLI gives it, the file widths do not change).
+        With Harvest a batch also closes at harvest_batch_bytes of Harvest's workspace, and load() refuses a rank whose
+        batches, all resident at once, would take more than half of the device's memory (check_resident)."""
         self.ctx, self.fs, self.fp = ctx, int(fs), float(frame_period)
+        self.f0_estimator, self.refine = f0_estimator, bool(refine)
+        W.f0_estimator_code(f0_estimator)                # a bad name: ValueError, ahead of everything else
         self.rank, self.world, self.backend = rank, world, backend
         self.spec_dim, self.ap_dim = int(spec_dim), int(ap_dim)
         self.samples = [int(n) for n in sample_counts]
@@ -92,13 +112,17 @@ class ShardedSweep:
         self.writers = writers
         # batch plan of EVERY rank (rank 0 needs the layout of what it receives): longest first inside a shard; with
         # several rounds the rounds taper off (tapered_batches)
+        over = {}
+        if (float(f0_floor), float(f0_ceil)) != (71.0, 800.0):
+            over = dict(f0_floor=float(f0_floor), f0_ceil=float(f0_ceil), fft_size=capi.cheaptrick_fft_size(self.fs))
+        self.params = W.default_params(self.fs, self.fp, **over)
+        fits = harvest_fits(self.params, self.samples, harvest_batch_bytes) if f0_estimator == "harvest" else None
         by_len = lambda s: sorted(s, key=lambda i: (-self.frames[i], i))
         if rounds > 1:
-            self.plan = [tapered_batches(by_len(s), self.frames, rounds, max_batch_frames) for s in self.shards]
+            self.plan = [tapered_batches(by_len(s), self.frames, rounds, max_batch_frames, fits=fits) for s in self.shards]
         else:
-            self.plan = [list(batches(by_len(s), self.frames, max_batch_frames)) for s in self.shards]
+            self.plan = [list(batches(by_len(s), self.frames, max_batch_frames, fits)) for s in self.shards]
         self.rounds = max((len(p) for p in self.plan), default=0)
-        self.params = W.default_params(self.fs, self.fp)
         self.loaded = []                 # [(WorldBatch, x on device)] for this rank's batches
         self._pinned = {}                # rank 0's host staging of the gathered slabs
         self._items = {}                 # round -> (sink, pinned pointers, the native writer's list for that round)
@@ -107,17 +131,35 @@ class ShardedSweep:
         self.my_frames = sum(self.frames[i] for i in self.shards[rank])
 
     # ---- input ------------------------------------------------------------------------------------------------
+    def harvest_resident_bytes(self, rank=None):
+        """Harvest's workspaces of all batches of `rank` (this rank's), which load() keeps resident together; 0 under Dio."""
+        if self.f0_estimator != "harvest":
+            return 0
+        return sum(W.harvest_workspace_bytes(self.params, [self.samples[i] for i in g])
+                   for g in self.plan[self.rank if rank is None else rank])
+
+    def check_resident(self, device_bytes):
+        """ValueError when Harvest's workspaces of this rank's batches add up to more than half of device_bytes."""
+        need = self.harvest_resident_bytes()
+        if 2 * need > device_bytes:
+            raise ValueError("Harvest's workspaces of rank %d's %d batches take %d bytes together, more than half of the "
+                             "device's %d bytes: use more ranks or fewer utterances per sweep"
+                             % (self.rank, len(self.plan[self.rank]), need, device_bytes))
+
     def load(self, waveform_of, io_threads=8):
         """waveform_of(i) -> float64 samples of utterance i.  Called for this rank's utterances only."""
         import torch
         self.close()
+        if self.f0_estimator == "harvest":
+            self.check_resident(torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory)
         with ThreadPoolExecutor(io_threads) as pool:
             for group in self.plan[self.rank]:
                 xs = list(pool.map(waveform_of, group))
                 for i, x in zip(group, xs):
                     if len(x) != self.samples[i]:
                         raise ValueError("utterance %d has %d samples, the plan says %d" % (i, len(x), self.samples[i]))
-                b = W.WorldBatch(self.ctx, self.params, x_lengths=[len(x) for x in xs])
+                b = W.WorldBatch(self.ctx, self.params, x_lengths=[len(x) for x in xs], f0_estimator=self.f0_estimator,
+                                 refine=self.refine)
                 x = torch.from_numpy(np.concatenate(xs)).pin_memory().cuda(non_blocking=True)
                 self.loaded.append((b, x))
         torch.cuda.synchronize()

@@ -192,6 +192,9 @@ def load_library():
     L.WorldMi355Analyze.argtypes = [vp, vp, vp, vp, vp, vp]
     L.WorldMi355AnalyzeSynthesize.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.WorldMi355UtteranceStatus.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.WorldMi355BatchSetF0Estimator.argtypes = [vp, C.c_int, C.c_int]
+    L.WorldMi355BatchGetF0Estimator.argtypes = [vp, _ip, _ip]
+    L.WorldMi355HarvestWorkspaceBytes.argtypes = [C.POINTER(WorldParams), C.c_int, _ip, C.POINTER(C.c_int64)]
     L.WorldMi355Vibrato.argtypes = [vp, vp, _ip, _ip, _ip, _dp, vp, vp, _ip]
     L.WorldMi355GetNumberOfAperiodicities.argtypes = [C.c_int]
     L.WorldMi355CodeSpectralEnvelope.argtypes = [vp, vp, C.c_int, vp]
@@ -264,6 +267,27 @@ def default_params(fs: int, frame_period: float = 5.0, **over) -> WorldParams:
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+F0_ESTIMATORS = ("dio", "harvest")                       # include/world_mi355.h: WM_F0_DIO, WM_F0_HARVEST
+
+
+def f0_estimator_code(name) -> int:
+    """WM_F0_* of an estimator's name; ValueError for any other."""
+    if name not in F0_ESTIMATORS:
+        raise ValueError("f0_estimator %r: one of %s" % (name, ", ".join(F0_ESTIMATORS)))
+    return F0_ESTIMATORS.index(name)
+
+
+def harvest_workspace_bytes(params: WorldParams, x_lengths) -> int:
+    """Bytes of device memory Harvest's workspace takes for a batch of these sample counts
+    (WorldMi355HarvestWorkspaceBytes: the sizes its set-up allocates; about 33 KB per 1 ms frame at the default range,
+    whatever the frame period).  Host only: needs no device."""
+    arr, ptr = _ints(x_lengths)
+    out = C.c_int64(0)
+    _check(load_library().WorldMi355HarvestWorkspaceBytes(C.byref(params), len(arr), ptr, C.byref(out)),
+           "HarvestWorkspaceBytes")
+    return int(out.value)
 
 
 class Context:
@@ -384,8 +408,11 @@ class WorldBatch:
     ``total_frames`` entries, sp/ap ``total_frames x (fft_size/2+1)``.
     """
 
-    def __init__(self, ctx: Context, params: WorldParams, x_lengths=None, f0_lengths=None, y_lengths=None):
+    def __init__(self, ctx: Context, params: WorldParams, x_lengths=None, f0_lengths=None, y_lengths=None,
+                 f0_estimator="dio", refine=True):
+        """f0_estimator, refine: the f0 front end of analyze() and analyze_synthesize() (set_f0_estimator)."""
         L = load_library()
+        code = f0_estimator_code(f0_estimator)
         self.ctx = ctx
         self.params = params
         n = len(x_lengths) if x_lengths is not None else len(f0_lengths)
@@ -404,6 +431,21 @@ class WorldBatch:
         self.sample_offsets = np.ctypeslib.as_array(L.WorldMi355BatchSampleOffsets(h), (n + 1,)).copy()
         self.frame_offsets = np.ctypeslib.as_array(L.WorldMi355BatchFrameOffsets(h), (n + 1,)).copy()
         self.out_offsets = np.ctypeslib.as_array(L.WorldMi355BatchOutputOffsets(h), (n + 1,)).copy()
+        self.f0_estimator, self.refine = "dio", True
+        if (code, bool(refine)) != (0, True):
+            try:
+                self.set_f0_estimator(f0_estimator, refine)
+            except Exception:
+                self.close()
+                raise
+
+    def set_f0_estimator(self, f0_estimator="dio", refine=True):
+        """The f0 front end of analyze() and analyze_synthesize() from the next call on: "dio" (a new batch's) or "harvest",
+        with StoneMask behind it (refine) or its contour as it is.  The chain gives the bits of the stages called one by
+        one.  A name other than the two raises ValueError; a batch without x_lengths is refused."""
+        code = f0_estimator_code(f0_estimator)
+        _check(load_library().WorldMi355BatchSetF0Estimator(self.handle, code, 1 if refine else 0), "BatchSetF0Estimator")
+        self.f0_estimator, self.refine = f0_estimator, bool(refine)
 
     @staticmethod
     def _p(t):
@@ -459,7 +501,8 @@ class WorldBatch:
         return pcm
 
     def analyze(self, x, out=None):
-        """Dio -> StoneMask -> CheapTrick -> D4C (test/analysis.cpp:243-390)."""
+        """Dio -> StoneMask -> CheapTrick -> D4C (test/analysis.cpp:243-390); with set_f0_estimator, Harvest in Dio's place
+        and StoneMask or not."""
         if out is None:
             out = (self._new(self.total_frames), self._new(self.total_frames),
                    self._new(self.total_frames, self.bins), self._new(self.total_frames, self.bins))
@@ -508,7 +551,8 @@ class WorldBatch:
         return vib, out, n.value
 
     def utterance_status(self, x=None, f0=None, sp=None, ap=None):
-        """int32 cuda tensor [n_utt] of WM_UTT_* flags (1 non-finite input, 2 too short for Dio, 4 non-finite output)."""
+        """int32 cuda tensor [n_utt] of WM_UTT_* flags (1 non-finite input, 2 too short for Dio -- not set when the batch's
+        estimator is Harvest --, 4 non-finite output)."""
         import torch
         st = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
         ptr = lambda t: None if t is None else self._p(t)

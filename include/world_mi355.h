@@ -132,12 +132,39 @@ int WorldMi355Analyze(WorldMi355Batch* b, const double* x, double* t, double* f0
 int WorldMi355AnalyzeSynthesize(WorldMi355Batch* b, const double* x, double* t, double* f0, double* sp,
                                 double* ap, double* y);
 
+/* The f0 front end of the two one-call forms above: a property of the batch.  A new batch has (WM_F0_DIO, 1), the chain
+ * of test/analysis.cpp.  With WM_F0_HARVEST the chain is Harvest -> [StoneMask ->] CheapTrick -> D4C (-> Synthesis): the
+ * composition of the reference's own functions (the reference ships no caller of Harvest), with the same launches and
+ * the same bits as the stage entry points called one by one.  refine 1: StoneMask behind the estimator; 0: the
+ * estimator's contour is the f0 of the chain.  The stage entry points are not affected.  May be called between any two
+ * calls on the batch; Harvest's workspace is made by the first call that needs it (see WorldMi355HarvestWorkspaceBytes).
+ * A NULL batch, an estimator other than the two, refine outside {0, 1}, a batch made without x_lengths (the setter):
+ * WM_ERR_BAD_ARG before any device call. */
+#define WM_F0_DIO 0
+#define WM_F0_HARVEST 1
+int WorldMi355BatchSetF0Estimator(WorldMi355Batch* b, int estimator, int refine);
+int WorldMi355BatchGetF0Estimator(const WorldMi355Batch* b, int* estimator, int* refine);
+
+/* What Harvest's workspace takes from the device for a batch of n_utt utterances of x_lengths samples, in bytes: the sum of
+ * the very sizes its set-up allocates, each as the library's allocator rounds it.  Host only: no context, no HIP call.
+ * It grows with the batch's 1 ms frames (Harvest analyses at 1 ms whatever p->frame_period says), not with its frames
+ * at the caller's hop.  At the default range (71 - 800 Hz: 152 channels, 105 candidates a frame) it is 33 KB per 1 ms
+ * frame at 16 kHz and at 48 kHz alike (32 912 and 33 197 bytes, utterances of 10 s and more; 35 KB at 3 s): 25.6 KB of
+ * that are the staging slots of the zero-crossing events (152 channels x 4 kinds x 1024 doubles per tile of 1554
+ * decimated samples, whole tiles per utterance), 3.4 KB the four candidate arrays, 1.2 KB the raw candidates; about
+ * 4.7 MB per batch do not depend on its length.  So a frame at a 5 ms hop costs 165 KB here, against the 16 KB of its
+ * fp64 sp + ap rows at fft_size 1024: a batch sized for those (1.5 M frames) would ask for 233 GiB.  Only fs, f0_floor
+ * and f0_ceil of p are read.  A NULL argument, n_utt < 1, a length < 1, a range that is none: WM_ERR_BAD_ARG; an f0
+ * range Harvest's kernels do not cover (more than 192 candidates a frame): WM_ERR_UNSUPPORTED. */
+int WorldMi355HarvestWorkspaceBytes(const WorldMi355Params* p, int n_utt, const int* x_lengths, int64_t* bytes);
+
 /* Per-utterance status of a batch: status[u] (DEVICE pointer, n_utt ints) receives a bit mask.  Utterances of a
  * batch never exchange data, so one with a flag set does not affect the results of the others (SURVEY.md section 5;
  * the reference has no error reporting: every entry point returns void).  x, f0, sp, ap are the arrays of the
  * analysis calls; any of them may be NULL and is then not scanned.  Asynchronous on the context's stream. */
 #define WM_UTT_INPUT_NONFINITE 1   /* NaN / Inf among the samples of x */
-#define WM_UTT_TOO_SHORT 2         /* f0_length <= Dio's voice_range_minimum: f0 is all zero (dio.cpp:263-266) */
+#define WM_UTT_TOO_SHORT 2         /* f0_length <= Dio's voice_range_minimum: f0 is all zero (dio.cpp:263-266).  Dio's rule:
+                                    * never set for a batch whose estimator is WM_F0_HARVEST, which has no such minimum */
 #define WM_UTT_OUTPUT_NONFINITE 4  /* NaN / Inf among the utterance's f0 / sp / ap */
 #define WM_UTT_D4C_DEFAULT_ROWS 8  /* never set since round 5 (kept for ABI compatibility): it marked frames with f0 >= fs / 16
                                     * at fs above 48.1 kHz, which kept D4C's default row; they are analysed now */
