@@ -282,7 +282,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn, ffi;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn, ffi, mgcep;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -344,6 +344,16 @@ int launch_recipe_decode(Batch& b, hipStream_t st, const float* d_lf0, const flo
 int check_mel_cepstrum(const Batch& b, const double* d_spec, const WorldMi355McepOption& opt, const double* d_mc);
 int launch_mel_cepstrum(Batch& b, hipStream_t st, const double* d_spec, const WorldMi355McepOption& opt, double* d_mc,
                         int* d_status);
+// mgcep.hip: mcep's itype 0 on rows of windowed frames, and on waveforms framed and windowed on the way in
+int sptk_frames(int64_t n_samples, int frame_length, int frame_shift, int64_t* n_frames);
+int sptk_window(int type, int normalize, int length, double* w);
+int check_mgcep(const Batch& b, const double* d_in, bool waveform, const double* window, int frame_length,
+                int frame_shift, const WorldMi355McepOption& opt, const double* d_mc);
+int launch_mel_cepstrum_of_frames(Batch& b, hipStream_t st, const double* d_frames, const WorldMi355McepOption& opt,
+                                  double* d_mc, int* d_status);
+int launch_mel_cepstrum_of_waveform(Batch& b, hipStream_t st, const double* d_x, const double* window, int frame_length,
+                                    int frame_shift, int pipe_float32, const WorldMi355McepOption& opt, double* d_mc,
+                                    int* d_status);
 int check_mgc2sp(const Batch& b, const double* d_mc, const WorldMi355Mgc2spOption& opt, const double* d_sp);
 int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355Mgc2spOption& opt, double* d_sp,
                   double* d_phase, int* d_status);

@@ -309,6 +309,26 @@ int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const Worl
   if (const int rc = check_mel_cepstrum(b->b, spectrum, *opt, mc)) return rc;   // refused before any device call
   return on_batch(b, launch_mel_cepstrum, spectrum, *opt, mc, status);
 }
+int WorldMi355SptkFrames(int64_t n_samples, int frame_length, int frame_shift, int64_t* n_frames) {
+  return sptk_frames(n_samples, frame_length, frame_shift, n_frames);
+}
+int WorldMi355SptkWindow(int type, int normalize, int length, double* w) {
+  return sptk_window(type, normalize, length, w);
+}
+int WorldMi355MelCepstrumOfFrames(WorldMi355Batch* b, const double* frames, const WorldMi355McepOption* opt, double* mc,
+                                  int* status) {
+  if (!b || !opt) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mgcep(b->b, frames, false, nullptr, 0, 0, *opt, mc)) return rc;   // before any device call
+  return on_batch(b, launch_mel_cepstrum_of_frames, frames, *opt, mc, status);
+}
+int WorldMi355MelCepstrumOfWaveform(WorldMi355Batch* b, const double* x, const double* window, int frame_length,
+                                    int frame_shift, int pipe_float32, const WorldMi355McepOption* opt, double* mc,
+                                    int* status) {
+  if (!b || !opt) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mgcep(b->b, x, true, window, frame_length, frame_shift, *opt, mc)) return rc;
+  return on_batch(b, launch_mel_cepstrum_of_waveform, x, window, frame_length, frame_shift, pipe_float32, *opt, mc,
+                  status);
+}
 void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* o) {                 // SPTK's mgc2sp defaults, ln |H| out
   if (!o) return;
   o->alpha = 0.35;

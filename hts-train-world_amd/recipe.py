@@ -32,6 +32,8 @@ model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is th
 (scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With USEMSPF gen_wave takes
 postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
 `mspf-stats` write (make_mspf, :3133-3221).
+mgcep_files() / `mgcep` is the recipe's spectral analysis without WORLD (data/Makefile.in:134-137, the default
+USEWORLD=0, GAMMA=0): `x2x +sf | frame | window | mgcep` from raw or wav files to float32 mgc, one kernel per batch.
 
 trajectory_files() / `trj-eval` stands where gen_param_files() stands when the model was trained by trajectory training
 ($TRJGV, scripts/Training.pl:930-940): the outputs and the cost of DNNDefine.trajectory_cost; the loss itself, for a
@@ -1395,6 +1397,103 @@ def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_ba
     return stage.frames
 
 
+# ---- mel-cepstra from waveforms (data/Makefile.in:134-137: x2x +sf | frame | window | mgcep at gamma 0) ---------------
+def read_samples(path):
+    """The int16 values of a headerless little-endian `.raw` file (what `x2x +sf` reads) or of a 16-bit wav, as float64
+    and as they are: SPTK's pipe carries them undivided."""
+    if str(path).lower().endswith(".raw"):
+        return np.fromfile(str(path), dtype="<i2").astype(np.float64)
+    x, _ = read_wav(path)
+    return x * 32768.0                                      # read_wav divided the 16-bit values by 2^15: exact both ways
+
+
+def _sample_count(path):
+    if str(path).lower().endswith(".raw"):
+        size = os.path.getsize(str(path))
+        if size % 2:
+            raise ValueError("%s: %d bytes are no int16 samples" % (path, size))
+        return size // 2
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError("%s: mgcep takes 16-bit samples, the file has %d-bit ones" % (path, 8 * w.getsampwidth()))
+        return w.getnframes()
+
+
+def mgcep_check(frame_length, frame_shift, fft_length, window, normalize, alpha, order, eps, max_batch_frames=1):
+    """What mgcep_files refuses, as a ValueError, before anything is opened."""
+    if fft_length not in (512, 1024, 2048, 4096):
+        raise ValueError("fft_length %r: 512, 1024, 2048 or 4096" % (fft_length,))
+    if not 2 <= frame_length <= fft_length:
+        raise ValueError("frame_length %r: from 2 to fft_length = %d" % (frame_length, fft_length))
+    if not 1 <= frame_shift <= frame_length:
+        raise ValueError("frame_shift %r: from 1 to frame_length = %d" % (frame_shift, frame_length))
+    if window not in (0, 1, 2, 5):
+        raise ValueError("window %r: 0 Blackman, 1 Hamming, 2 Hanning or 5 rectangular" % (window,))
+    if normalize not in (0, 1, 2):
+        raise ValueError("normalize %r: 0 none, 1 power or 2 magnitude" % (normalize,))
+    if not 1 <= order <= 63:
+        raise ValueError("order %r: from 1 to 63" % (order,))
+    if not abs(alpha) < 1.0:
+        raise ValueError("alpha %r: |alpha| < 1" % (alpha,))
+    if not eps >= 0.0:
+        raise ValueError("eps %r: a value >= 0 added to the periodogram" % (eps,))
+    if max_batch_frames < 1:
+        raise ValueError("max_batch_frames %r: at least 1" % (max_batch_frames,))
+
+
+def mgcep_files(jobs, frame_length=1200, frame_shift=240, fft_length=2048, window=1, normalize=1, alpha=0.55, order=49,
+                eps=1.0e-8, itr1=2, itr2=30, dd=1.0e-3, pipe_float32=True, ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
+                io_threads=8, resume=False):
+    """The recipe's spectral analysis without WORLD (data/Makefile.in:134-137, the default USEWORLD=0, GAMMA=0) for a file
+    list: `x2x +sf raw | frame -l frame_length -p frame_shift | window -l frame_length -L fft_length -w window -n
+    normalize | mgcep -a alpha -m order -l fft_length -e eps > mgc`, in one kernel per batch (mel_cepstrum_of_waveform).
+
+    jobs:  [(raw_or_wav, mgc_out)] -- `.raw`: headerless little-endian int16; anything else: a 16-bit wav.  The samples
+           are the int16 values as they are.  Out: float32 [J][order+1], J = sptk_frames(samples).
+    pipe_float32: the windowed samples are rounded to float32 once, as the pipe between `window` and `mgcep` does.
+    An utterance with a frame of status 1 or 2 (theq's singular pivot, a periodogram value that is not positive and
+    finite) is reported on stderr and its file is not written -- the recipe's $(NAN) check (:152-155); status -1 is mcep's
+    ordinary return.  Rank-sharded by frame count; batches close at max_batch_frames; with resume, utterances whose
+    output has the complete size are skipped.  Returns (frames analysed by this rank, the flagged inputs)."""
+    mgcep_check(frame_length, frame_shift, fft_length, window, normalize, alpha, order, eps, max_batch_frames)
+    import torch  # noqa: F401 -- ahead of the first call into the library (analysis_files says why)
+    jobs = list(jobs)
+    width = int(order) + 1
+    with ThreadPoolExecutor(io_threads) as pool:
+        samples = list(pool.map(lambda j: _sample_count(j[0]), jobs))
+    empty = [jobs[i][0] for i, n in enumerate(samples) if n == 0]
+    if empty:
+        raise ValueError("%s holds no samples" % empty[0])
+    frames = [W.sptk_frames(n, frame_length, frame_shift) for n in samples]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 4 * width * frames[i])))
+    flagged = []
+    if not mine:
+        return 0, flagged
+    table = W.sptk_window(window, normalize, frame_length)
+    params = W.default_params(48000, 5.0, fft_size=fft_length)     # of the batch only fft_size is read
+    with _Stage(ctx, io_threads) as stage:
+        for group in stage.groups(mine, frames, max_batch_frames):
+            xs = list(stage.pool.map(lambda i: read_samples(jobs[i][0]), group))
+            with stage.batch(params, x_lengths=[len(x) for x in xs], f0_lengths=[frames[i] for i in group]) as b:
+                x = _upload(np.concatenate(xs), pinned=True)
+                del xs
+                mc, status = b.mel_cepstrum_of_waveform(x, table, frame_length, frame_shift, order, alpha, pipe_float32,
+                                                        etype=1, e=eps, itr1=itr1, itr2=itr2, dd=dd)
+                host = mc.float().cpu().numpy()
+                st = status.cpu().numpy()
+                fo = b.frame_offsets
+                paths = []
+                for k, i in enumerate(group):
+                    bad = np.nonzero(st[fo[k]:fo[k + 1]] > 0)[0]
+                    if len(bad):
+                        print("warning: %s: %d frames flagged (first: frame %d, status %d), not written" % (
+                            jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
+                        flagged.append(jobs[i][0])
+                    paths.append(None if len(bad) else jobs[i][1])
+                stage.put(b, host, paths)
+    return stage.frames, flagged
+
+
 # ---- modulation-spectrum postfilter (scripts/Training.pl:2950-3038 postfiltering_mspf, :3133-3221 make_mspf) ----------
 def mspf_label_rows(lines, frame_shift_s, n_rows, silences=()):
     """Rows that make_mspf's silence removal keeps: label lines "start end name" in 100 ns units; a segment's frames are
@@ -1715,6 +1814,20 @@ def main(argv=None):
     p.add_argument("--beta", type=float, default=1.4, help="the postfiltering coefficient (pf_mcp)")
     p.add_argument("--length", type=int, default=4096, help="bins of the energy sums (IMPLEN)")
     p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
+    p = sub.add_parser("mgcep", help="x2x +sf | frame | window | mgcep at gamma 0: mel-cepstra of a list of raw or wav files")
+    p.add_argument("--scp", required=True, help="job list: the .raw (int16) or wav file, then the mgc file to write")
+    p.add_argument("--frame-length", type=int, default=1200, help="FRAMELEN")
+    p.add_argument("--frame-shift", type=int, default=240, help="FRAMESHIFT")
+    p.add_argument("--fft-length", type=int, default=2048, help="FFTLEN")
+    p.add_argument("--window", type=int, default=1, help="WINDOWTYPE: 0 Blackman, 1 Hamming, 2 Hanning (5 rectangular)")
+    p.add_argument("--normalize", type=int, default=1, help="NORMALIZE: 0 none, 1 power, 2 magnitude")
+    p.add_argument("--alpha", type=float, default=0.55, help="FREQWARP")
+    p.add_argument("--order", type=int, default=49, help="MGCORDER: a row holds order + 1 float32")
+    p.add_argument("--eps", type=float, default=1.0e-8, help="mgcep -e: added to the periodogram")
+    p.add_argument("--no-pipe-float32", action="store_true", help="keep the windowed samples in double (SPTK built with "
+                   "DOUBLE), not rounded to float32 as the pipe between window and mgcep does")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose mgc file is already complete")
+    p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
     for cmd in ("mspf-stats", "mspf"):
         p = sub.add_parser(cmd, help="make_mspf: statistics of the modulation spectra of a list of files" if cmd == "mspf-stats"
                            else "postfiltering_mspf: the modulation-spectrum postfilter on a list of mgc files")
@@ -1836,6 +1949,17 @@ def main(argv=None):
         n = mspf_files(_read_scp(a.scp, 2), a.dim, a.gen_stats, a.nat_stats, a.name, a.emphasis, a.frame_length,
                        a.fft_length, resume=a.resume)
         print("complete. %d frames" % n)
+        return 0
+    if a.cmd == "mgcep":
+        try:
+            mgcep_check(a.frame_length, a.frame_shift, a.fft_length, a.window, a.normalize, a.alpha, a.order, a.eps,
+                        a.max_batch_frames)
+        except ValueError as err:
+            ap.error(str(err))
+        n, flagged = mgcep_files(_read_scp(a.scp, 2), a.frame_length, a.frame_shift, a.fft_length, a.window, a.normalize,
+                                 a.alpha, a.order, a.eps, pipe_float32=not a.no_pipe_float32,
+                                 max_batch_frames=a.max_batch_frames, resume=a.resume)
+        print("complete. %d frames, %d utterances flagged" % (n, len(flagged)))
         return 0
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)

@@ -206,6 +206,10 @@ def load_library():
     L.WorldMi355DefaultMcepOption.restype = None
     L.WorldMi355DefaultMcepOption.argtypes = [C.POINTER(McepOption)]
     L.WorldMi355MelCepstrum.argtypes = [vp, vp, C.POINTER(McepOption), vp, vp]
+    L.WorldMi355SptkFrames.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    L.WorldMi355SptkWindow.argtypes = [C.c_int, C.c_int, C.c_int, _dp]
+    L.WorldMi355MelCepstrumOfFrames.argtypes = [vp, vp, C.POINTER(McepOption), vp, vp]
+    L.WorldMi355MelCepstrumOfWaveform.argtypes = [vp, vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(McepOption), vp, vp]
     L.WorldMi355DefaultMgc2spOption.restype = None
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
@@ -399,6 +403,24 @@ def _ints(a):
         return None, None
     arr = np.ascontiguousarray(a, dtype=np.int32)
     return arr, arr.ctypes.data_as(_ip)
+
+
+def sptk_frames(n_samples, frame_length, frame_shift):
+    """The number of frames SPTK's `frame -l frame_length -p frame_shift` makes of n_samples samples
+    (WorldMi355SptkFrames: ceil((T + frame_length // 2) / frame_shift), 0 for T = 0).  Host only."""
+    n = C.c_int64(0)
+    _check(load_library().WorldMi355SptkFrames(int(n_samples), int(frame_length), int(frame_shift), C.byref(n)),
+           "SptkFrames")
+    return int(n.value)
+
+
+def sptk_window(type, normalize, length):
+    """The table of SPTK's `window -l length -w type -n normalize` as float64 [length] (WorldMi355SptkWindow): type 0
+    Blackman, 1 Hamming, 2 Hanning, 5 rectangular; normalize 0 none, 1 sum w^2 = 1, 2 sum w = 1.  Host only."""
+    w = np.zeros(max(int(length), 1), dtype=np.float64)
+    _check(load_library().WorldMi355SptkWindow(int(type), int(normalize), int(length), w.ctypes.data_as(_dp)),
+           "SptkWindow")
+    return w[:int(length)]
 
 
 class WorldBatch:
@@ -636,6 +658,55 @@ class WorldBatch:
         status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
         _check(load_library().WorldMi355MelCepstrum(self.handle, self._p(spectrum), C.byref(o), self._p(mc),
                                                     C.c_void_p(status.data_ptr())), "MelCepstrum")
+        return mc, status
+
+    def _mcep_option(self, where, order, alpha, opt):
+        o = McepOption()
+        load_library().WorldMi355DefaultMcepOption(C.byref(o))
+        o.order, o.alpha, o.itype = int(order), float(alpha), 0
+        for k, v in opt.items():
+            if k not in ("itr1", "itr2", "dd", "etype", "e", "f", "itype"):
+                raise TypeError(f"{where}: unknown option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def mel_cepstrum_of_frames(self, frames, order=25, alpha=0.35, **opt):
+        """SPTK's mcep with itype 0 per frame (test/sptkfunctions.cpp:11-184 with flng = fft_size): frames is float64 cuda
+        [total_frames][fft_size], windowed and zero-padded.  Options as mel_cepstrum's; etype 2 (the floor e < 0 dB below
+        the frame's maximum) is taken here.  Returns (mc, status) as mel_cepstrum does."""
+        import torch
+        o = self._mcep_option("mel_cepstrum_of_frames", order, alpha, opt)
+        if (tuple(frames.shape) != (self.total_frames, self.fft_size) or frames.dtype != torch.float64
+                or not frames.is_cuda or not frames.is_contiguous()):
+            raise ValueError(f"mel_cepstrum_of_frames: frames must be a contiguous float64 cuda tensor "
+                             f"[{self.total_frames}][{self.fft_size}], got {frames.dtype} {tuple(frames.shape)}")
+        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MelCepstrumOfFrames(self.handle, self._p(frames), C.byref(o), self._p(mc),
+                                                            C.c_void_p(status.data_ptr())), "MelCepstrumOfFrames")
+        return mc, status
+
+    def mel_cepstrum_of_waveform(self, x, window, frame_length, frame_shift, order=25, alpha=0.35, pipe_float32=False,
+                                 **opt):
+        """`frame -l frame_length -p frame_shift | window | mgcep` at gamma 0 from the batch's packed samples: x float64
+        cuda [total_samples]; window the host table of frame_length doubles (sptk_window's); the batch's f0_lengths must
+        be sptk_frames of its x_lengths.  pipe_float32 rounds every windowed sample to float32 once, as SPTK's pipe does.
+        Options as mel_cepstrum_of_frames'.  Returns (mc, status) as mel_cepstrum does."""
+        import torch
+        o = self._mcep_option("mel_cepstrum_of_waveform", order, alpha, opt)
+        if (tuple(x.shape) != (self.total_samples,) or x.dtype != torch.float64 or not x.is_cuda
+                or not x.is_contiguous()):
+            raise ValueError(f"mel_cepstrum_of_waveform: x must be a contiguous float64 cuda tensor "
+                             f"[{self.total_samples}], got {x.dtype} {tuple(x.shape)}")
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        if w.shape != (max(int(frame_length), 0),):
+            raise ValueError(f"mel_cepstrum_of_waveform: window must hold frame_length = {frame_length} values, "
+                             f"got {w.shape}")
+        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MelCepstrumOfWaveform(
+            self.handle, self._p(x), w.ctypes.data_as(_dp), int(frame_length), int(frame_shift), 1 if pipe_float32 else 0,
+            C.byref(o), self._p(mc), C.c_void_p(status.data_ptr())), "MelCepstrumOfWaveform")
         return mc, status
 
     def spectrum_from_mel_cepstrum(self, mc, alpha=0.35, gamma=0.0, out_format=0, phase=False):

@@ -204,7 +204,8 @@ int WorldMi355RecipeDecode(WorldMi355Batch* b, const float* lf0, const float* mg
  * arguments (:11-13): alpha a, order m, itr1 / itr2 the least / most Newton steps (:142-158), dd the end condition
  * (:153), etype 0 nothing or 1 `e` added to the periodogram (:31-33; 2, the dB floor of :104-117, is WM_ERR_UNSUPPORTED),
  * f theq's singularity threshold (theq.cpp:90-104, negative: 1e-6), itype 3 amplitude or 4 periodogram rows (:85-94;
- * 0 / 1 / 2 are WM_ERR_UNSUPPORTED). */
+ * 0 / 1 / 2 are WM_ERR_UNSUPPORTED here).  itype 0, windowed frames, and etype 2 are what WorldMi355MelCepstrumOfFrames and
+ * WorldMi355MelCepstrumOfWaveform below take, with this same struct. */
 typedef struct {
   double alpha;
   int order;
@@ -225,6 +226,41 @@ void WorldMi355DefaultMcepOption(WorldMi355McepOption* opt);
  * WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's stream. */
 int WorldMi355MelCepstrum(WorldMi355Batch* b, const double* spectrum, const WorldMi355McepOption* opt, double* mc,
                           int* status);
+
+/* ---- Mel-cepstra from windowed frames and from waveforms: the recipe line that starts at a waveform
+ * (data/Makefile.in:134-137),
+ *   x2x +sf raw | frame -l L -p P | window -l L -L fft_size -w type -n norm | mgcep -a alpha -m order -l fft_size -e eps
+ * at gamma 0, mgcep being mcep (test/sptkfunctions.cpp:11-184) with itype 0, "windowed data sequence" (:66-72): fftr,
+ * x[k] = re^2 + im^2 + eps (:68-71), for etype 2 the floor at max 10^(e / 10) (:104-117), then as WorldMi355MelCepstrum.
+ * SPTK's frame and window are not in the reference tree; they are taken by this definition:
+ *   frame    an utterance of T >= 1 samples x[0 .. T), length L, shift P, 1 <= P <= L <= fft_size, has
+ *            J = ceil((T + L / 2) / P) frames (L / 2 rounded down); frame j holds z[i] = x[j P - L / 2 + i], i < L, zero
+ *            outside [0, T): frame 0 is centred on sample 0, and frames go on while they hold a sample.  T = 0: J = 0.
+ *   window   a = 2 pi / (L - 1); type 0 Blackman 0.42 - 0.5 cos(a i) + 0.08 cos(2 a i), 1 Hamming 0.54 - 0.46 cos(a i),
+ *            2 Hanning 0.5 - 0.5 cos(a i), 5 rectangular (3 Bartlett and 4 trapezoid: WM_ERR_UNSUPPORTED); normalize 0 as
+ *            it is, 1 scaled to sum w^2 = 1, 2 to sum w = 1; computed in double.  The windowed frame is w[i] z[i], one
+ *            multiply, and fft_size - L zeros; with pipe_float32 every product is rounded to float32 once, which is what
+ *            SPTK's pipe between `window` and `mgcep` carries.
+ * Both host only, no device needed: n_frames of n_samples, or WM_ERR_BAD_ARG outside 1 <= frame_shift <= frame_length or
+ * for n_samples < 0; the table w[length], or WM_ERR_BAD_ARG for a type outside 0 .. 5, normalize outside 0 .. 2,
+ * length < 2 or a table to be normalised whose sum is not positive. */
+int WorldMi355SptkFrames(int64_t n_samples, int frame_length, int frame_shift, int64_t* n_frames);
+int WorldMi355SptkWindow(int type, int normalize, int length, double* w);
+/* frames: DEVICE double[total_frames][fft_size], windowed and zero-padded; mc, status and their codes as
+ * WorldMi355MelCepstrum's (rows of status 2 -- a periodogram value <= 0 or non-finite after eps and the floor -- are zeros).
+ * opt->itype must be 0; etype 0, 1 (e >= 0) or 2 (e < 0, :26-29); order, step and alpha limits as WorldMi355MelCepstrum's;
+ * anything else is WM_ERR_BAD_ARG before any device call.  Asynchronous on the context's stream. */
+int WorldMi355MelCepstrumOfFrames(WorldMi355Batch* b, const double* frames, const WorldMi355McepOption* opt, double* mc,
+                                  int* status);
+/* The same from the samples: x DEVICE, the batch's packed samples as WorldMi355Dio takes them
+ * (WorldMi355BatchSampleOffsets); window HOST double[frame_length] (WorldMi355SptkWindow's, or the caller's own), uploaded
+ * by the library; mc DEVICE double[total_frames][order+1].  The batch's f0_lengths must be WorldMi355SptkFrames of its
+ * x_lengths, and frame_length <= fft_size, 1 <= frame_shift <= frame_length, else WM_ERR_BAD_ARG before any device call.
+ * The frames are gathered, windowed and transformed on the way in: neither they nor their periodograms exist in device
+ * memory.  The bits are those of WorldMi355MelCepstrumOfFrames on the frames of the definition above. */
+int WorldMi355MelCepstrumOfWaveform(WorldMi355Batch* b, const double* x, const double* window, int frame_length,
+                                    int frame_shift, int pipe_float32, const WorldMi355McepOption* opt, double* mc,
+                                    int* status);
 
 /* ---- Spectra from mel-generalized cepstra: the CLIs' SPTK port, mgc2sp(mgc, m, a, g, x, y, flng = fft_size)
  * (test/sptkfunctions.cpp:186-219) = mgc2mgc towards alpha 0, gamma 0 and fft_size/2 coefficients (:221-254: freqt
@@ -657,7 +693,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
+ * "synth_ola_kernel", "mcep_kernel", "mgcep_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
  * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
  * column kernels and trj_reduce_kernel as one record, "dnn_layer_kernel": all layers of a call as one record,
  * "dnn_cost_kernel", "optimizer_step_kernel", "label_match_kernel", "ffi_rows_kernel").  Enable clears earlier records; Query synchronises the stream and
