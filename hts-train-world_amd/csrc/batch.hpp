@@ -282,7 +282,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mspf, trj, dnn, ffi, mgcep;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -364,6 +364,18 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
                 const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
                 const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
                 const WorldMi355MlpgOption& opt, float* const* out, int* d_status);
+int launch_mlpg_flags(Batch& b, hipStream_t st, int n_streams, const float* const* mean, int64_t ld_mean,
+                      const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                      const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
+                      const WorldMi355MlpgOption& opt, float* const* out, int* d_status, int* d_colflag);
+int check_mlpg_gv(int n_streams, const int* dims, const float* const* gv_mean, const float* const* gv_var,
+                  const WorldMi355GvOption* gv);
+int launch_mlpg_gv(Batch& b, hipStream_t st, int n_streams, const float* const* mean, int64_t ld_mean,
+                   const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                   const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
+                   const WorldMi355MlpgOption& opt, const float* const* gv_mean, const float* const* gv_var,
+                   const unsigned char* gv_mask, const WorldMi355GvOption& gv, float* const* out, double* info,
+                   int* d_status);
 int check_trj(int n_streams, const float* const* pred, const float* const* obs, int64_t ld, const float* const* var,
               const float* const* gv_var, const int* dims, const int* n_windows, const double* const* const* windows,
               const int* const* window_sizes, const float* const* msd_pred, const float* const* msd_obs,

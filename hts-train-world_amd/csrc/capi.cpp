@@ -366,6 +366,31 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
   return on_batch(b, launch_mlpg, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, msd,
                   *opt, out, status);
 }
+void WorldMi355DefaultGvOption(WorldMi355GvOption* o) {                         // configure.ac:808-880
+  if (!o) return;
+  o->max_iter = 50;
+  o->scale = 1;
+  o->epsilon = 1.0e-4;
+  o->step_init = 1.0;
+  o->step_inc = 1.2;
+  o->step_dec = 0.5;
+  o->hmm_weight = 1.0;
+  o->gv_weight = 1.0;
+}
+int WorldMi355ParameterGenerationGv(WorldMi355Batch* b, int n_streams, const float* const* mean, int64_t ld_mean,
+                                    const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                                    const double* const* const* windows, const int* const* window_sizes,
+                                    const float* const* msd, const WorldMi355MlpgOption* opt,
+                                    const float* const* gv_mean, const float* const* gv_var,
+                                    const unsigned char* gv_mask, const WorldMi355GvOption* gv, float* const* out,
+                                    double* info, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mlpg(n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, opt, out))
+    return rc;                                                                  // refused before any device call
+  if (const int rc = check_mlpg_gv(n_streams, dims, gv_mean, gv_var, gv)) return rc;
+  return on_batch(b, launch_mlpg_gv, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, msd,
+                  *opt, gv_mean, gv_var, gv_mask, *gv, out, info, status);
+}
 void WorldMi355DefaultTrajectoryOption(WorldMi355TrajectoryOption* o) {         // DNNDefine.py:248-249
   if (!o) return;
   o->edge = 0;

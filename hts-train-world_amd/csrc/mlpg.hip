@@ -54,9 +54,17 @@ __device__ __forceinline__ double mlpg_coef(const double (*wz)[kMlpgRow], int ed
   return a;
 }
 
+// Where a flagged column is also recorded by itself (the status word is per utterance): p[u * width + col0[slot] + col],
+// for the GV generation that follows the solve (mlpg_gv.hip).  p == nullptr: nothing is recorded.
+struct MlpgColFlags {
+  int* p;
+  int width;
+  int col0[kWinMaxStreams];
+};
+
 template <int B>
 __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __restrict__ f_off,
-                                                  double* __restrict__ ws, int* __restrict__ status) {
+                                                  double* __restrict__ ws, int* __restrict__ status, MlpgColFlags cf) {
   constexpr int BB = B > 0 ? B : 1;
   const BandBlock blk = band_decode(m.t);
   const int s = blk.s, u = blk.u, col = blk.col;
@@ -193,6 +201,7 @@ __global__ __launch_bounds__(64) void mlpg_kernel(MlpgMeta m, const int64_t* __r
   const bool flagged = bad || sing;
   if (flagged) {
     if (status != nullptr) atomicOr(status + u, bad ? 1 : 2);
+    if (cf.p != nullptr) cf.p[(int64_t)u * cf.width + cf.col0[s] + col] = 1;
     for (int t = 0; t < T; ++t) out[(fb + t) * (int64_t)dim] = 0.0f;
     return;
   }
@@ -239,6 +248,16 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
                 const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
                 const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
                 const WorldMi355MlpgOption& opt, float* const* out, int* d_status) {
+  return launch_mlpg_flags(b, st, n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, msd, opt,
+                           out, d_status, nullptr);
+}
+
+// launch_mlpg, which also sets d_colflag[u][column over the statics of all streams] of every flagged column (the caller
+// zeroes it); nullptr: launch_mlpg itself.
+int launch_mlpg_flags(Batch& b, hipStream_t st, int n_streams, const float* const* mean, int64_t ld_mean,
+                      const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                      const double* const* const* windows, const int* const* window_sizes, const float* const* msd,
+                      const WorldMi355MlpgOption& opt, float* const* out, int* d_status, int* d_colflag) {
   if (const int rc = check_mlpg(n_streams, mean, ld_mean, var, ld_var, dims, n_windows, windows, window_sizes, &opt, out))
     return rc;
   if (b.total_f <= 0 || b.n_utt <= 0) return WM_OK;
@@ -277,11 +296,17 @@ int launch_mlpg(Batch& b, hipStream_t st, int n_streams, const float* const* mea
       m.out[k] = out[src[k]];
     }
     double* d_ws = W != nullptr ? W->d : nullptr;
+    MlpgColFlags cf;
+    memset(&cf, 0, sizeof(cf));
+    cf.p = d_colflag;
+    for (int q = 0; q < n_streams; ++q) cf.width += dims[q];
+    for (int k = 0; k < m.t.n_streams; ++k)
+      for (int q = 0; q < src[k]; ++q) cf.col0[k] += dims[q];
     switch (kBands[g]) {
-      case 0: hipLaunchKernelGGL((mlpg_kernel<0>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status); break;
-      case 2: hipLaunchKernelGGL((mlpg_kernel<2>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status); break;
-      case 4: hipLaunchKernelGGL((mlpg_kernel<4>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status); break;
-      default: hipLaunchKernelGGL((mlpg_kernel<14>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status); break;
+      case 0: hipLaunchKernelGGL((mlpg_kernel<0>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status, cf); break;
+      case 2: hipLaunchKernelGGL((mlpg_kernel<2>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status, cf); break;
+      case 4: hipLaunchKernelGGL((mlpg_kernel<4>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status, cf); break;
+      default: hipLaunchKernelGGL((mlpg_kernel<14>), dim3(blocks), dim3(64), 0, st, m, b.d_f_off, d_ws, d_status, cf); break;
     }
   }
   return wm_check(hipGetLastError());

@@ -35,6 +35,7 @@ SYNTHESIS_STREAMS = ("mgc", "lf0", "bap")            # what recipe_decode and sy
 FFT_SIZES = (512, 1024, 2048, 4096)                  # the sizes recipe_decode and synthesize are built for
 STAGES = ("ffi", "forward", "mlpg", "postfilter")    # the status word's fields, 4 bits each, in this order
 FFI_BITS, FORWARD_SHIFT, MLPG_SHIFT, POSTFILTER_SHIFT = 0xF, 4, 8, 12
+GV_KEPT_MLPG = 4                                     # parameter_generation_gv: a column had no variance to work on; mlpg's stands
 
 
 def y_length(n_frames, frame_period, fs):
@@ -72,10 +73,12 @@ def status_word(ffi, forward, mlpg, postfilter):
 
 def flagged_stage(word):
     """(stage name, that stage's status) of the first stage that flagged the utterance, or None: the ffi bits are
-    warnings (a value was clamped; no state-level information), as in ffi_files."""
-    for name, shift in (("forward", FORWARD_SHIFT), ("mlpg", MLPG_SHIFT), ("postfilter", POSTFILTER_SHIFT)):
-        if (int(word) >> shift) & 0xF:
-            return name, (int(word) >> shift) & 0xF
+    warnings (a value was clamped; no state-level information), as in ffi_files, and so is GV generation's 4 in the
+    mlpg field (an utterance of one frame, an unvoiced one: the trajectory is mlpg's, which is a waveform to use)."""
+    for name, shift, bits in (("forward", FORWARD_SHIFT, 0xF), ("mlpg", MLPG_SHIFT, 0xF & ~GV_KEPT_MLPG),
+                              ("postfilter", POSTFILTER_SHIFT, 0xF)):
+        if (int(word) >> shift) & bits:
+            return name, (int(word) >> shift) & bits
     return None
 
 
@@ -123,7 +126,29 @@ class _Setup:
                 int(fft_size), FFT_SIZES[0], FFT_SIZES[-1], ", ".join(str(f) for f in FFT_SIZES)))
         self.fs, self.frame_period, self.fft_size = int(fs), float(frame_period), int(fft_size)
         self.alpha, self.edge, self.unvoiced_value = float(alpha), int(edge), float(unvoiced_value)
-        self.postfilter, self.tables = self._postfilter(postfilter, dim_of("mgc"))
+        if postfilter is not None and postfilter[0] == "gv":
+            self.postfilter, self.tables = self._gv(postfilter, [d for d, _, _ in self.streams])
+        else:
+            self.postfilter, self.tables = self._postfilter(postfilter, dim_of("mgc"))
+
+    @staticmethod
+    def _gv(choice, dims):
+        """("gv", gv_mean, gv_var, options): gv.mean and gv.var of gv_pdf_files (paths, or float32 rows over the static
+        columns of all streams) and a dict of gen_param_gv_files' options.  Returns (("gv", options), per stream
+        (gv_mean, gv_var))."""
+        if len(choice) != 4:
+            raise ValueError('postfilter ("gv", gv_mean, gv_var, options) takes three values, got %d' % (len(choice) - 1))
+        options = dict(choice[3] or {})
+        unknown = sorted(set(options) - set(R.GV_OPTIONS))
+        if unknown:
+            raise ValueError("postfilter gv: unknown option %s" % ", ".join(unknown))
+        rows = [np.fromfile(str(a), dtype=np.float32) if isinstance(a, (str, os.PathLike)) else np.asarray(a, dtype=np.float32)
+                for a in choice[1:3]]
+        for what, r in zip(("gv_mean", "gv_var"), rows):
+            if r.shape != (sum(dims),):
+                raise ValueError("postfilter gv: %s holds %d values, the streams have %d static columns" % (what, r.size, sum(dims)))
+        at = np.concatenate([[0], np.cumsum(dims)])
+        return ("gv", options), [(rows[0][at[k]:at[k + 1]], rows[1][at[k]:at[k + 1]]) for k in range(len(dims))]
 
     @staticmethod
     def _postfilter(choice, dim):
@@ -148,8 +173,8 @@ class _Setup:
 
             tables = (table(gen_dir, 0), table(gen_dir, 1), table(nat_dir, 0), table(nat_dir, 1))
             return ("mspf", float(emphasis), int(frame_length), int(fft_length)), tables
-        raise ValueError('postfilter is None, ("mcp", beta, length) or ("mspf", gen_stats_dir, nat_stats_dir, emphasis, '
-                         "frame_length, fft_length)")
+        raise ValueError('postfilter is None, ("mcp", beta, length), ("mspf", gen_stats_dir, nat_stats_dir, emphasis, '
+                         'frame_length, fft_length) or ("gv", gv_mean, gv_var, options)')
 
 
 class Generated:
@@ -189,6 +214,8 @@ class Generator:
                  named mgc, lf0 and bap feed synthesis, any other (vib) is generated and returned
     postfilter:  None, ("mcp", beta, length) -- postfilter_files on the mgc stream at `alpha` --, or ("mspf",
                  gen_stats_dir, nat_stats_dir, emphasis, frame_length, fft_length) -- mspf_files on mgc_dim<d>.mean / .stdd
+                 --, or ("gv", gv_mean, gv_var, options) -- gen_param_gv_files' generation in MLPG's place and, as gen_wave
+                 does with GV generation on, no postfilter after it; its status is the status word's mlpg field
     edge, unvoiced_value: as gen_param_files
     ctx:         a world.Context, or None for one of its own (closed by close()).  The casts between the library's calls
                  are torch's: with a context on a caller's stream, call with that stream as torch's current one.
@@ -210,6 +237,9 @@ class Generator:
             self.model = s.model.cuda()
             self.var_row = self.model.variance.variances[s.spkr].detach().to(torch.float32)       # forward_files' var_row
             self.params = W.default_params(s.fs, s.frame_period, fft_size=s.fft_size)              # synth_files' params
+            self.gv = None
+            if s.postfilter and s.postfilter[0] == "gv":                                           # gen_param_gv_files' rows
+                self.gv = ([R._upload(m) for m, _ in s.tables], [R._upload(v) for _, v in s.tables])
         except BaseException:
             self.close()
             raise
@@ -242,13 +272,17 @@ class Generator:
             ffo, _, st_fwd = self.model.infer(b, ffi, [s.spkr] * len(frames))                       # forward_files
             args = [(ffo[:, c0:c0 + n], self.var_row[c0:c0 + n], wins, None if mcol is None else ffo[:, mcol])
                     for (mcol, c0, n), (_, wins, _) in zip(s.layout, s.streams)]                    # gen_param_files
-            outs, st_mlpg = b.parameter_generation(args, edge=s.edge, unvoiced_value=s.unvoiced_value)
+            if self.gv is not None:                                                                 # gen_param_gv_files
+                outs, st_mlpg = b.parameter_generation_gv(args, self.gv[0], self.gv[1], edge=s.edge,
+                                                          unvoiced_value=s.unvoiced_value, **s.postfilter[1])
+            else:
+                outs, st_mlpg = b.parameter_generation(args, edge=s.edge, unvoiced_value=s.unvoiced_value)
             gen = dict(zip(s.stream_names, outs))
             p_mgc, st_post = None, None
             if s.postfilter and s.postfilter[0] == "mcp":                                           # postfilter_files
                 out, st_post = b.postfilter_mel_cepstrum(gen["mgc"].double(), s.alpha, s.postfilter[1], s.postfilter[2])
                 p_mgc = out.float()
-            elif s.postfilter:                                                                      # mspf_files
+            elif s.postfilter and s.postfilter[0] == "mspf":                                        # mspf_files; gv: none (gen_wave:749-757)
                 out, st_post = b.postfilter_modulation_spectrum(gen["mgc"].double(), *s.tables, *s.postfilter[1:])
                 p_mgc = out.float()
             f0, sp, ap = b.recipe_decode(gen["lf0"].reshape(-1), gen["mgc"] if p_mgc is None else p_mgc, gen["bap"])

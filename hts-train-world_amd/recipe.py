@@ -27,6 +27,9 @@ features travel to rank 0, which writes them all.
            --spec-dim 50 --ap-dim 25          # jobs.txt: one "f0 sp ap wav" per line
 
 cmp_files() is the stage after it (data/Makefile.in:244-323: window.pl per stream, merge, addhtkheader.pl).
+gv_pdf_files() / `gv-pdf` and gen_param_gv_files() / `gen-param-gv` are gen-param for a voice trained with GV: the pdf
+of the per-utterance variances that `gv-data` writes, and parameter generation that also maximises its likelihood
+(HMGenS with USEHMMGV = 1, scripts/Training.pl:1892-1903), after which gen_wave skips the postfilter (:749-757).
 gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
 model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is the step gen_wave takes between the two
 (scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With USEMSPF gen_wave takes
@@ -490,6 +493,14 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
     var_path: one float32 row in the ffo layout, the global variances (:2788-2791)
     A frame with voicing value below 0.5 (:2782) receives unvoiced_value in every dim of its stream (:2783, :2800-2801).
     Rank-sharded by frame count; with resume, utterances whose stream files are complete are skipped."""
+    return _gen_param(jobs, streams, var_path, ctx, max_batch_frames, io_threads, resume,
+                      lambda b, group, args: b.parameter_generation(args, edge=edge, unvoiced_value=unvoiced_value),
+                      "the flagged columns are zeros")
+
+
+def _gen_param(jobs, streams, var_path, ctx, max_batch_frames, io_threads, resume, generate, flagged_means):
+    """gen_param_files and gen_param_gv_files: the job list, the plan and the stream files are the same;
+    generate(batch, group, parameter_generation's streams) -> (outs, status) is the call in the middle."""
     jobs = list(jobs)
     streams = _streams_arg(streams)
     layout, width = ffo_layout(streams)
@@ -505,13 +516,90 @@ def gen_param_files(jobs, streams, var_path, edge=0, unvoiced_value=-1.0e10, ctx
                 rows = stage.load([jobs[i][0] for i in group], width)
                 args = [(rows[:, c0:c0 + n], dvar[c0:c0 + n], wins, None if mcol is None else rows[:, mcol])
                         for (mcol, c0, n), (_, wins, _) in zip(layout, streams)]
-                outs, status = b.parameter_generation(args, edge=edge, unvoiced_value=unvoiced_value)
+                outs, status = generate(b, [jobs[i] for i in group], args)
                 for k in np.nonzero(status.cpu().numpy())[0]:
-                    print("warning: %s: status %d, the flagged columns are zeros" % (jobs[group[k]][0], int(status[k])),
+                    print("warning: %s: status %d, %s" % (jobs[group[k]][0], int(status[k]), flagged_means),
                           file=sys.stderr)
                 for s_, o in enumerate(outs):
                     stage.put(b, o.cpu().numpy(), [jobs[i][1 + s_] for i in group])
     return stage.frames
+
+
+# ---- parameter generation considering global variance (HMGenS with USEHMMGV = 1; scripts/Training.pl:1892-1903) --------
+GV_OPTIONS = ("max_iter", "epsilon", "step_init", "step_inc", "step_dec", "hmm_weight", "gv_weight", "scale")
+
+
+def gv_pdf_files(cmp_paths, out_dir):
+    """The GV pdf of a corpus from the one-vector HTK files that gv_data_files writes (12 bytes of header, then one
+    float32 row over the static columns of all streams): out_dir/gv.mean and out_dir/gv.var, the mean and the variance
+    (dividing by n, as stats_files does) of every column over the files, float32.  Host only; in double, two passes.
+    Returns the number of files read."""
+    rows = [np.fromfile(str(p), dtype=np.float32, offset=12).astype(np.float64) for p in cmp_paths]
+    if not rows:
+        raise ValueError("gv_pdf_files: no file")
+    for p, r in zip(cmp_paths, rows):
+        if r.size != rows[0].size or r.size == 0:
+            raise ValueError("%s holds %d values, %s holds %d" % (p, r.size, cmp_paths[0], rows[0].size))
+    x = np.stack(rows)
+    mean = x.mean(axis=0)
+    var = ((x - mean) ** 2).mean(axis=0)
+    os.makedirs(str(out_dir), exist_ok=True)
+    mean.astype(np.float32).tofile(os.path.join(str(out_dir), "gv.mean"))
+    var.astype(np.float32).tofile(os.path.join(str(out_dir), "gv.var"))
+    return len(rows)
+
+
+def gv_label_mask(lines, frame_shift_s, n_rows, silences=()):
+    """uint8 [n_rows]: 1 on the rows mspf_label_rows keeps, 0 on the rest -- the frames of the segments named in
+    `silences` (the recipe's NOSILGV) and whatever no label line covers."""
+    mask = np.zeros(n_rows, dtype=np.uint8)
+    mask[mspf_label_rows(lines, frame_shift_s, n_rows, silences)] = 1
+    return mask
+
+
+def gen_param_gv_files(jobs, streams, var_path, gv_mean_path, gv_var_path, label_dir=None, silences=(),
+                       frame_shift_s=0.005, edge=0, unvoiced_value=-1.0e10, ctx=None, max_batch_frames=MAX_BATCH_FRAMES,
+                       io_threads=8, resume=False, **options):
+    """gen_param_files with parameter generation considering global variance in mlpg's place
+    (WorldBatch.parameter_generation_gv): the same jobs, streams, var_path, files and resume rule.
+
+    gv_mean_path, gv_var_path: gv.mean and gv.var of gv_pdf_files, float32 rows over the static columns of all streams
+    label_dir, silences: with both, <label_dir>/<base of ffo_in>.lab says where the segments named in `silences` lie
+              (frames of frame_shift_s seconds, the rows of mspf_label_rows); GV is switched off in their frames
+    options:  max_iter, epsilon, step_init, step_inc, step_dec, hmm_weight, gv_weight, scale (GV_OPTIONS); the recipe's
+              defaults where left out
+    A status of 1 or 4 leaves the column as gen_param_files writes it; see parameter_generation_gv."""
+    unknown = sorted(set(options) - set(GV_OPTIONS))
+    if unknown:
+        raise TypeError("gen_param_gv_files: unknown option %s" % ", ".join(unknown))
+    specs = _streams_arg(streams)
+    static = sum(int(d) for d, _, _ in specs)
+    gv = [np.fromfile(str(p), dtype=np.float32) for p in (gv_mean_path, gv_var_path)]
+    for p, a in zip((gv_mean_path, gv_var_path), gv):
+        if a.size != static:
+            raise ValueError("%s has %d values, the streams have %d static columns" % (p, a.size, static))
+    silences = tuple(silences)
+    dev = {}
+
+    def generate(b, group, args):
+        if not dev:
+            at = np.concatenate([[0], np.cumsum([int(d) for d, _, _ in specs])])
+            dev["mean"] = [_upload(gv[0][at[k]:at[k + 1]]) for k in range(len(specs))]
+            dev["var"] = [_upload(gv[1][at[k]:at[k + 1]]) for k in range(len(specs))]
+        mask = None
+        if label_dir is not None and silences:
+            parts = []
+            for k, job in enumerate(group):
+                lab = os.path.join(str(label_dir), os.path.splitext(os.path.basename(job[0]))[0] + ".lab")
+                with open(lab) as f:
+                    parts.append(gv_label_mask(f.readlines(), frame_shift_s, int(b.frame_offsets[k + 1] - b.frame_offsets[k]),
+                                               silences))
+            mask = _upload(np.concatenate(parts))
+        return b.parameter_generation_gv(args, dev["mean"], dev["var"], gv_mask=mask, edge=edge,
+                                         unvoiced_value=unvoiced_value, **options)
+
+    return _gen_param(jobs, streams, var_path, ctx, max_batch_frames, io_threads, resume, generate,
+                      "columns flagged 1 or 2 by mlpg are zeros, the others are mlpg's")
 
 
 # ---- trajectory training's criterion and outputs (scripts/Training.pl:930-940, DNNDefine.trajectory_cost) --------------
@@ -1714,6 +1802,10 @@ def generate_arguments(ap, a):
         if not (a.gen_stats and a.nat_stats):
             ap.error("--postfilter mspf needs --gen-stats and --nat-stats")
         post = ("mspf", a.gen_stats, a.nat_stats, a.emphasis, a.mspf_frame_length, a.mspf_fft_length)
+    elif a.postfilter == "gv":
+        if not (a.gv_mean and a.gv_var):
+            ap.error("--postfilter gv needs --gv-mean and --gv-var")
+        post = ("gv", a.gv_mean, a.gv_var, {} if a.gv_max_iter is None else {"max_iter": a.gv_max_iter})
     if a.frame_shift < 1:
         ap.error("--frame-shift must be positive")
     return dict(config=a.config, frame_shift=a.frame_shift, model=a.model, spkr=a.spkr, streams=a.stream, fs=a.fs,
@@ -1755,6 +1847,30 @@ def main(argv=None):
     p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
                    help="one per stream in the row's order: dimension, 1 if a voicing column precedes it, window files")
     p.add_argument("--var", required=True, help="one float32 row of variances in the ffo layout")
+    p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
+    p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
+    p.add_argument("--resume", action="store_true", help="skip utterances whose stream files are already complete")
+    p = sub.add_parser("gv-pdf", help="gv.mean and gv.var from the one-vector files of gv-data")
+    p.add_argument("--scp", required=True, help="one gv-data file per line")
+    p.add_argument("--out-dir", required=True)
+    p = sub.add_parser("gen-param-gv", help="gen-param with parameter generation considering global variance")
+    p.add_argument("--scp", required=True, help="job list: the ffo file, then one output path per stream")
+    p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
+                   help="one per stream in the row's order: dimension, 1 if a voicing column precedes it, window files")
+    p.add_argument("--var", required=True, help="one float32 row of variances in the ffo layout")
+    p.add_argument("--gv-mean", required=True, help="gv.mean of gv-pdf")
+    p.add_argument("--gv-var", required=True, help="gv.var of gv-pdf")
+    p.add_argument("--label-dir", default=None, help="where <base>.lab of every ffo file lies (with --silence)")
+    p.add_argument("--silence", action="append", default=[], help="a label name in whose segments GV is off (NOSILGV)")
+    p.add_argument("--frame-shift-s", type=float, default=0.005, help="seconds per frame of the labels")
+    p.add_argument("--max-iter", type=int, default=None, help="MAXGVITER (50)")
+    p.add_argument("--epsilon", type=float, default=None, help="GVEPSILON (1e-4)")
+    p.add_argument("--step-init", type=float, default=None, help="STEPINIT (1)")
+    p.add_argument("--step-inc", type=float, default=None, help="STEPINC (1.2)")
+    p.add_argument("--step-dec", type=float, default=None, help="STEPDEC (0.5)")
+    p.add_argument("--hmm-weight", type=float, default=None, help="HMMWEIGHT (1)")
+    p.add_argument("--gv-weight", type=float, default=None, help="GVWEIGHT (1)")
+    p.add_argument("--no-scale", action="store_true", help="start from mlpg's trajectory as it is")
     p.add_argument("--edge", type=int, default=0, help="0 taps beyond the ends dropped (SPTK), 1 clamped (window.pl)")
     p.add_argument("--unvoiced-value", type=float, default=-1.0e10)
     p.add_argument("--resume", action="store_true", help="skip utterances whose stream files are already complete")
@@ -1888,7 +2004,11 @@ def main(argv=None):
     p.add_argument("--frame-period", type=float, default=5.0)
     p.add_argument("--fft-size", type=int, required=True)
     p.add_argument("--alpha", type=float, required=True, help="frequency warping of the mgc stream (the mcp postfilter's)")
-    p.add_argument("--postfilter", default="none", choices=("none", "mcp", "mspf"))
+    p.add_argument("--postfilter", default="none", choices=("none", "mcp", "mspf", "gv"),
+                   help="gv: gen-param-gv in gen-param's place and no postfilter after it")
+    p.add_argument("--gv-mean", default=None, help="gv: gv.mean of gv-pdf")
+    p.add_argument("--gv-var", default=None, help="gv: gv.var of gv-pdf")
+    p.add_argument("--gv-max-iter", type=int, default=None, help="gv: MAXGVITER (50)")
     p.add_argument("--beta", type=float, default=1.4, help="mcp: the postfiltering coefficient (pf_mcp)")
     p.add_argument("--length", type=int, default=4096, help="mcp: bins of the energy sums (IMPLEN)")
     p.add_argument("--gen-stats", default=None, help="mspf: directory of the generated parameters' statistics")
@@ -1986,6 +2106,17 @@ def main(argv=None):
         for j, cost in zip(jobs, costs):
             if cost is not None:
                 print("Evaluation: cost = %e (%s)" % (cost, j[0]))
+        return 0
+    if a.cmd == "gv-pdf":
+        print("complete. %d files" % gv_pdf_files([r[0] for r in _read_scp(a.scp, 1)], a.out_dir))
+        return 0
+    if a.cmd == "gen-param-gv":
+        opts = {k: getattr(a, k) for k in GV_OPTIONS[:-1] if getattr(a, k) is not None}
+        if a.no_scale:
+            opts["scale"] = 0
+        n = gen_param_gv_files(_read_scp(a.scp, 1 + len(a.stream)), a.stream, a.var, a.gv_mean, a.gv_var, a.label_dir,
+                               a.silence, a.frame_shift_s, a.edge, a.unvoiced_value, resume=a.resume, **opts)
+        print("complete. %d frames" % n)
         return 0
     if a.cmd == "gen-param":
         n = gen_param_files(_read_scp(a.scp, 1 + len(a.stream)), a.stream, a.var, a.edge, a.unvoiced_value,

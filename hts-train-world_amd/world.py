@@ -85,6 +85,12 @@ class MlpgOption(C.Structure):
                 ("unvoiced_value", C.c_double)]
 
 
+class GvOption(C.Structure):
+    """include/world_mi355.h: WorldMi355GvOption (parameter generation considering global variance)."""
+    _fields_ = [("max_iter", C.c_int), ("scale", C.c_int), ("epsilon", C.c_double), ("step_init", C.c_double),
+                ("step_inc", C.c_double), ("step_dec", C.c_double), ("hmm_weight", C.c_double), ("gv_weight", C.c_double)]
+
+
 class TrajectoryOption(C.Structure):
     """include/world_mi355.h: WorldMi355TrajectoryOption (the trajectory training criterion, DNNDefine.trajectory_cost)."""
     _fields_ = [("edge", C.c_int), ("msd_weight", C.c_double), ("gv_weight", C.c_double)]
@@ -231,6 +237,10 @@ def load_library():
     L.WorldMi355DefaultMlpgOption.argtypes = [C.POINTER(MlpgOption)]
     L.WorldMi355ParameterGeneration.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp,
                                                 C.POINTER(MlpgOption), vp, vp]
+    L.WorldMi355DefaultGvOption.restype = None
+    L.WorldMi355DefaultGvOption.argtypes = [C.POINTER(GvOption)]
+    L.WorldMi355ParameterGenerationGv.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp,
+                                                  C.POINTER(MlpgOption), vp, vp, vp, C.POINTER(GvOption), vp, vp, vp]
     L.WorldMi355DefaultTrajectoryOption.restype = None
     L.WorldMi355DefaultTrajectoryOption.argtypes = [C.POINTER(TrajectoryOption)]
     L.WorldMi355TrajectoryCost.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -972,18 +982,28 @@ class WorldBatch:
         Returns ([float32 [total_frames][dim] per stream], status int32 [n_utt]: bit 1 a column with a non-finite or
         non-positive input, bit 2 a column whose matrix is not positive definite; such columns are zeros).
         The C call takes one row stride for all streams: tensors that do not share one are packed side by side first."""
+        a = self._mlpg_args("parameter_generation", streams, var_per_frame, edge, input_type, unvoiced_value)
+        _check(load_library().WorldMi355ParameterGeneration(
+            self.handle, a.n, a.means, a.ld_mean, a.vars, a.ld_var, a.dims, a.nwin, a.wptrs, a.sptrs, a.msds,
+            C.byref(a.opt), a.out_ptrs, C.c_void_p(a.status.data_ptr())), "ParameterGeneration")
+        return a.outs, a.status
+
+    def _mlpg_args(self, who, streams, var_per_frame, edge, input_type, unvoiced_value):
+        """What parameter_generation and parameter_generation_gv hand to their C calls: the checked streams on one row
+        stride, the window tables, the option, and fresh outputs and status."""
         import torch
+        import types
         n = len(streams)
         tf = self.total_frames
         for mean, var, wins, msd in streams:
             if not (mean.is_cuda and mean.dtype == torch.float32 and mean.dim() == 2 and mean.shape[0] == tf
                     and len(wins) >= 1 and mean.shape[1] % len(wins) == 0):
-                raise ValueError("parameter_generation: mean must be float32 cuda [total_frames][n_windows * dim]")
+                raise ValueError(f"{who}: mean must be float32 cuda [total_frames][n_windows * dim]")
             want = (tf, mean.shape[1]) if var_per_frame else (mean.shape[1],)
             if not (var.is_cuda and var.dtype == torch.float32 and tuple(var.shape) == want):
-                raise ValueError(f"parameter_generation: var must be float32 cuda {want}, got {tuple(var.shape)}")
+                raise ValueError(f"{who}: var must be float32 cuda {want}, got {tuple(var.shape)}")
             if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and tuple(msd.shape) == (tf,)):
-                raise ValueError("parameter_generation: msd must be float32 cuda [total_frames]")
+                raise ValueError(f"{who}: msd must be float32 cuda [total_frames]")
 
         ld_mean, means, msds, keep_m = _shared_row_stride([t for t, _, _, _ in streams], [m for _, _, _, m in streams], tf)
         if var_per_frame:
@@ -1001,11 +1021,55 @@ class WorldBatch:
         o.edge, o.var_per_frame, o.input_type = int(edge), 1 if var_per_frame else 0, int(input_type)
         o.unvoiced_value = float(unvoiced_value)
         ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        _check(load_library().WorldMi355ParameterGeneration(
-            self.handle, n, vpn(*[ptr(t) for t in means]), ld_mean, vpn(*[ptr(t) for t in vars_]), ld_var, dims, nwin,
-            wptrs, sptrs, vpn(*[ptr(t) for t in msds]), C.byref(o), vpn(*[ptr(t) for t in outs]),
-            C.c_void_p(status.data_ptr())), "ParameterGeneration")
-        return outs, status
+        return types.SimpleNamespace(
+            n=n, means=vpn(*[ptr(t) for t in means]), ld_mean=ld_mean, vars=vpn(*[ptr(t) for t in vars_]), ld_var=ld_var,
+            dims=dims, nwin=nwin, wptrs=wptrs, sptrs=sptrs, msds=vpn(*[ptr(t) for t in msds]), opt=o,
+            out_ptrs=vpn(*[ptr(t) for t in outs]), outs=outs, status=status, keep=keep)
+
+    def parameter_generation_gv(self, streams, gv_mean, gv_var, gv_mask=None, want_info=False, var_per_frame=False,
+                                edge=0, input_type=0, unvoiced_value=-1e10, max_iter=None, epsilon=None, step_init=None,
+                                step_inc=None, step_dec=None, hmm_weight=None, gv_weight=None, scale=None):
+        """Parameter generation considering global variance (HMGenS with USEHMMGV = 1, OPTKIND = NEWTON; include/
+        world_mi355.h states the definition): parameter_generation's trajectory, then up to max_iter trials of a
+        diagonal Newton step on  hmm_weight w (-1/2 c'Rc + c'r) - 1/2 gv_weight (v - gv_mean)^2 / gv_var  per column, v
+        the variance of the column over the utterance's GV frames.  streams, var_per_frame, edge, input_type and
+        unvoiced_value as parameter_generation.  gv_mean, gv_var: per stream float32 cuda [dim] (gv.mean and gv.var over
+        the stream's statics).  gv_mask: None, or uint8 cuda [total_frames]: 0 takes a frame out of the GV set (silence);
+        an unvoiced frame of a stream with msd is never in it.  Options left None keep the recipe's defaults
+        (WorldMi355DefaultGvOption: 50 trials, epsilon 1e-4, steps 1 / 1.2 / 0.5, weights 1, scale 1).
+        Returns (outs, status) as parameter_generation -- status further 1 for a gv_mean or gv_var that is not positive,
+        4 for a column with fewer than two GV frames or no variance, both returned as parameter_generation's -- and with
+        want_info (outs, status, info float64 [n_utt][sum of dims][4]: f at the start, f at the end, trials, accepts)."""
+        import torch
+        a = self._mlpg_args("parameter_generation_gv", streams, var_per_frame, edge, input_type, unvoiced_value)
+        if len(gv_mean) != a.n or len(gv_var) != a.n:
+            raise ValueError("parameter_generation_gv: one gv_mean and one gv_var per stream")
+        gvs = []
+        for name, rows in (("gv_mean", gv_mean), ("gv_var", gv_var)):
+            for s, t in enumerate(rows):
+                if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (int(a.dims[s]),)):
+                    raise ValueError(f"parameter_generation_gv: {name}[{s}] must be float32 cuda [{int(a.dims[s])}]")
+            gvs.append([t.contiguous() for t in rows])
+        if gv_mask is not None and not (gv_mask.is_cuda and gv_mask.dtype == torch.uint8
+                                        and tuple(gv_mask.shape) == (self.total_frames,)):
+            raise ValueError("parameter_generation_gv: gv_mask must be uint8 cuda [total_frames]")
+        mask = None if gv_mask is None else gv_mask.contiguous()
+        g = GvOption()
+        load_library().WorldMi355DefaultGvOption(C.byref(g))
+        for key, val in (("max_iter", max_iter), ("epsilon", epsilon), ("step_init", step_init), ("step_inc", step_inc),
+                         ("step_dec", step_dec), ("hmm_weight", hmm_weight), ("gv_weight", gv_weight)):
+            if val is not None:
+                setattr(g, key, int(val) if key == "max_iter" else float(val))
+        if scale is not None:
+            g.scale = 1 if scale else 0
+        info = torch.zeros(self.n_utt, sum(int(d) for d in a.dims), 4, dtype=torch.float64, device="cuda") if want_info else None
+        vpn = C.c_void_p * a.n
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        _check(load_library().WorldMi355ParameterGenerationGv(
+            self.handle, a.n, a.means, a.ld_mean, a.vars, a.ld_var, a.dims, a.nwin, a.wptrs, a.sptrs, a.msds,
+            C.byref(a.opt), vpn(*[ptr(t) for t in gvs[0]]), vpn(*[ptr(t) for t in gvs[1]]), ptr(mask), C.byref(g),
+            a.out_ptrs, ptr(info), C.c_void_p(a.status.data_ptr())), "ParameterGenerationGv")
+        return (a.outs, a.status, info) if want_info else (a.outs, a.status)
 
     def trajectory_cost(self, streams, var, gv_var, msd_weight=1.0, gv_weight=1.0e-6, want_c=True, want_grad_pred=True,
                         want_grad_var=True):

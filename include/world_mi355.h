@@ -336,6 +336,58 @@ int WorldMi355ParameterGeneration(WorldMi355Batch* b, int n_streams, const float
                                   const double* const* const* windows, const int* const* window_sizes,
                                   const float* const* msd, const WorldMi355MlpgOption* opt, float* const* out,
                                   int* status);
+/* ---- Parameter generation considering global variance (GV): what HMGenS does with USEHMMGV = 1 and OPTKIND = NEWTON
+ * (scripts/Training.pl:1892-1903), as a stage in ParameterGeneration's place; gen_wave then skips the postfilter
+ * (:749-757).  Parity with HTS is unpinned: the yardstick is this definition (tests/gv_reference.py states it in numpy).
+ * A column is one utterance, one stream and one dimension, with T frames and n windows; R = W' P W and r = W' P mu are
+ * ParameterGeneration's, edge, var_per_frame and input_type included.  A frame is in the GV set G when it is voiced (a
+ * stream with msd: value >= 0.5) and gv_mask, if given, is non-zero there; N = |G|.  Everything below is in double.
+ *   start      c = ParameterGeneration's float32 output of the column, before its voicing overwrite
+ *   moments    m = sum_{t in G} c_t / N,  e_t = c_t - m for t in G, else 0,  v = sum e_t^2 / N   (two passes)
+ *   objective  f(c) = hmm_weight w (-1/2 c'Rc + c'r) - 1/2 gv_weight p_v (v - mu_v)^2,
+ *              w = 1 / (n T), mu_v = gv_mean, p_v = 1 / gv_var
+ *   scaling    with scale != 0, once before the loop: c_t <- m + sqrt(mu_v / v) e_t for t in G
+ *   direction  g_t = hmm_weight w (r - Rc)_t - gv_weight p_v (v - mu_v) (2 / N) e_t
+ *              H_t = -hmm_weight w R_tt - [t in G] gv_weight (2 / N^2) p_v ((N - 1)(v - mu_v) + 2 e_t^2)
+ *              d_t = g_t / max(-H_t, 1e-3 hmm_weight w R_tt)        (the diagonal Newton step hts_engine publishes)
+ *   loop       step = step_init; for trial 1 .. max_iter: c' = c + step d, d the direction at the current c;
+ *              f(c') >= f(c): accept, step *= step_inc, and stop when epsilon > 0 and (f(c') - f(c)) / |f(c')| < epsilon;
+ *              otherwise keep c and step *= step_dec
+ *   output     float32(c), then unvoiced_value in the unvoiced frames as ParameterGeneration.
+ * max_iter 0 with scale 0 is ParameterGeneration bit for bit.  Columns and utterances never exchange data, and the sums
+ * are taken in an order that depends on T alone: an utterance's bits do not depend on the batch around it. */
+typedef struct {
+  int max_iter;           /* trials, accepted or not (MAXGVITER); default 50 */
+  int scale;              /* 1: start from the trajectory scaled to the GV mean; default 1 */
+  double epsilon;         /* relative gain below which an accepted trial ends the loop (GVEPSILON); 0 never; default 1e-4 */
+  double step_init;       /* STEPINIT 1 */
+  double step_inc;        /* STEPINC 1.2 */
+  double step_dec;        /* STEPDEC 0.5 */
+  double hmm_weight;      /* HMMWEIGHT 1 */
+  double gv_weight;       /* GVWEIGHT 1 */
+} WorldMi355GvOption;
+void WorldMi355DefaultGvOption(WorldMi355GvOption* opt);       /* 50, 1, 1e-4, 1, 1.2, 0.5, 1, 1 */
+/* ParameterGeneration's arguments (opt is its option; msd, out and status as there) and
+ * gv_mean[s], gv_var[s]: DEVICE float32 [dims[s]]: the mean and the variance of the per-utterance variance (gv.mean,
+ *   gv.var restricted to the stream's statics).
+ * gv_mask: NULL, or DEVICE uint8 [total_frames]: 0 takes a frame out of G in every stream (silence: NOSILGV).
+ * info: NULL, or DEVICE double [n_utt][sum of dims][4]: f at the start of the loop, f at its end, trials, accepted
+ *   trials; zeros for a column that is returned as ParameterGeneration leaves it.
+ * status: ParameterGeneration's bits 1 and 2 (such a column stays zeros); further 1: a gv_mean or gv_var of the column
+ *   that is not positive and finite; 4: N < 2, or v not positive and finite at the start.  A column with 1 or 4 is
+ *   ParameterGeneration's, with the voicing overwrite; no other column is affected.
+ * WM_ERR_BAD_ARG before any device call: what ParameterGeneration refuses; a NULL gv_mean, gv_var, gv or entry of
+ * them; max_iter < 0 or above 100000; scale not 0 or 1; epsilon negative or non-finite; a step_init, step_inc, step_dec
+ * or hmm_weight that is not positive and finite; a gv_weight negative or non-finite.
+ * Asynchronous on the context's stream; a batch of zero frames returns WM_OK.  Timed as "mlpg_kernel" (the start) and
+ * "mlpg_gv_kernel". */
+int WorldMi355ParameterGenerationGv(WorldMi355Batch* b, int n_streams, const float* const* mean, int64_t ld_mean,
+                                    const float* const* var, int64_t ld_var, const int* dims, const int* n_windows,
+                                    const double* const* const* windows, const int* const* window_sizes,
+                                    const float* const* msd, const WorldMi355MlpgOption* opt,
+                                    const float* const* gv_mean, const float* const* gv_var,
+                                    const unsigned char* gv_mask, const WorldMi355GvOption* gv, float* const* out,
+                                    double* info, int* status);
 /* ---- Trajectory training criterion with gradients: DNNDefine.trajectory_cost (data/scripts/DNNDefine.py:240-399) as
  * DNNTraining.py -w win drives it (scripts/Training.pl:930-940), for a whole batch of utterances.  Rows are in the `ffo`
  * layout (per stream an optional voicing column, then [window 0: dim | window 1: dim | ...]); per column (utterance,
