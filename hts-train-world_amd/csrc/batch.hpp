@@ -177,6 +177,7 @@ struct Context {
   // drop-in API makes a batch per utterance length: rebuilding them per batch was 0.1 - 0.3 ms of every call)
   std::vector<std::unique_ptr<Table>> tables;
   template <class Build> int table(const TableKey& key, const Table*& out, Build build);
+  std::unique_ptr<StageWs> mlsa_noise;   // excite's Gaussian sequence g (mlsa.hip), grown by grow_ws' rule
   // optional per-kernel HIP-event timing (bench.py's roofline leg): see TimedScope
   bool timing = false;
   std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> timed;
@@ -282,7 +283,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -357,6 +358,19 @@ int launch_mel_cepstrum_of_waveform(Batch& b, hipStream_t st, const double* d_x,
 int check_mgc2sp(const Batch& b, const double* d_mc, const WorldMi355Mgc2spOption& opt, const double* d_sp);
 int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355Mgc2spOption& opt, double* d_sp,
                   double* d_phase, int* d_status);
+// mlsa.hip: excite | dfs | mglsadf.  mode bits of check_mlsa: 1 the excitation's arguments, 2 the filter's
+int mlsa_samples(int n_frames, int frame_shift, int* n_samples);
+int mlsa_pade(int order, double* row);
+int mlsa_noise(int64_t n, double* out);
+int check_mlsa(const Batch& b, int mode, const void* pitch, const void* mc, const double* lowpass, int n_low,
+               const double* highpass, int n_high, const WorldMi355MlsaOption* opt, const void* e, const void* y);
+int launch_mlsa_excitation(Batch& b, hipStream_t st, const float* d_pitch, const double* lowpass, int n_low,
+                           const double* highpass, int n_high, const WorldMi355MlsaOption& opt, double* d_e);
+int launch_mlsa_filter(Batch& b, hipStream_t st, const double* d_e, const float* d_mc, const WorldMi355MlsaOption& opt,
+                       double* d_y, int* d_status);
+int launch_mlsa_synthesis(Batch& b, hipStream_t st, const float* d_pitch, const float* d_mc, const double* lowpass,
+                          int n_low, const double* highpass, int n_high, const WorldMi355MlsaOption& opt, double* d_y,
+                          int* d_status);
 int check_mlpg(int n_streams, const float* const* mean, int64_t ld_mean, const float* const* var, int64_t ld_var,
                const int* dims, const int* n_windows, const double* const* const* windows,
                const int* const* window_sizes, const WorldMi355MlpgOption* opt, float* const* out);

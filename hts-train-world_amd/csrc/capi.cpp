@@ -342,6 +342,38 @@ int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const 
   if (const int rc = check_mgc2sp(b->b, mc, *opt, spectrum)) return rc;         // refused before any device call
   return on_batch(b, launch_mgc2sp, mc, *opt, spectrum, phase, status);
 }
+void WorldMi355DefaultMlsaOption(WorldMi355MlsaOption* o) {                     // SPTK's mglsadf defaults, Pade order 4
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->alpha = 0.35;
+  o->order = 25;
+  o->pade_order = 4;
+  o->frame_shift = 100;
+}
+int WorldMi355MlsaSamples(int n_frames, int frame_shift, int* n_samples) {
+  return mlsa_samples(n_frames, frame_shift, n_samples);
+}
+int WorldMi355MlsaPade(int order, double* row) { return mlsa_pade(order, row); }
+int WorldMi355MlsaNoise(int64_t n, double* out) { return mlsa_noise(n, out); }
+int WorldMi355MlsaExcitation(WorldMi355Batch* b, const float* pitch, const double* lowpass, int n_low,
+                             const double* highpass, int n_high, const WorldMi355MlsaOption* opt, double* e) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mlsa(b->b, 1, pitch, nullptr, lowpass, n_low, highpass, n_high, opt, e, nullptr))
+    return rc;                                                                  // refused before any device call
+  return on_batch(b, launch_mlsa_excitation, pitch, lowpass, n_low, highpass, n_high, *opt, e);
+}
+int WorldMi355MlsaFilter(WorldMi355Batch* b, const double* e, const float* mc, const WorldMi355MlsaOption* opt, double* y,
+                         int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mlsa(b->b, 2, nullptr, mc, nullptr, 0, nullptr, 0, opt, e, y)) return rc;
+  return on_batch(b, launch_mlsa_filter, e, mc, *opt, y, status);
+}
+int WorldMi355MlsaSynthesis(WorldMi355Batch* b, const float* pitch, const float* mc, const double* lowpass, int n_low,
+                            const double* highpass, int n_high, const WorldMi355MlsaOption* opt, double* y, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mlsa(b->b, 3, pitch, mc, lowpass, n_low, highpass, n_high, opt, nullptr, y)) return rc;
+  return on_batch(b, launch_mlsa_synthesis, pitch, mc, lowpass, n_low, highpass, n_high, *opt, y, status);
+}
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {

@@ -1582,6 +1582,113 @@ def mgcep_files(jobs, frame_length=1200, frame_shift=240, fft_length=2048, windo
     return stage.frames, flagged
 
 
+# ---- waveforms from mel-cepstra (scripts/Training.pl:2873-2899: excite | dfs | vopr -a | mglsadf | x2x +fs -o) ----------
+def read_taps(text_or_path):
+    """The taps `dfs -b` takes, from the text data/scripts/makefilter.pl prints (numbers separated by blanks) or from a
+    file that holds it."""
+    text = str(text_or_path)
+    if os.path.exists(text):
+        with open(text) as f:
+            text = f.read()
+    try:
+        taps = np.array([float(t) for t in text.split()], dtype=np.float64)
+    except ValueError:
+        raise ValueError("%r: neither a file nor numbers separated by blanks" % (text_or_path,))
+    if not 1 <= len(taps) <= 256 or not np.isfinite(taps).all():
+        raise ValueError("%r: 1 to 256 finite taps, got %d" % (text_or_path, len(taps)))
+    return taps
+
+
+def mlsa_pitch(lf0, fs):
+    """`sopr -magic -1.0E+10 -EXP -INV -m fs -MAGIC 0.0` on float32 lf0: the period in samples, in double and rounded to
+    float32 once; 0 for the magic value."""
+    lf0 = np.asarray(lf0, dtype=np.float32)
+    voiced = lf0 != np.float32(-1.0e10)
+    pitch = np.zeros(lf0.shape, dtype=np.float64)
+    pitch[voiced] = float(fs) * (1.0 / np.exp(lf0[voiced].astype(np.float64)))
+    return pitch.astype(np.float32)
+
+
+def pcm16_of_pipe(y):
+    """`x2x +fs -o`: clipped to [-32768, 32767] and truncated toward zero (this reading of -o is unpinned: SPTK is not in
+    the reference tree)."""
+    return np.trunc(np.clip(np.asarray(y, dtype=np.float64), -32768.0, 32767.0)).astype("<i2")
+
+
+def _put_raw_and_wav(raw_path, wav_path, pcm, fs):
+    pcm.tofile(raw_path)
+    n = len(pcm)
+    head = b"RIFF" + struct.pack("<I", 36 + n * 2) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, fs, fs * 2, 2, 16)
+    _put(wav_path, pcm, head + b"data" + struct.pack("<I", n * 2))
+
+
+def mlsa_synth_check(fs, frame_shift, order, alpha, pade_order, max_batch_frames=2):
+    """What mlsa_synth_files refuses, as a ValueError, before anything is opened."""
+    if fs < 1:
+        raise ValueError("fs %r: a sampling rate in Hz" % (fs,))
+    if frame_shift < 1:
+        raise ValueError("frame_shift %r: at least 1 sample" % (frame_shift,))
+    if not 1 <= order <= 62:
+        raise ValueError("order %r: from 1 to 62" % (order,))
+    if not abs(alpha) < 1.0:
+        raise ValueError("alpha %r: |alpha| < 1" % (alpha,))
+    if not 1 <= pade_order <= 7:
+        raise ValueError("pade_order %r: from 1 to 7" % (pade_order,))
+    if max_batch_frames < 2:
+        raise ValueError("max_batch_frames %r: at least 2" % (max_batch_frames,))
+
+
+def mlsa_synth_files(jobs, lowpass, highpass, fs=48000, frame_shift=240, order=49, alpha=0.55, pade_order=5,
+                     pipe_float32=True, pade=None, ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8,
+                     resume=False):
+    """gen_wave's first branch (scripts/Training.pl:2873-2899, the default USEWORLD=0, GAMMA=0) for a file list:
+    `sopr ... lf0 > pit`, `excite -n -p frame_shift | dfs -b`, `vopr -a`, `mglsadf -P pade_order -m order -p frame_shift
+    -a alpha -c 0 mgc | x2x +fs -o > raw`, in one call per batch (mlsa_synthesis).
+
+    jobs:  [(lf0, mgc, raw_out, wav_out)] -- float32 [T] with -1e10 for unvoiced and float32 [T][order+1] in; int16 and a
+           16-bit wav of (T - 1) * frame_shift samples out.
+    lowpass, highpass: the taps, as read_taps gives them (makefilter.pl's output for the sampling rate).
+    pipe_float32: a value is rounded to float32 at each pipe of the shell line, as SPTK's float pipes do.
+    The int16 conversion is pcm16_of_pipe's.  An utterance of status 1 (a non-finite coefficient, a non-finite or negative
+    pitch) or 2 (a non-finite sample) is reported on stderr and its files are not written.  Rank-sharded by frame count;
+    with resume, utterances whose two outputs have the complete sizes are skipped.  Returns (frames synthesised by this
+    rank, the flagged lf0 inputs)."""
+    mlsa_synth_check(fs, frame_shift, order, alpha, pade_order, max_batch_frames)
+    import torch  # noqa: F401 -- ahead of the first call into the library (analysis_files says why)
+    lowpass, highpass = np.asarray(lowpass, dtype=np.float64), np.asarray(highpass, dtype=np.float64)
+    jobs = list(jobs)
+    width = int(order) + 1
+    frames = [_rows_in(j, 1, 4, "lf0, mgc and the two output paths") for j in jobs]
+    short = [jobs[i][0] for i, n in enumerate(frames) if n < 2]
+    if short:
+        raise ValueError("%s holds fewer than two frames" % short[0])
+    samples = [W.mlsa_samples(n, frame_shift) for n in frames]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][2], 2 * samples[i])
+                                           and _size_is(jobs[i][3], 44 + 2 * samples[i])))
+    flagged = []
+    if not mine:
+        return 0, flagged
+    with _Stage(ctx, io_threads) as stage:
+        for group in stage.groups(mine, frames, max_batch_frames):
+            with stage.batch(f0_lengths=[frames[i] for i in group], y_lengths=[samples[i] for i in group]) as b:
+                want = [(frames[i], jobs[i][0]) for i in group]
+                lf0 = list(stage.pool.map(lambda i: _f32(jobs[i][0]), group))
+                pitch = _upload(np.concatenate([mlsa_pitch(a, fs) for a in lf0]))
+                mc = stage.load([jobs[i][1] for i in group], width, want)
+                y, status = b.mlsa_synthesis(pitch, mc, lowpass, highpass, order, alpha, pade_order, frame_shift,
+                                             pipe_float32, pade)
+                host = y.cpu().numpy()
+                st = status.cpu().numpy()
+                yo = b.out_offsets
+                for k, i in enumerate(group):
+                    if st[k]:
+                        print("warning: %s: status %d, not written" % (jobs[i][0], int(st[k])), file=sys.stderr)
+                        flagged.append(jobs[i][0])
+                        continue
+                    stage.submit(_put_raw_and_wav, jobs[i][2], jobs[i][3], pcm16_of_pipe(host[yo[k]:yo[k + 1]]), int(fs))
+    return stage.frames, flagged
+
+
 # ---- modulation-spectrum postfilter (scripts/Training.pl:2950-3038 postfiltering_mspf, :3133-3221 make_mspf) ----------
 def mspf_label_rows(lines, frame_shift_s, n_rows, silences=()):
     """Rows that make_mspf's silence removal keeps: label lines "start end name" in 100 ns units; a segment's frames are
@@ -1944,6 +2051,23 @@ def main(argv=None):
                    "DOUBLE), not rounded to float32 as the pipe between window and mgcep does")
     p.add_argument("--resume", action="store_true", help="skip utterances whose mgc file is already complete")
     p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
+    p = sub.add_parser("mlsa-synth", help="excite | dfs | mglsadf | x2x +fs -o: raw and wav files from lists of lf0 and mgc files")
+    p.add_argument("--scp", required=True, help="job list: the lf0 file, the mgc file, then the raw and the wav file to write")
+    p.add_argument("--lowpass", required=True, help="the taps of `dfs -b` on the pulse branch: what makefilter.pl prints "
+                   "at flag 0, or a file that holds it")
+    p.add_argument("--highpass", required=True, help="the same for the noise branch (makefilter.pl's flag 1)")
+    p.add_argument("--fs", type=int, default=48000, help="SAMPFREQ: turns lf0 into a period in samples")
+    p.add_argument("--frame-shift", type=int, default=240, help="FRAMESHIFT")
+    p.add_argument("--alpha", type=float, default=0.55, help="FREQWARP")
+    p.add_argument("--order", type=int, default=49, help="MGCORDER: a row holds order + 1 float32")
+    p.add_argument("--pade-order", type=int, default=5, help="mglsadf -P, 1 to 7 (gen_wave passes 7: the rows of orders 6 "
+                   "and 7 are the plain Pade approximant here, SPTK's own were not at hand)")
+    p.add_argument("--no-pipe-float32", action="store_true", help="keep every value in double (SPTK built with DOUBLE), not "
+                   "rounded to float32 at each pipe of the shell line")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose raw and wav files are already complete")
+    p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
+    p.description = ("The int16 samples are the filter's output clipped to [-32768, 32767] and truncated toward zero: a "
+                     "reading of `x2x +fs -o` that is unpinned, like the parity of the whole stage with SPTK.")
     for cmd in ("mspf-stats", "mspf"):
         p = sub.add_parser(cmd, help="make_mspf: statistics of the modulation spectra of a list of files" if cmd == "mspf-stats"
                            else "postfiltering_mspf: the modulation-spectrum postfilter on a list of mgc files")
@@ -2079,6 +2203,17 @@ def main(argv=None):
         n, flagged = mgcep_files(_read_scp(a.scp, 2), a.frame_length, a.frame_shift, a.fft_length, a.window, a.normalize,
                                  a.alpha, a.order, a.eps, pipe_float32=not a.no_pipe_float32,
                                  max_batch_frames=a.max_batch_frames, resume=a.resume)
+        print("complete. %d frames, %d utterances flagged" % (n, len(flagged)))
+        return 0
+    if a.cmd == "mlsa-synth":
+        try:
+            mlsa_synth_check(a.fs, a.frame_shift, a.order, a.alpha, a.pade_order, a.max_batch_frames)
+            taps = read_taps(a.lowpass), read_taps(a.highpass)
+        except ValueError as err:
+            ap.error(str(err))
+        n, flagged = mlsa_synth_files(_read_scp(a.scp, 4), taps[0], taps[1], a.fs, a.frame_shift, a.order, a.alpha,
+                                      a.pade_order, pipe_float32=not a.no_pipe_float32,
+                                      max_batch_frames=a.max_batch_frames, resume=a.resume)
         print("complete. %d frames, %d utterances flagged" % (n, len(flagged)))
         return 0
     if a.cmd == "postfilter":

@@ -79,6 +79,12 @@ class Mgc2spOption(C.Structure):
     _fields_ = [("alpha", C.c_double), ("gamma", C.c_double), ("order", C.c_int), ("out_format", C.c_int)]
 
 
+class MlsaOption(C.Structure):
+    """include/world_mi355.h: WorldMi355MlsaOption (SPTK's excite | dfs | mglsadf, gen_wave's first branch)."""
+    _fields_ = [("alpha", C.c_double), ("order", C.c_int), ("pade_order", C.c_int), ("frame_shift", C.c_int),
+                ("pipe_float32", C.c_int), ("use_pade", C.c_int), ("pade", C.c_double * 8)]
+
+
 class MlpgOption(C.Structure):
     """include/world_mi355.h: WorldMi355MlpgOption (parameter generation, SPTK's mlpg)."""
     _fields_ = [("edge", C.c_int), ("var_per_frame", C.c_int), ("input_type", C.c_int),
@@ -216,6 +222,14 @@ def load_library():
     L.WorldMi355SptkWindow.argtypes = [C.c_int, C.c_int, C.c_int, _dp]
     L.WorldMi355MelCepstrumOfFrames.argtypes = [vp, vp, C.POINTER(McepOption), vp, vp]
     L.WorldMi355MelCepstrumOfWaveform.argtypes = [vp, vp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(McepOption), vp, vp]
+    L.WorldMi355DefaultMlsaOption.restype = None
+    L.WorldMi355DefaultMlsaOption.argtypes = [C.POINTER(MlsaOption)]
+    L.WorldMi355MlsaSamples.argtypes = [C.c_int, C.c_int, _ip]
+    L.WorldMi355MlsaPade.argtypes = [C.c_int, _dp]
+    L.WorldMi355MlsaNoise.argtypes = [C.c_int64, _dp]
+    L.WorldMi355MlsaExcitation.argtypes = [vp, vp, _dp, C.c_int, _dp, C.c_int, C.POINTER(MlsaOption), vp]
+    L.WorldMi355MlsaFilter.argtypes = [vp, vp, vp, C.POINTER(MlsaOption), vp, vp]
+    L.WorldMi355MlsaSynthesis.argtypes = [vp, vp, vp, _dp, C.c_int, _dp, C.c_int, C.POINTER(MlsaOption), vp, vp]
     L.WorldMi355DefaultMgc2spOption.restype = None
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
@@ -431,6 +445,30 @@ def sptk_window(type, normalize, length):
     _check(load_library().WorldMi355SptkWindow(int(type), int(normalize), int(length), w.ctypes.data_as(_dp)),
            "SptkWindow")
     return w[:int(length)]
+
+
+def mlsa_samples(n_frames, frame_shift):
+    """The samples `excite -p frame_shift | mglsadf -p frame_shift` make of n_frames frames (WorldMi355MlsaSamples:
+    (n_frames - 1) * frame_shift; n_frames < 2 or frame_shift < 1 is refused).  Host only."""
+    n = C.c_int(0)
+    _check(load_library().WorldMi355MlsaSamples(int(n_frames), int(frame_shift), C.byref(n)), "MlsaSamples")
+    return int(n.value)
+
+
+def mlsa_pade(order):
+    """The Pade row pp[0 .. order] of the MLSA filter as float64 (WorldMi355MlsaPade): SPTK's modified tables at orders 4
+    and 5 as recalled, the plain approximant of exp at 1, 2, 3, 6 and 7.  Host only."""
+    row = np.zeros(8, dtype=np.float64)
+    _check(load_library().WorldMi355MlsaPade(int(order), row.ctypes.data_as(_dp)), "MlsaPade")
+    return row[:int(order) + 1]
+
+
+def mlsa_noise(n):
+    """The first n values of excite's Gaussian sequence g (nrandom at seed 1) as float64 (WorldMi355MlsaNoise).  Host
+    only."""
+    out = np.zeros(max(int(n), 1), dtype=np.float64)
+    _check(load_library().WorldMi355MlsaNoise(int(n), out.ctypes.data_as(_dp)), "MlsaNoise")
+    return out[:max(int(n), 0)]
 
 
 class WorldBatch:
@@ -718,6 +756,88 @@ class WorldBatch:
             self.handle, self._p(x), w.ctypes.data_as(_dp), int(frame_length), int(frame_shift), 1 if pipe_float32 else 0,
             C.byref(o), self._p(mc), C.c_void_p(status.data_ptr())), "MelCepstrumOfWaveform")
         return mc, status
+
+    @staticmethod
+    def _mlsa_option(order=25, alpha=0.35, pade_order=4, frame_shift=100, pipe_float32=False, pade=None):
+        o = MlsaOption()
+        load_library().WorldMi355DefaultMlsaOption(C.byref(o))
+        o.order, o.alpha, o.pade_order, o.frame_shift = int(order), float(alpha), int(pade_order), int(frame_shift)
+        o.pipe_float32 = 1 if pipe_float32 else 0
+        if pade is not None:
+            row = [float(v) for v in pade]
+            if len(row) != int(pade_order) + 1 or len(row) > 8:
+                raise ValueError(f"mlsa: pade must hold pade_order + 1 = {int(pade_order) + 1} values, got {len(row)}")
+            o.use_pade = 1
+            for k, v in enumerate(row):
+                o.pade[k] = v
+        return o
+
+    @staticmethod
+    def _mlsa_taps(where, name, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float64)
+        if t.ndim != 1:
+            raise ValueError(f"{where}: {name} must be a list of taps, got shape {t.shape}")
+        return t
+
+    def _mlsa_rows(self, where, name, t, shape, dtype):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{where}: {name} must be a contiguous {dtype} cuda tensor {list(shape)}, "
+                             f"got {t.dtype} {tuple(t.shape)}")
+        return C.c_void_p(t.data_ptr())
+
+    def mlsa_excitation(self, pitch, lowpass, highpass, frame_shift=100, pipe_float32=False):
+        """`excite -n -p frame_shift pit | dfs -b lowpass` plus `excite` of an all-zero pitch `| dfs -b highpass`
+        (scripts/Training.pl:2873-2899): pitch float32 cuda [total_frames], the period in samples with 0 for unvoiced;
+        lowpass, highpass the caller's taps (1 to 256 each, host).  The batch's y_lengths must be mlsa_samples of its
+        f0_lengths.  Returns e float64 [total output samples]; an utterance with a non-finite or negative pitch is zeros."""
+        import torch
+        where = "mlsa_excitation"
+        o = self._mlsa_option(frame_shift=frame_shift, pipe_float32=pipe_float32)
+        lp, hp = self._mlsa_taps(where, "lowpass", lowpass), self._mlsa_taps(where, "highpass", highpass)
+        pp = self._mlsa_rows(where, "pitch", pitch, (self.total_frames,), torch.float32)
+        e = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
+        _check(load_library().WorldMi355MlsaExcitation(self.handle, pp, lp.ctypes.data_as(_dp), len(lp),
+                                                       hp.ctypes.data_as(_dp), len(hp), C.byref(o), self._p(e)),
+               "MlsaExcitation")
+        return e
+
+    def mlsa_filter(self, e, mc, alpha=0.35, pade_order=4, frame_shift=100, pipe_float32=False, pade=None):
+        """`mglsadf -m order -a alpha -P pade_order -p frame_shift -c 0` at interpolation period 1: e float64 cuda [total
+        output samples], mc float32 cuda [total_frames][order+1]; pade a caller's row of pade_order + 1 values in place of
+        mlsa_pade's.  Returns (y float64 [total output samples], status int32 [n_utt]: 0 fine, 1 a non-finite coefficient
+        -- the utterance is zeros --, 2 a non-finite output sample)."""
+        import torch
+        where = "mlsa_filter"
+        if mc.dim() != 2:
+            raise ValueError(f"{where}: mc must be [total_frames][order+1], got {tuple(mc.shape)}")
+        o = self._mlsa_option(int(mc.shape[1]) - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
+        mp = self._mlsa_rows(where, "mc", mc, (self.total_frames, int(mc.shape[1])), torch.float32)
+        ep = self._mlsa_rows(where, "e", e, (self.total_out,), torch.float64)
+        y = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MlsaFilter(self.handle, ep, mp, C.byref(o), self._p(y),
+                                                   C.c_void_p(status.data_ptr())), "MlsaFilter")
+        return y, status
+
+    def mlsa_synthesis(self, pitch, mc, lowpass, highpass, order=None, alpha=0.35, pade_order=4, frame_shift=100,
+                       pipe_float32=False, pade=None):
+        """mlsa_excitation and mlsa_filter in one call, bit for bit, without the excitation in device memory beyond the
+        block being filtered.  order, if given, must be mc's.  Returns (y, status) as mlsa_filter does; status 1 also for
+        a non-finite or negative pitch."""
+        import torch
+        where = "mlsa_synthesis"
+        if mc.dim() != 2 or (order is not None and int(order) != int(mc.shape[1]) - 1):
+            raise ValueError(f"{where}: mc must be [total_frames][order+1], got {tuple(mc.shape)} at order {order}")
+        o = self._mlsa_option(int(mc.shape[1]) - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
+        lp, hp = self._mlsa_taps(where, "lowpass", lowpass), self._mlsa_taps(where, "highpass", highpass)
+        pp = self._mlsa_rows(where, "pitch", pitch, (self.total_frames,), torch.float32)
+        mp = self._mlsa_rows(where, "mc", mc, (self.total_frames, int(mc.shape[1])), torch.float32)
+        y = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355MlsaSynthesis(self.handle, pp, mp, lp.ctypes.data_as(_dp), len(lp),
+                                                      hp.ctypes.data_as(_dp), len(hp), C.byref(o), self._p(y),
+                                                      C.c_void_p(status.data_ptr())), "MlsaSynthesis")
+        return y, status
 
     def spectrum_from_mel_cepstrum(self, mc, alpha=0.35, gamma=0.0, out_format=0, phase=False):
         """SPTK's mgc2sp per frame (test/sptkfunctions.cpp:186-219 with flng = fft_size): mc is float64 cuda

@@ -288,6 +288,74 @@ void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* opt);
 int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const WorldMi355Mgc2spOption* opt,
                                     double* spectrum, double* phase, int* status);
 
+/* ---- Waveforms from mel-cepstra: the first branch of gen_wave (scripts/Training.pl:2873-2899), the synthesis half of the
+ * recipe's default configuration (USEWORLD = 0, GAMMA = 0),
+ *   sopr -m 0 pit | excite -n -p P | dfs -b highpass > unv
+ *   excite -n -p P pit | dfs -b lowpass | vopr -a unv | mglsadf -P pd -m order -p P -a alpha -c 0 mgc | x2x +fs -o
+ * SPTK is not in the reference tree.  PARITY WITH SPTK IS UNPINNED: the yardstick is the definition below, which
+ * tests/mlsa_reference.py states in float64.  Everything is in double unless a float32 pipe is named; T is the number of
+ * frames of an utterance, P = frame_shift; an utterance of T >= 2 frames gives (T - 1) P samples.
+ *   noise      nrandom at excite's seed: next = 1 (unsigned); rnd(): next = next * 1103515245 + 12345,
+ *              r = (next / 65536) % 32768, value r / 32767.0.  Pairs: repeat r1 = 2 rnd() - 1, r2 = 2 rnd() - 1,
+ *              s = r1 r1 + r2 r2 while s > 1 or s == 0; s = sqrt(-2 log(s) / s); the pair is r1 s, r2 s.  The sequence
+ *              g[0], g[1], ... is the same for every utterance and for both excite processes of the line.
+ *   excite     pitch[T]: the period in samples, exactly 0 = unvoiced.  p1 = pitch[0], cnt = p1.  For f = 1 .. T-1, p2 =
+ *              pitch[f]: if p1 != 0 and p2 != 0, inc = (p2 - p1) / P, else inc = 0, cnt = p2, p1 = 0.  Then P times: p1 == 0
+ *              emits the next unused g; otherwise cnt += 1, and cnt >= p1 emits sqrt(p1) with cnt -= p1, anything else 0;
+ *              then p1 += inc.  After the frame p1 = p2.
+ *   dfs        y[n] = sum_k b[k] x[n - k], x zero before sample 0, taps taken in the order k = 0, 1, ...
+ *   e          e[n] = dfs(lowpass, excite(pitch))[n] + dfs(highpass, g)[n].  Both tap sets are the CALLER's (the recipe's
+ *              makefilter.pl prints the ones it uses); the library holds no filter table.
+ *   mglsadf    per frame b = mc2b(mc): b[m] = mc[m], b[i] = mc[i] - alpha b[i+1].  Between frames f and f + 1,
+ *              inc[k] = (b_next[k] - b[k]) / P and b[k] += inc[k] after every sample, as a running sum; after P samples
+ *              b = b_next exactly.  Per sample x = e[n] exp(b[0]), x = mlsadf1(x), y[n] = mlsadf2(x), with
+ *              aa = 1 - alpha^2, the Pade row pp[0 .. pd] and all state zero at the start:
+ *                mlsadf1  out = 0; for i = pd .. 1: d1[i] = aa pt1[i-1] + alpha d1[i], pt1[i] = d1[i] b[1],
+ *                         v = pt1[i] pp[i], x += (i odd) ? v : -v, out += v; then pt1[0] = x, out += x
+ *                mlsadf2  the same with pt2[i] = mlsafir(pt2[i-1], D[i-1]) in place of the first two assignments
+ *                mlsafir  d[0] = x, d[1] = aa d[0] + alpha d[1]; for k = 2 .. m: d[k] += alpha (d[k+1] - d[k-1]),
+ *                         y += d[k] b[k]; for k = m+1 .. 2: d[k] = d[k-1]
+ *   Pade rows  pp[0] = 1.  Order 4: 0.4999273, 0.1067005, 0.01170221, 0.0005656279 and order 5: 0.4999391, 0.1107098,
+ *              0.01369984, 0.0009564853, 0.00003041721, SPTK's modified tables AS RECALLED.  Orders 1, 2, 3, 6 and 7 are
+ *              the plain Pade approximant of exp, pp[k] = L! (2L-k)! / ((2L)! k! (L-k)!): SPTK's own tables for 6 and 7
+ *              were not at hand.  Whoever has them passes them in pade[] with use_pade = 1 and gets SPTK's filter.
+ *   float32    with pipe_float32 a value is rounded to float32 once at each pipe of the line: excite's output (both
+ *              times), each dfs output, the vopr sum and mglsadf's output.
+ * Not offered: gamma != 0, an interpolation period other than 1, -k, -t, -v, excite without -n. */
+typedef struct {
+  double alpha;           /* 0.35 */
+  int order;              /* m; 25 */
+  int pade_order;         /* pd, 1 .. 7; 4 */
+  int frame_shift;        /* P, samples per frame; 100 */
+  int pipe_float32;       /* 0 */
+  int use_pade;           /* 0: the row of pade_order as above; 1: pade[0 .. pade_order] */
+  double pade[8];
+} WorldMi355MlsaOption;
+void WorldMi355DefaultMlsaOption(WorldMi355MlsaOption* opt);
+/* Host only, no device needed.  MlsaSamples: (n_frames - 1) * frame_shift, WM_ERR_BAD_ARG for n_frames < 2, frame_shift < 1
+ * or a product beyond int.  MlsaPade: row[0 .. order] of the table above, WM_ERR_BAD_ARG outside 1 .. 7.  MlsaNoise: the
+ * first n values of g, WM_ERR_BAD_ARG for n < 0. */
+int WorldMi355MlsaSamples(int n_frames, int frame_shift, int* n_samples);
+int WorldMi355MlsaPade(int order, double* row);
+int WorldMi355MlsaNoise(int64_t n, double* out);
+/* The batch's f0_lengths are the T and its y_lengths must be WorldMi355MlsaSamples of them.
+ * pitch: DEVICE float[total_frames]; lowpass, highpass: HOST double[n_low], double[n_high], uploaded by the library;
+ * e: DEVICE double[total output samples] (WorldMi355BatchOutputOffsets); mc: DEVICE float[total_frames][order+1];
+ * y: DEVICE double[total output samples]; status: DEVICE int[n_utt] or NULL: 0 fine; 1 a non-finite or negative pitch or a
+ * non-finite coefficient: the utterance's samples are zeros (MlsaExcitation, which has no status, writes zeros too);
+ * 2 a non-finite output sample: the samples are left as computed.  Utterances never exchange data.
+ * MlsaSynthesis is MlsaExcitation and MlsaFilter in one call, bit for bit, without e in device memory beyond the block of
+ * samples being filtered.
+ * WM_ERR_BAD_ARG before any device call: T < 2, order outside 1 .. 62, pade_order outside 1 .. 7, |alpha| >= 1,
+ * frame_shift < 1, n_low or n_high outside 1 .. 256, y_lengths that are not MlsaSamples of f0_lengths, a NULL pointer
+ * (status excepted), a non-finite tap or pade entry.  Asynchronous on the context's stream.  Timed as "mlsa_kernel". */
+int WorldMi355MlsaExcitation(WorldMi355Batch* b, const float* pitch, const double* lowpass, int n_low,
+                             const double* highpass, int n_high, const WorldMi355MlsaOption* opt, double* e);
+int WorldMi355MlsaFilter(WorldMi355Batch* b, const double* e, const float* mc, const WorldMi355MlsaOption* opt, double* y,
+                         int* status);
+int WorldMi355MlsaSynthesis(WorldMi355Batch* b, const float* pitch, const float* mc, const double* lowpass, int n_low,
+                            const double* highpass, int n_high, const WorldMi355MlsaOption* opt, double* y, int* status);
+
 /* ---- `cmp` composition (data/scripts/window.pl:45-146, addhtkheader.pl:45-82), SURVEY.md section 8(f) rank 3 ----
  * Applies each stream's dynamic-feature windows and lays the results side by side per frame:
  *   out[frame] = [stream 0: window 0 (dim) | window 1 | ...][stream 1: ...]...      (float32)
