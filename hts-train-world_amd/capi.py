@@ -191,3 +191,57 @@ def decode_aperiodicity(coded, fs, fft_size):
     out = np.zeros((cd.shape[0], fft_size // 2 + 1))
     L.DecodeAperiodicity(_rows(cd), cd.shape[0], int(fs), cd.shape[1], int(fft_size), _rows(out))
     return out
+
+
+# ---- objective evaluation, one pair of feature files per call (no WORLD counterpart) -----------------------------------
+def dtw_workspace_bytes(a_length, b_length):
+    """WorldMi355DtwWorkspaceBytes for one pair: what dtw_align keeps on the device.  Host only."""
+    from . import world as W
+    return W.dtw_workspace_bytes([int(a_length)], [int(b_length)])
+
+
+def _pair_batch(a, b):
+    import torch
+    from . import world as W
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or len(a) < 1:
+        raise ValueError("rows of float32 are expected, at least one of a: got %s and %s" % (a.shape, b.shape))
+    ctx = W.Context()
+    batch = W.WorldBatch(ctx, W.default_params(48000, 5.0), f0_lengths=[len(a)])
+    rows = lambda x: torch.from_numpy(x if len(x) else np.zeros((1, x.shape[1]), np.float32)).cuda()[:len(x)].contiguous()
+    return ctx, batch, rows(a), rows(b)
+
+
+def dtw_align(a, b, first=0, count=None):
+    """WorldMi355DtwAlign for one pair of host arrays a [T_a][ld_a], b [T_b][ld_b] over the columns [first, first + count)
+    -> (path int32 [path_len][2], cost, status)."""
+    ctx, batch, da, db = _pair_batch(a, b)
+    try:
+        path, n, cost, status = batch.dtw_align(da, db, [len(db)], first, count)
+        n = int(n.cpu()[0])
+        return path.cpu().numpy()[:n], float(cost.cpu()[0]), int(status.cpu()[0])
+    finally:
+        batch.close()
+        ctx.close()
+
+
+def feature_distortion(a, b, first, count, kind, path=None, b_mask=None, voiced_above=-1e9):
+    """WorldMi355FeatureDistortion for one pair of host arrays and one column group -> the four sums of the group's kind
+    (include/world_mi355.h).  path: dtw_align's, or None for truncation; b_mask: None or uint8 [T_b]."""
+    import torch
+    ctx, batch, da, db = _pair_batch(a, b)
+    try:
+        dp = dn = dm = None
+        if path is not None:
+            cap = len(da) + len(db) - 1
+            full = np.full((cap, 2), -1, dtype=np.int32)
+            full[:len(path)] = path
+            dp, dn = torch.from_numpy(full).cuda(), torch.tensor([len(path)], dtype=torch.int32).cuda()
+        if b_mask is not None:
+            dm = torch.from_numpy(np.ascontiguousarray(b_mask, dtype=np.uint8)).cuda()
+        out = batch.feature_distortion([(da, db, first, count, kind)], [len(db)], dp, dn, dm, voiced_above)
+        return out.cpu().numpy()[0, 0]
+    finally:
+        batch.close()
+        ctx.close()

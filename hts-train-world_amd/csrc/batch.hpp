@@ -283,7 +283,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa, dtw;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -371,6 +371,18 @@ int launch_mlsa_filter(Batch& b, hipStream_t st, const double* d_e, const float*
 int launch_mlsa_synthesis(Batch& b, hipStream_t st, const float* d_pitch, const float* d_mc, const double* lowpass,
                           int n_low, const double* highpass, int n_high, const WorldMi355MlsaOption& opt, double* d_y,
                           int* d_status);
+// dtw.hip: alignment of two feature sequences per utterance and the distortion measures along a path
+int dtw_workspace_bytes(int n_utt, const int* a_lengths, const int* b_lengths, int64_t* bytes);
+int check_dtw(const Batch& b, const float* a, int64_t ld_a, const float* bs, int64_t ld_b, const int64_t* b_off, int first,
+              int count, const int* path, const int* path_len, const double* cost);
+int launch_dtw_align(Batch& b, hipStream_t st, const float* d_a, int64_t ld_a, const float* d_b, int64_t ld_b,
+                     const int64_t* b_off, int first, int count, int* d_path, int* d_path_len, double* d_cost,
+                     int* d_status);
+int check_distortion(const Batch& b, const int* path, const int* path_len, const int64_t* b_off, int n_groups,
+                     const WorldMi355DistortionGroup* groups, const WorldMi355DistortionOption* opt, const double* out);
+int launch_feature_distortion(Batch& b, hipStream_t st, const int* d_path, const int* d_path_len, const int64_t* b_off,
+                              const unsigned char* d_b_mask, int n_groups, const WorldMi355DistortionGroup* groups,
+                              const WorldMi355DistortionOption& opt, double* d_out);
 int check_mlpg(int n_streams, const float* const* mean, int64_t ld_mean, const float* const* var, int64_t ld_var,
                const int* dims, const int* n_windows, const double* const* const* windows,
                const int* const* window_sizes, const WorldMi355MlpgOption* opt, float* const* out);

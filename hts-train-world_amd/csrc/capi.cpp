@@ -374,6 +374,27 @@ int WorldMi355MlsaSynthesis(WorldMi355Batch* b, const float* pitch, const float*
   if (const int rc = check_mlsa(b->b, 3, pitch, mc, lowpass, n_low, highpass, n_high, opt, nullptr, y)) return rc;
   return on_batch(b, launch_mlsa_synthesis, pitch, mc, lowpass, n_low, highpass, n_high, *opt, y, status);
 }
+void WorldMi355DefaultDistortionOption(WorldMi355DistortionOption* o) {
+  if (!o) return;
+  o->voiced_above = -1.0e9;                                                     // the recipe's unvoiced value is -1e10
+}
+int WorldMi355DtwWorkspaceBytes(int n_utt, const int* a_lengths, const int* b_lengths, int64_t* bytes) {
+  return dtw_workspace_bytes(n_utt, a_lengths, b_lengths, bytes);
+}
+int WorldMi355DtwAlign(WorldMi355Batch* b, const float* a, int64_t ld_a, const float* bs, int64_t ld_b, const int64_t* b_off,
+                       int first, int count, int* path, int* path_len, double* cost, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_dtw(b->b, a, ld_a, bs, ld_b, b_off, first, count, path, path_len, cost))
+    return rc;                                                                  // refused before any device call
+  return on_batch(b, launch_dtw_align, a, ld_a, bs, ld_b, b_off, first, count, path, path_len, cost, status);
+}
+int WorldMi355FeatureDistortion(WorldMi355Batch* b, const int* path, const int* path_len, const int64_t* b_off,
+                                const unsigned char* b_mask, int n_groups, const WorldMi355DistortionGroup* groups,
+                                const WorldMi355DistortionOption* opt, double* out) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_distortion(b->b, path, path_len, b_off, n_groups, groups, opt, out)) return rc;
+  return on_batch(b, launch_feature_distortion, path, path_len, b_off, b_mask, n_groups, groups, *opt, out);
+}
 int WorldMi355ComposeCmp(WorldMi355Batch* b, int n_streams, const float* const* streams, const int* dims,
                          const int* n_windows, const double* const* const* windows,
                          const int* const* window_sizes, float* out) {

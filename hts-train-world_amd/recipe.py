@@ -1875,6 +1875,153 @@ def vibrato_files(jobs, frame_period, fs=48000, ctx=None, max_batch_frames=MAX_B
     return stage.frames
 
 
+# ---- objective evaluation: generated against natural feature files (no counterpart in the recipe's scripts) -----------
+EVAL_WORKSPACE_BYTES = 4 << 30                # a batch's alignment workspace stays below this where it holds several pairs
+
+
+def parse_eval_stream(text):
+    """`NAME:DIM` of evaluate's command line -> (name, dim), e.g. mgc:50."""
+    name, _, dim = text.partition(":")
+    if not name or not dim.isdigit() or int(dim) < 1:
+        raise ValueError("a stream is NAME:DIM with DIM >= 1: " + text)
+    return name, int(dim)
+
+
+def evaluate_groups(streams, with_c0=False):
+    """What evaluate scores of each stream, [(first column, count, kind)]: mgc is cepstral (kind 0) over the columns
+    1 .. DIM-1, with_c0 adds column 0; lf0 is log f0 (kind 1, one column); any other stream is kind 0 over all columns."""
+    groups = []
+    for name, dim in streams:
+        if name == "lf0":
+            if dim != 1:
+                raise ValueError("lf0 is one column, not %d" % dim)
+            groups.append((0, 1, 1))
+        elif name == "mgc" and not with_c0:
+            if dim < 2:
+                raise ValueError("mgc without c0 needs more than one column")
+            groups.append((1, dim - 1, 0))
+        else:
+            groups.append((0, dim, 0))
+    if any(c > 64 for _, c, _ in groups):
+        raise ValueError("a stream is scored over at most 64 columns")
+    return groups
+
+
+def evaluate_files(jobs, streams, align="dtw", with_c0=False, silences=(), frame_shift_s=0.005, voiced_above=-1.0e9,
+                   ctx=None, max_batch_frames=MAX_BATCH_FRAMES, max_workspace_bytes=EVAL_WORKSPACE_BYTES, io_threads=8):
+    """Objective measures of generated against natural feature files (WorldBatch.dtw_align, feature_distortion).
+
+    jobs:     [(generated_0, natural_0, generated_1, natural_1, ..., label file or None)]: per stream, in the streams'
+              order, float32 rows of the stream's DIM; the natural utterance's label file last
+    streams:  [(name, dim)]; what is scored of each: evaluate_groups
+    align:    "dtw": the path is found on the mgc stream's scored columns and every stream is scored along it;
+              "truncate": frame k against frame k up to the shorter side
+    silences: label names whose frames of the NATURAL side are left out (gv_label_mask's rows, frame_shift_s seconds)
+    Rank-sharded by cells (frames for truncate); a batch is closed by frames and, for dtw, by W.dtw_workspace_bytes.
+    Returns (pooled, rows, info): pooled = W.pool_distortion's dict per stream, rows float64 [n_jobs][n_streams][4] in the
+    jobs' order (zeros for a flagged utterance), info int64 [n_jobs][4] = T_a, T_b, pairs on the path, status.  With
+    several ranks the rows are added up over the ranks, so every rank returns the same."""
+    import torch
+    if align not in ("dtw", "truncate"):
+        raise ValueError("align is dtw or truncate, not %r" % (align,))
+    streams = [(str(n_), int(d)) for n_, d in streams]
+    groups = evaluate_groups(streams, with_c0)
+    kinds = [k for _, _, k in groups]
+    ns = len(streams)
+    names = [n_ for n_, _ in streams]
+    if align == "dtw" and "mgc" not in names:
+        raise ValueError("--align dtw finds the path on the mgc stream: there is none")
+    jobs = [tuple(j) for j in jobs]
+    silences = tuple(silences)
+    ta, tb = [], []
+    for j in jobs:
+        if len(j) != 2 * ns + 1:
+            raise ValueError("%s: a job is %d paths (generated and natural per stream, the label file), not %d"
+                             % (j[0], 2 * ns + 1, len(j)))
+        sides = []
+        for side in (0, 1):
+            n = {_rows_in((j[2 * s + side],), d) for s, (_, d) in enumerate(streams)}
+            if len(n) != 1:
+                raise ValueError("%s: the streams' files disagree on the frames" % j[side])
+            sides.append(n.pop())
+        if not 1 <= sides[0] <= 32767 or sides[1] > 32767:
+            raise ValueError("%s: %d generated and %d natural frames; 1 .. 32767 and 0 .. 32767 can be aligned"
+                             % (j[0], sides[0], sides[1]))
+        ta.append(sides[0])
+        tb.append(sides[1])
+    cost = [a_ * max(b_, 1) for a_, b_ in zip(ta, tb)] if align == "dtw" else ta
+    mine = [k for k in _my_share(cost)]
+    rank, world = _rank_world()
+    rows = np.zeros((len(jobs), ns, 4), dtype=np.float64)
+    info = np.zeros((len(jobs), 4), dtype=np.int64)
+    fits = None
+    if align == "dtw":
+        fits = lambda g: W.dtw_workspace_bytes([ta[i] for i in g], [tb[i] for i in g]) <= max_workspace_bytes
+    if mine:
+        with _Stage(ctx, io_threads) as stage:
+            order = sorted(mine, key=lambda i: -cost[i])
+            for group in _batches(order, ta, max_batch_frames, fits):
+                b_len = [tb[i] for i in group]
+                with stage.batch(f0_lengths=[ta[i] for i in group]) as b:
+                    gen = [stage.load([jobs[i][2 * s] for i in group], d) for s, (_, d) in enumerate(streams)]
+                    nat = [stage.load([jobs[i][2 * s + 1] for i in group], d) if sum(b_len) else
+                           torch.zeros(0, d, dtype=torch.float32, device="cuda") for s, (_, d) in enumerate(streams)]
+                    mask = None
+                    if silences and any(jobs[i][-1] for i in group):
+                        parts = []
+                        for i in group:
+                            if jobs[i][-1]:
+                                with open(jobs[i][-1]) as f:
+                                    parts.append(gv_label_mask(f.readlines(), frame_shift_s, tb[i], silences))
+                            else:
+                                parts.append(np.ones(tb[i], dtype=np.uint8))
+                        mask = _upload(np.concatenate(parts))
+                    path = path_len = None
+                    status = np.array([0 if n_ else 2 for n_ in b_len])
+                    pairs = np.minimum([ta[i] for i in group], b_len)
+                    if align == "dtw" and sum(b_len):
+                        m = names.index("mgc")
+                        path, path_len, _, st = b.dtw_align(gen[m], nat[m], b_len, groups[m][0], groups[m][1])
+                        status, pairs = st.cpu().numpy(), path_len.cpu().numpy()
+                    if sum(b_len):
+                        out = b.feature_distortion([(gen[s], nat[s], f, c, k) for s, (f, c, k) in enumerate(groups)], b_len,
+                                                   path, path_len, mask, voiced_above).cpu().numpy()
+                    else:
+                        out = np.zeros((len(group), ns, 4))
+                    for k, i in enumerate(group):
+                        rows[i] = out[k]
+                        info[i] = (ta[i], tb[i], pairs[k], status[k])
+    if world > 1:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("evaluate_files with WORLD_SIZE > 1 needs torch.distributed to be initialised: the ranks' "
+                               "rows have to be put together")
+        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+        packed = torch.from_numpy(rows).to(dev)                      # a row is another rank's or zeros: the sum is exact
+        counts = torch.from_numpy(info).to(dev)
+        dist.all_reduce(packed)
+        dist.all_reduce(counts)
+        rows, info = packed.cpu().numpy(), counts.cpu().numpy()
+    return W.pool_distortion(rows, kinds), rows, info
+
+
+def evaluate_report(streams, pooled, rows, info, jobs, align):
+    """(the JSON object of evaluate's --out, the lines of --per-utterance) from evaluate_files' results."""
+    obj = {"align": align, "utterances": int(len(jobs)), "flagged": int(np.count_nonzero(info[:, 3])), "streams": {}}
+    for (name, _), p in zip(streams, pooled):
+        obj["streams"][name] = p
+    lines = []
+    for i, j in enumerate(jobs):
+        cols = [j[0]] + [str(int(v)) for v in info[i]]
+        for g, p in enumerate(W.pool_distortion(rows[i:i + 1], [p_["kind"] for p_ in pooled])):
+            if p["kind"] == 0:
+                cols += ["%.17g" % p["mean_db"], str(p["pairs"])]
+            else:
+                cols += ["%.17g" % p["rmse_cents"], "%.17g" % p["vuv_error_percent"], str(p["voiced_pairs"]), str(p["pairs"])]
+        lines.append("\t".join(cols))
+    return obj, lines
+
+
 def _read_scp(path, n=4):
     with open(path) as f:
         rows = [ln.split() for ln in f if ln.strip() and not ln.startswith("#")]
@@ -2146,7 +2293,47 @@ def main(argv=None):
                    "one file per stream and .p_mgc")
     p.add_argument("--resume", action="store_true", help="skip utterances whose wav is already complete")
     p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
+    p = sub.add_parser("evaluate", help="objective measures of generated against natural feature files: mel-cepstral "
+                       "distortion, lf0 RMSE, V/UV error, along a DTW path or by truncation")
+    p.add_argument("--scp", required=True, help="job list: per --stream in order the generated then the natural file, and the "
+                   "natural utterance's label file last ('-' for none)")
+    p.add_argument("--stream", action="append", required=True, type=parse_eval_stream, metavar="NAME:DIM",
+                   help="mgc: cepstral distortion over columns 1 .. DIM-1; lf0: RMSE and V/UV error; any other name: cepstral "
+                   "distortion over all columns")
+    p.add_argument("--align", choices=("dtw", "truncate"), default="dtw", help="dtw: along the path found on the mgc stream")
+    p.add_argument("--with-c0", action="store_true", help="score column 0 of mgc too")
+    p.add_argument("--silence", action="append", default=[], help="a label name whose natural frames are left out (may be repeated)")
+    p.add_argument("--frame-shift-s", type=float, default=0.005, help="seconds per frame, for the label files")
+    p.add_argument("--voiced-above", type=float, default=-1.0e9, help="an lf0 value above this is voiced")
+    p.add_argument("--out", default=None, help="the pooled figures and counts as one JSON object")
+    p.add_argument("--per-utterance", default=None, help="a tab-separated line per utterance, in the job list's order")
+    p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
     a = ap.parse_args(argv)
+    if a.cmd == "evaluate":
+        import json
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:                # torchrun: the ranks' rows are put together
+            import torch
+            import torch.distributed as dist
+            torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+            if not dist.is_initialized():
+                dist.init_process_group(os.environ.get("WM_BACKEND", "nccl"))
+        jobs = [r[:-1] + (None if r[-1] == "-" else r[-1],) for r in _read_scp(a.scp, 2 * len(a.stream) + 1)]
+        try:
+            pooled, rows, info = evaluate_files(jobs, a.stream, a.align, a.with_c0, a.silence, a.frame_shift_s,
+                                                a.voiced_above, max_batch_frames=a.max_batch_frames)
+        except ValueError as err:
+            ap.error(str(err))
+        obj, lines = evaluate_report(a.stream, pooled, rows, info, jobs, a.align)
+        if _rank_world()[0] == 0:
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(obj, f, indent=1)
+                    f.write("\n")
+            if a.per_utterance:
+                with open(a.per_utterance, "w") as f:
+                    f.write("".join(ln + "\n" for ln in lines))
+            print(json.dumps(obj))
+        return 0
     if a.cmd == "generate":
         from . import generate
         n, flagged = generate.generate_files(_read_scp(a.scp, 2), **generate_arguments(ap, a))

@@ -85,6 +85,20 @@ class MlsaOption(C.Structure):
                 ("pipe_float32", C.c_int), ("use_pade", C.c_int), ("pade", C.c_double * 8)]
 
 
+class DistortionGroup(C.Structure):
+    """include/world_mi355.h: WorldMi355DistortionGroup (one scored column group of WorldMi355FeatureDistortion)."""
+    _fields_ = [("a", C.c_void_p), ("ld_a", C.c_int64), ("b", C.c_void_p), ("ld_b", C.c_int64), ("first", C.c_int),
+                ("count", C.c_int), ("kind", C.c_int)]
+
+
+class DistortionOption(C.Structure):
+    """include/world_mi355.h: WorldMi355DistortionOption."""
+    _fields_ = [("voiced_above", C.c_double)]
+
+
+DISTORTION_KINDS = ("cepstral", "lf0")                   # kind 0 and 1 of WorldMi355FeatureDistortion
+
+
 class MlpgOption(C.Structure):
     """include/world_mi355.h: WorldMi355MlpgOption (parameter generation, SPTK's mlpg)."""
     _fields_ = [("edge", C.c_int), ("var_per_frame", C.c_int), ("input_type", C.c_int),
@@ -230,6 +244,12 @@ def load_library():
     L.WorldMi355MlsaExcitation.argtypes = [vp, vp, _dp, C.c_int, _dp, C.c_int, C.POINTER(MlsaOption), vp]
     L.WorldMi355MlsaFilter.argtypes = [vp, vp, vp, C.POINTER(MlsaOption), vp, vp]
     L.WorldMi355MlsaSynthesis.argtypes = [vp, vp, vp, _dp, C.c_int, _dp, C.c_int, C.POINTER(MlsaOption), vp, vp]
+    L.WorldMi355DtwWorkspaceBytes.argtypes = [C.c_int, _ip, _ip, C.POINTER(C.c_int64)]
+    L.WorldMi355DtwAlign.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.WorldMi355DefaultDistortionOption.restype = None
+    L.WorldMi355DefaultDistortionOption.argtypes = [C.POINTER(DistortionOption)]
+    L.WorldMi355FeatureDistortion.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp, C.c_int, C.POINTER(DistortionGroup),
+                                              C.POINTER(DistortionOption), vp]
     L.WorldMi355DefaultMgc2spOption.restype = None
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
@@ -469,6 +489,56 @@ def mlsa_noise(n):
     out = np.zeros(max(int(n), 1), dtype=np.float64)
     _check(load_library().WorldMi355MlsaNoise(int(n), out.ctypes.data_as(_dp)), "MlsaNoise")
     return out[:max(int(n), 0)]
+
+
+def dtw_workspace_bytes(a_lengths, b_lengths) -> int:
+    """Bytes of device memory WorldBatch.dtw_align keeps for pairs of these frame counts (WorldMi355DtwWorkspaceBytes: one
+    back-pointer byte per cell in strips of 64 rows, two rows of D per pair, the descriptors).  Host only: needs no
+    device.  A length outside 0 .. 32767 is refused."""
+    aa, ap = _ints(a_lengths)
+    ba, bp = _ints(b_lengths)
+    if len(aa) != len(ba):
+        raise ValueError("dtw_workspace_bytes: %d lengths of a and %d of b" % (len(aa), len(ba)))
+    out = C.c_int64(0)
+    _check(load_library().WorldMi355DtwWorkspaceBytes(len(aa), ap, bp, C.byref(out)), "DtwWorkspaceBytes")
+    return int(out.value)
+
+
+def _b_offsets(where, b_lengths, n_utt):
+    lens = np.asarray(b_lengths, dtype=np.int64).reshape(-1)
+    if len(lens) != n_utt:
+        raise ValueError("%s: %d lengths of b for %d utterances" % (where, len(lens), n_utt))
+    off = np.zeros(n_utt + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    return off
+
+
+def pool_distortion(out, kinds):
+    """The corpus figures of WorldBatch.feature_distortion outputs.  out: [n_utt][n_groups][4] (numpy, or anything
+    np.asarray takes; the rows of several batches or ranks stacked in any order); kinds: the n_groups kinds, 0 cepstral
+    and 1 log f0.  Returns one dict per group: kind 0 {"kind": 0, "mean_db": sum e / n, "std_db": its spread over the
+    pairs, "pairs": n}; kind 1 {"kind": 1, "rmse_cents": (1200 / ln 2) sqrt(sum D^2 / n) over the pairs voiced on
+    both sides, "voiced_pairs": n, "vuv_error_percent": 100 differing / counted, "vuv_errors", "pairs"}.  A figure
+    without pairs is nan.  Sums are math.fsum's, exact, so the result does not depend on how a job list was split."""
+    import math
+    o = np.asarray(out, dtype=np.float64).reshape(-1, len(kinds), 4)
+    res = []
+    for g, kind in enumerate(kinds):
+        col = [math.fsum(o[:, g, k].tolist()) for k in range(4)]
+        if int(kind) == 0:
+            n = int(round(col[2]))
+            mean = col[0] / n if n else float("nan")
+            var = max(col[1] / n - mean * mean, 0.0) if n else float("nan")
+            res.append({"kind": 0, "mean_db": mean, "std_db": math.sqrt(var) if n else float("nan"), "pairs": n})
+        elif int(kind) == 1:
+            nv, ne, n = int(round(col[1])), int(round(col[2])), int(round(col[3]))
+            res.append({"kind": 1,
+                        "rmse_cents": 1200.0 / math.log(2.0) * math.sqrt(col[0] / nv) if nv else float("nan"),
+                        "voiced_pairs": nv, "vuv_error_percent": 100.0 * ne / n if n else float("nan"),
+                        "vuv_errors": ne, "pairs": n})
+        else:
+            raise ValueError("pool_distortion: kind %r is neither 0 nor 1" % (kind,))
+    return res
 
 
 class WorldBatch:
@@ -838,6 +908,76 @@ class WorldBatch:
                                                       hp.ctypes.data_as(_dp), len(hp), C.byref(o), self._p(y),
                                                       C.c_void_p(status.data_ptr())), "MlsaSynthesis")
         return y, status
+
+    @staticmethod
+    def _dtw_rows(where, name, t, n_rows):
+        import torch
+        if (not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or int(t.shape[0]) != n_rows):
+            raise ValueError(f"{where}: {name} must be a contiguous float32 cuda tensor of {n_rows} rows, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        return C.c_void_p(t.data_ptr()), int(t.shape[1])
+
+    def dtw_align(self, a, b, b_lengths, first=0, count=None):
+        """The dynamic-time-warping path between the batch's utterances in `a` and their counterparts in `b`
+        (WorldMi355DtwAlign; the definition is in include/world_mi355.h): a float32 cuda [total_frames][ld_a] on the batch's
+        frame layout, b float32 cuda [sum(b_lengths)][ld_b], utterance u's b_lengths[u] rows one after another; the
+        Euclidean distance over the columns [first, first + count) of both (count None: every column of `a` from `first`
+        on; 1 to 64 columns).  Returns (path int32 [sum(T_a + T_b - 1)][2] -- utterance u's pairs (i, j) from index
+        frame_offsets[u] + b_offsets[u] - u on, (-1, -1) behind them --, path_len int32 [n_utt], cost float64 [n_utt],
+        status int32 [n_utt]: bit 1 a non-finite value in the used columns, bit 2 an empty side; either way path_len 0)."""
+        import torch
+        where = "dtw_align"
+        off = _b_offsets(where, b_lengths, self.n_utt)
+        ap, ld_a = self._dtw_rows(where, "a", a, self.total_frames)
+        bp, ld_b = self._dtw_rows(where, "b", b, int(off[-1]))
+        if count is None:
+            count = ld_a - int(first)
+        cap = max(int(self.total_frames + off[-1] - self.n_utt), 0)
+        path = torch.empty(cap, 2, dtype=torch.int32, device="cuda")
+        path_len = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        cost = torch.empty(self.n_utt, dtype=torch.float64, device="cuda")
+        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        _check(load_library().WorldMi355DtwAlign(self.handle, ap, ld_a, bp, ld_b, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 int(first), int(count), C.c_void_p(path.data_ptr()),
+                                                 C.c_void_p(path_len.data_ptr()), self._p(cost),
+                                                 C.c_void_p(status.data_ptr())), "DtwAlign")
+        return path, path_len, cost, status
+
+    def feature_distortion(self, groups, b_lengths, path=None, path_len=None, b_mask=None, voiced_above=-1e9):
+        """The distortion measures along a path (WorldMi355FeatureDistortion).  groups: 1 to 8 of (a, b, first, count, kind)
+        with a and b as dtw_align takes them and kind 0 (cepstral: e = (10 / ln 10) sqrt(2 sum D^2) in dB per pair) or 1
+        (log f0, count 1; a value above voiced_above is voiced).  path, path_len: dtw_align's, or both None: the pairs
+        (k, k) for k < min(T_a, T_b).  b_mask: None or uint8 cuda [sum(b_lengths)], 0 where a frame of b is left out.
+        Returns float64 cuda [n_utt][n_groups][4]: kind 0 (sum e, sum e^2, counted pairs, 0); kind 1 (sum D^2 over the
+        pairs voiced on both sides, those pairs, the pairs whose voicing differs, counted pairs).  pool_distortion makes
+        the corpus figures of it."""
+        import torch
+        where = "feature_distortion"
+        off = _b_offsets(where, b_lengths, self.n_utt)
+        groups = list(groups)
+        arr = (DistortionGroup * max(1, len(groups)))()
+        for g, (a, b, first, count, kind) in enumerate(groups):
+            ap, ld_a = self._dtw_rows(where, "a of group %d" % g, a, self.total_frames)
+            bp, ld_b = self._dtw_rows(where, "b of group %d" % g, b, int(off[-1]))
+            arr[g] = DistortionGroup(ap, ld_a, bp, ld_b, int(first), int(count), int(kind))
+        if (path is None) != (path_len is None):
+            raise ValueError(f"{where}: path and path_len come together")
+        cap = max(int(self.total_frames + off[-1] - self.n_utt), 0)
+        for name, t, shape, dtype in (("path", path, (cap, 2), torch.int32), ("path_len", path_len, (self.n_utt,), torch.int32),
+                                      ("b_mask", b_mask, (int(off[-1]),), torch.uint8)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError(f"{where}: {name} must be a contiguous {dtype} cuda tensor {list(shape)}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+        o = DistortionOption()
+        load_library().WorldMi355DefaultDistortionOption(C.byref(o))
+        o.voiced_above = float(voiced_above)
+        out = torch.empty(self.n_utt, len(groups), 4, dtype=torch.float64, device="cuda")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        _check(load_library().WorldMi355FeatureDistortion(self.handle, ptr(path), ptr(path_len),
+                                                          off.ctypes.data_as(C.POINTER(C.c_int64)), ptr(b_mask), len(groups),
+                                                          arr, C.byref(o), self._p(out)), "FeatureDistortion")
+        return out
 
     def spectrum_from_mel_cepstrum(self, mc, alpha=0.35, gamma=0.0, out_format=0, phase=False):
         """SPTK's mgc2sp per frame (test/sptkfunctions.cpp:186-219 with flng = fft_size): mc is float64 cuda

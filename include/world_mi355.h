@@ -356,6 +356,64 @@ int WorldMi355MlsaFilter(WorldMi355Batch* b, const double* e, const float* mc, c
 int WorldMi355MlsaSynthesis(WorldMi355Batch* b, const float* pitch, const float* mc, const double* lowpass, int n_low,
                             const double* highpass, int n_high, const WorldMi355MlsaOption* opt, double* y, int* status);
 
+/* ---- Objective evaluation: alignment by dynamic time warping and the distortion measures along a path ----
+ * What tells a generated feature file from the natural one: mel-cepstral distortion in dB, the lf0 error on the frames both
+ * sides call voiced, the voiced/unvoiced error, the distortion of any other stream.  The reference tree holds no evaluation
+ * code.  PARITY IS UNPINNED: the yardstick is the definition below, which tests/dtw_reference.py states in numpy.
+ * For utterance u, sequence A is the rows of `a` on the batch's frame layout: T_a is the batch's frame count of u, row t at
+ * a + (frame_off[u] + t) * ld_a.  Sequence B is the rows of `b`: b_off is HOST int64[n_utt + 1], T_b = b_off[u+1] - b_off[u],
+ * row t at b + (b_off[u] + t) * ld_b.  a and b are DEVICE float32.  Only the columns [first, first + count) of both enter.
+ * Everything is computed in double:
+ *   d(i, j) = sqrt( sum_{k = first .. first+count-1} (a[i][k] - b[j][k])^2 )        ascending k
+ *   D(0,0) = d(0,0);  D(i,0) = d(i,0) + D(i-1,0);  D(0,j) = d(0,j) + D(0,j-1)
+ *   D(i,j) = d(i,j) + min( D(i-1,j-1), D(i-1,j), D(i,j-1) )
+ *   path:  backwards from (T_a-1, T_b-1) to (0,0); at (i,j) with i, j > 0 the predecessor with the smallest D,
+ *          on equality (i-1,j-1) before (i-1,j) before (i,j-1); written in forward order
+ * path: DEVICE int32[sum_u (T_a + T_b - 1)][2], pairs (i, j); utterance u starts at pair index frame_off[u] + b_off[u] - u
+ * and its unused capacity is written (-1, -1).  path_len: DEVICE int32[n_utt].  cost: DEVICE double[n_utt], D(T_a-1, T_b-1).
+ * status: DEVICE int[n_utt] or NULL.  Bit 1: a non-finite value in the used columns of either sequence; path_len is 0 and
+ * cost NaN.  Bit 2: T_a = 0 or T_b = 0; path_len is 0 and cost 0.  A flagged utterance affects no other, and an utterance's
+ * bits do not depend on the batch around it.
+ * Limits: count 1 .. 64; T_a, T_b <= 32767.  WM_ERR_BAD_ARG before any device call: a limit exceeded, a NULL pointer (status
+ * excepted), first < 0, first + count beyond ld_a or ld_b, a b_off that decreases or does not start at 0.  Asynchronous on
+ * the context's stream.  Timed as "dtw_kernel" (the recurrence) and "dtw_path_kernel" (the walk).
+ * The call keeps one byte per cell on the device (the back-pointers, in strips of 64 rows of A by T_b + 63 steps) and two
+ * rows of D per pair, as the batch's workspace: DtwWorkspaceBytes says how much for these lengths (host only, no device
+ * needed; WM_ERR_BAD_ARG for a NULL pointer or a length outside 0 .. 32767).  The descriptors of the pairs are kept with
+ * b_off: a call with another b_off on the same batch waits for the stream and rebuilds them. */
+int WorldMi355DtwWorkspaceBytes(int n_utt, const int* a_lengths, const int* b_lengths, int64_t* bytes);
+int WorldMi355DtwAlign(WorldMi355Batch* b, const float* a, int64_t ld_a, const float* bs, int64_t ld_b, const int64_t* b_off,
+                       int first, int count, int* path, int* path_len, double* cost, int* status);
+/* The measures along a path.  path, path_len: DtwAlign's, or both NULL: the pairs are (k, k) for k < min(T_a, T_b), i.e.
+ * truncation.  b_off as above.  b_mask: NULL or DEVICE uint8[b_off[n_utt]]; a pair whose B frame has mask 0 is left out (the
+ * silences of the natural utterance's labels).  A pair outside [0, T_a) x [0, T_b) is left out too.  groups: HOST, 1 .. 8 of
+ * them, rows of a and b laid out as above, each scored over its columns [first, first + count):
+ *   kind 0, cepstral, in dB   e = (10 / ln 10) sqrt(2 sum_k D_k^2), D_k = a[i][k] - b[j][k], per counted pair
+ *                             out: sum e, sum e^2, counted pairs, 0
+ *   kind 1, log f0, count 1   a value above voiced_above is voiced; D = a - b in natural-log units
+ *                             out: sum D^2 over the pairs voiced on both sides, the number of those pairs, the pairs whose
+ *                             voicing differs, counted pairs
+ * out: DEVICE double[n_utt][n_groups][4].  Sums run in pair order, in double; a left-out pair adds 0, so the order depends on
+ * path_len alone.  An utterance DtwAlign flagged (path_len 0) gives zeros.
+ * WM_ERR_BAD_ARG before any device call: as above, and n_groups outside 1 .. 8, a kind other than 0 and 1, kind 1 with count
+ * other than 1, only one of path and path_len, a non-finite voiced_above.  Asynchronous on the context's stream. */
+typedef struct {
+  const float* a;
+  int64_t ld_a;
+  const float* b;
+  int64_t ld_b;
+  int first;
+  int count;
+  int kind;
+} WorldMi355DistortionGroup;
+typedef struct {
+  double voiced_above;    /* -1e9: the recipe's unvoiced value is -1e10 */
+} WorldMi355DistortionOption;
+void WorldMi355DefaultDistortionOption(WorldMi355DistortionOption* opt);
+int WorldMi355FeatureDistortion(WorldMi355Batch* b, const int* path, const int* path_len, const int64_t* b_off,
+                                const unsigned char* b_mask, int n_groups, const WorldMi355DistortionGroup* groups,
+                                const WorldMi355DistortionOption* opt, double* out);
+
 /* ---- `cmp` composition (data/scripts/window.pl:45-146, addhtkheader.pl:45-82), SURVEY.md section 8(f) rank 3 ----
  * Applies each stream's dynamic-feature windows and lays the results side by side per frame:
  *   out[frame] = [stream 0: window 0 (dim) | window 1 | ...][stream 1: ...]...      (float32)
