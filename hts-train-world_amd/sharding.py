@@ -51,7 +51,8 @@ def lpt_shards(costs, world_size: int, handicap=None) -> list[list[int]]:
     empty) list."""
     order = sorted(range(len(costs)), key=lambda i: (-costs[i], i))
     scale = [1.0] * world_size if handicap is None else [float(h) for h in handicap]
-    assert len(scale) == world_size and all(h >= 1.0 for h in scale)
+    if len(scale) != world_size or not all(h >= 1.0 for h in scale):
+        raise ValueError("lpt_shards: handicap needs one factor >= 1 per rank (%d), got %r" % (world_size, scale))
     load = [0.0] * world_size
     shards: list[list[int]] = [[] for _ in range(world_size)]
     for i in order:
@@ -99,7 +100,8 @@ def gather_features(tensors, frame_counts, dst: int = 0, group=None, all_counts=
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if all_counts is not None:
         counts = [[int(c) for c in cs] for cs in all_counts]
-        assert counts[rank] == [int(c) for c in frame_counts]
+        if counts[rank] != [int(c) for c in frame_counts]:
+            raise ValueError("gather_features: all_counts[%d] is not this rank's frame_counts" % rank)
     else:
         counts = [None] * world
         dist.all_gather_object(counts, [int(c) for c in frame_counts], group=group)

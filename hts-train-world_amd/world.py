@@ -4,6 +4,7 @@ Mirrors the reference's per-utterance operator interface
 (externs/WORLD_v2/src/world/{dio,stonemask,cheaptrick,d4c,synthesis,harvest}.h)
 for numpy callers and adds ``WorldBatch`` for device-resident batches (torch
 tensors on ``cuda``).  torch is used only for device memory and streams.
+The C ABI takes raw pointers, so every tensor passes ``check_tensor`` first.
 
 The library is mandatory: nothing here computes WORLD on the CPU.
 """
@@ -41,12 +42,88 @@ def _window_tables(window_lists):
     return nwin, wptrs, sptrs, keep
 
 
+class _LazyTorch:
+    """Stands in for torch until something here first needs it, then makes way for it: importing this module does not
+    import torch."""
+
+    def __getattr__(self, name):
+        global torch
+        import torch
+        return getattr(torch, name)
+
+
+torch = _LazyTorch()
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def row_stride(t):
+    """The row stride the library is given for a 2-D tensor: the tensor's own, except that a tensor of one row reports
+    any stride, so its width."""
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def torch_device(device):
+    """The torch device of a context made with `device`: cuda of that index, torch's current device for None; a
+    torch.device or its name stays what it is."""
+    if device is None:
+        device = torch.cuda.current_device()
+    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+def check_tensor(where, name, t, dtype, shape, device, layout="contiguous", optional=False):
+    """The one check of a tensor handed to the library, whose C ABI takes raw pointers and can check nothing itself.
+    shape: a tuple with, per dimension, an int for "exactly this" or None for "free, at least 1"; an int alone: that many
+    elements in any shape; None: any shape.  layout: "contiguous"; "rows" (2-D, unit column stride, rows that do not
+    overlap: passed by its row stride); "any" (the caller makes the copy it needs).  optional: None passes through as
+    None, a NULL pointer.
+    Returns the c_void_p, then with "rows" the row stride (row_stride), then the free dimensions in order (the element
+    count for shape None) -- alone when nothing follows it, else as a tuple.  Anything else -- no tensor, another dtype,
+    shape, layout or device -- raises ValueError naming the method, the argument, what was wanted and what was given."""
+    if t is None and optional:
+        return None
+    ok, free = torch.is_tensor(t) and t.dtype == dtype and t.device == device, []
+    if ok and isinstance(shape, tuple):
+        ok = t.dim() == len(shape) and all(g == w if w is not None else g >= 1 for w, g in zip(shape, t.shape))
+        free = [int(g) for w, g in zip(shape, t.shape) if w is None]
+    elif ok:
+        ok, free = shape is None or t.numel() == shape, [int(t.numel())] if shape is None else []
+    if ok and layout == "rows":
+        ok = t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1) and (t.shape[0] < 2 or t.stride(0) >= t.shape[1])
+        free.insert(0, row_stride(t) if ok else 0)
+    elif ok and layout == "contiguous":
+        ok = t.is_contiguous()
+    if not ok:
+        dims = ("" if shape is None else "of %d elements " % shape if isinstance(shape, int)
+                else "".join("[%s]" % ("any" if w is None else w) for w in shape) + " ")
+        want = {"contiguous": "contiguous ", "rows": "unit-column-stride ", "any": ""}[layout]
+        given = (f"{t.dtype} {list(t.shape)} with strides {list(t.stride())} on {t.device}" if torch.is_tensor(t)
+                 else type(t).__name__)
+        raise ValueError(f"{where}: {name} must be a {want}{dtype} tensor {dims}on {device}, got {given}")
+    return (C.c_void_p(t.data_ptr()), *free) if free else C.c_void_p(t.data_ptr())
+
+
+def _option(where, Struct, default, fields, allowed=None, *args):
+    """A Struct as the library's `default` call (with `args` in front of the struct) fills it, then `fields` set: a
+    value of None keeps the default, a name outside `allowed` (None: every field of the Struct) raises TypeError."""
+    o = Struct()
+    getattr(load_library(), default)(*args, C.byref(o))
+    names = [f[0] for f in Struct._fields_] if allowed is None else allowed
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError(f"{where}: unknown option {k!r}")
+        if v is not None:
+            setattr(o, k, v)
+    return o
+
+
 def _shared_row_stride(rows, cols, total_frames):
     """One row stride for the matrices `rows` and the column vectors `cols` (None entries stay None): as given when
     all share one, else packed side by side.  Returns (row stride, rows, cols, what to keep alive)."""
-    import torch
     ts = list(rows) + [c for c in cols if c is not None]
-    ld = {int(t.stride(0)) for t in ts}
+    ld = {row_stride(t) for t in rows} | {int(c.stride(0)) for c in cols if c is not None}
     if total_frames > 1 and len(ld) == 1 and all(t.stride(1) == 1 for t in rows):
         return ld.pop(), rows, cols, ts
     mat = torch.cat(list(rows) + [c[:, None] for c in cols if c is not None], dim=1)
@@ -145,12 +222,8 @@ OPTIMIZER_SLOT_INIT = ((), (0.0,), (0.1,), (0.0, 0.0), (0.0, 0.0), (1.0,))      
 
 def default_optimizer_option(rule, **over) -> OptimizerOption:
     """TF 1.x's defaults of `rule` (a name or its code); the powers are the betas."""
-    o = OptimizerOption()
-    load_library().WorldMi355DefaultOptimizerOption(OPTIMIZER_RULES.index(rule) if isinstance(rule, str) else int(rule),
-                                                    C.byref(o))
-    for k, v in over.items():
-        setattr(o, k, v)
-    return o
+    return _option("default_optimizer_option", OptimizerOption, "WorldMi355DefaultOptimizerOption", over, None,
+                   OPTIMIZER_RULES.index(rule) if isinstance(rule, str) else int(rule))
 
 
 class McpfOption(C.Structure):
@@ -348,6 +421,7 @@ class Context:
                                          C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(h)),
                "CreateContext")
         self.handle = h
+        self.device = device                                # None: the current device (torch_device resolves it)
 
     def set_stream(self, stream_ptr: int | None = None):
         """Move the context to another HIP stream (WorldMi355SetStream): waits on the host for everything queued on the
@@ -378,23 +452,20 @@ class Context:
         every rule but sgd; slot1: adadelta and adam); rates: one float per tensor.  params and the slots are updated in
         place.  Returns None, or with want_status an int32 cuda tensor [len(params)]: 1 where a gradient element of that
         tensor is not finite.  Asynchronous on the context's stream."""
-        import torch
         n = len(params)
         need = OPTIMIZER_SLOTS[option.rule] if 0 <= option.rule < len(OPTIMIZER_SLOTS) else 0
         lists = [params, grads] + [slot0, slot1][:need]
         if any(l is None or len(l) != n for l in lists) or len(rates) != n:
             raise ValueError("optimizer_step: %d parameters need as many gradients, rates and (%d) slots each" % (n, need))
-        for l in lists:
-            for t, p in zip(l, params):
-                if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                    raise ValueError("optimizer_step: every tensor must be float32, cuda and contiguous")
-                if t.numel() != p.numel() or t.device != p.device:
-                    raise ValueError("optimizer_step: a gradient or slot of %d elements for a parameter of %d"
-                                     % (t.numel(), p.numel()))
-        ptrs = [(C.c_void_p * n)(*[t.data_ptr() for t in l]) for l in lists] + [None] * (2 - need)
-        count = (C.c_int64 * n)(*[p.numel() for p in params])
+        device = torch_device(self.device)
+        sizes = [check_tensor("optimizer_step", "params[%d]" % k, p, torch.float32, None, device)[1]
+                 for k, p in enumerate(params)]
+        ptrs = [(C.c_void_p * n)(*[check_tensor("optimizer_step", "%s[%d]" % (name, k), t, torch.float32, sizes[k], device)
+                                   for k, t in enumerate(l)])
+                for name, l in zip(("params", "grads", "slot0", "slot1"), lists)] + [None] * (2 - need)
+        count = (C.c_int64 * n)(*sizes)
         rate = (C.c_float * n)(*[float(r) for r in rates])
-        status = torch.empty(n, dtype=torch.int32, device=params[0].device) if want_status and n else None
+        status = torch.empty(n, dtype=torch.int32, device=device) if want_status and n else None
         _check(load_library().WorldMi355OptimizerStep(self.handle, C.byref(option), n, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
                                                       count, rate, status.data_ptr() if status is not None else None),
                "OptimizerStep")
@@ -541,11 +612,17 @@ def pool_distortion(out, kinds):
     return res
 
 
+MCEP_OPTIONS = ("order", "alpha", "itr1", "itr2", "dd", "etype", "e", "f", "itype")
+
+
 class WorldBatch:
     """A batch of utterances resident in HBM (torch cuda tensors, float64).
 
     x is the concatenation of the waveforms (see ``sample_offsets``); t, f0 have
     ``total_frames`` entries, sp/ap ``total_frames x (fft_size/2+1)``.
+
+    Every tensor argument is checked on the host against the dtype, shape, layout and device its method states
+    (check_tensor: ValueError); every output is made on ``device``, the context's.
     """
 
     def __init__(self, ctx: Context, params: WorldParams, x_lengths=None, f0_lengths=None, y_lengths=None,
@@ -572,12 +649,13 @@ class WorldBatch:
         self.frame_offsets = np.ctypeslib.as_array(L.WorldMi355BatchFrameOffsets(h), (n + 1,)).copy()
         self.out_offsets = np.ctypeslib.as_array(L.WorldMi355BatchOutputOffsets(h), (n + 1,)).copy()
         self.f0_estimator, self.refine = "dio", True
-        if (code, bool(refine)) != (0, True):
-            try:
+        try:
+            self.device = torch_device(getattr(ctx, "device", None))       # where the library runs: outputs, checks
+            if (code, bool(refine)) != (0, True):
                 self.set_f0_estimator(f0_estimator, refine)
-            except Exception:
-                self.close()
-                raise
+        except Exception:
+            self.close()
+            raise
 
     def set_f0_estimator(self, f0_estimator="dio", refine=True):
         """The f0 front end of analyze() and analyze_synthesize() from the next call on: "dio" (a new batch's) or "harvest",
@@ -587,172 +665,201 @@ class WorldBatch:
         _check(load_library().WorldMi355BatchSetF0Estimator(self.handle, code, 1 if refine else 0), "BatchSetF0Estimator")
         self.f0_estimator, self.refine = f0_estimator, bool(refine)
 
-    @staticmethod
-    def _p(t):
-        assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64", "cuda float64 contiguous"
-        return C.c_void_p(t.data_ptr())
+    def _new(self, *shape, dtype=None, zero=False):
+        """Every output and status tensor: on the batch's device, float64 unless `dtype` says otherwise."""
+        return (torch.zeros if zero else torch.empty)(shape, dtype=dtype or torch.float64, device=self.device)
 
-    def _new(self, *shape):
-        import torch
-        return torch.empty(*shape, dtype=torch.float64, device="cuda")
+    def _f64(self, where, name, t, *shape, **mode):
+        return check_tensor(where, name, t, torch.float64, shape, self.device, **mode)
+
+    def _f32(self, where, name, t, *shape, **mode):
+        return check_tensor(where, name, t, torch.float32, shape, self.device, **mode)
+
+    def _out(self, where, out, *shape, name="out"):
+        """A caller's float64 output, checked, or a fresh one: (tensor, pointer)."""
+        if out is None:
+            out = self._new(*shape)
+            return out, _ptr(out)
+        return out, self._f64(where, name, out, *shape)
+
+    def _xtf0(self, where, x, t, f0):
+        return (self._f64(where, "x", x, self.total_samples), self._f64(where, "t", t, self.total_frames),
+                self._f64(where, "f0", f0, self.total_frames))
+
+    def _f0_sp_ap(self, where, f0, sp, ap, optional=False):
+        return (self._f64(where, "f0", f0, self.total_frames, optional=optional),
+                self._f64(where, "sp", sp, self.total_frames, self.bins, optional=optional),
+                self._f64(where, "ap", ap, self.total_frames, self.bins, optional=optional))
+
+    def _f0_front(self, where, call, x):
+        xp = self._f64(where, "x", x, self.total_samples)
+        t, f0 = self._new(self.total_frames), self._new(self.total_frames)
+        _check(getattr(load_library(), "WorldMi355" + call)(self.handle, xp, _ptr(t), _ptr(f0)), call)
+        return t, f0
 
     def dio(self, x):
-        t, f0 = self._new(self.total_frames), self._new(self.total_frames)
-        _check(load_library().WorldMi355Dio(self.handle, self._p(x), self._p(t), self._p(f0)), "Dio")
-        return t, f0
+        return self._f0_front("dio", "Dio", x)
 
     def harvest(self, x):
-        t, f0 = self._new(self.total_frames), self._new(self.total_frames)
-        _check(load_library().WorldMi355Harvest(self.handle, self._p(x), self._p(t), self._p(f0)), "Harvest")
-        return t, f0
+        return self._f0_front("harvest", "Harvest", x)
 
     def stonemask(self, x, t, f0):
+        args = self._xtf0("stonemask", x, t, f0)
         out = self._new(self.total_frames)
-        _check(load_library().WorldMi355StoneMask(self.handle, self._p(x), self._p(t), self._p(f0), self._p(out)),
-               "StoneMask")
+        _check(load_library().WorldMi355StoneMask(self.handle, *args, _ptr(out)), "StoneMask")
+        return out
+
+    def _per_bin(self, where, call, x, t, f0, out):
+        args = self._xtf0(where, x, t, f0)
+        out, op = self._out(where, out, self.total_frames, self.bins)
+        _check(getattr(load_library(), "WorldMi355" + call)(self.handle, *args, op), call)
         return out
 
     def cheaptrick(self, x, t, f0, out=None):
-        sp = out if out is not None else self._new(self.total_frames, self.bins)
-        _check(load_library().WorldMi355CheapTrick(self.handle, self._p(x), self._p(t), self._p(f0), self._p(sp)),
-               "CheapTrick")
-        return sp
+        return self._per_bin("cheaptrick", "CheapTrick", x, t, f0, out)
 
     def d4c(self, x, t, f0, out=None):
-        ap = out if out is not None else self._new(self.total_frames, self.bins)
-        _check(load_library().WorldMi355D4C(self.handle, self._p(x), self._p(t), self._p(f0), self._p(ap)), "D4C")
-        return ap
+        return self._per_bin("d4c", "D4C", x, t, f0, out)
 
     def samples_from_pcm16(self, pcm, out=None):
         """int16 cuda tensor [total_samples] (the wav payload) -> float64 samples s / 32768 (wavread)."""
-        assert pcm.is_cuda and pcm.is_contiguous() and str(pcm.dtype) == "torch.int16" and pcm.numel() == self.total_samples
-        x = out if out is not None else self._new(self.total_samples)
-        _check(load_library().WorldMi355SamplesFromPcm16(self.handle, C.c_void_p(pcm.data_ptr()), self._p(x)),
-               "SamplesFromPcm16")
+        pp = check_tensor("samples_from_pcm16", "pcm", pcm, torch.int16, int(self.total_samples), self.device)
+        x, xp = self._out("samples_from_pcm16", out, self.total_samples)
+        _check(load_library().WorldMi355SamplesFromPcm16(self.handle, pp, xp), "SamplesFromPcm16")
         return x
 
     def samples_to_pcm16(self, y, out=None):
         """float64 y [total_out] -> int16 as wavwrite stores it: clamp(int(y * 32767)), truncating towards zero."""
-        import torch
-        pcm = out if out is not None else torch.empty(self.total_out, dtype=torch.int16, device="cuda")
-        assert pcm.is_cuda and pcm.is_contiguous() and pcm.numel() == self.total_out
-        _check(load_library().WorldMi355SamplesToPcm16(self.handle, self._p(y), C.c_void_p(pcm.data_ptr())),
-               "SamplesToPcm16")
+        yp = self._f64("samples_to_pcm16", "y", y, self.total_out)
+        pcm = out if out is not None else self._new(self.total_out, dtype=torch.int16)
+        pp = check_tensor("samples_to_pcm16", "out", pcm, torch.int16, int(self.total_out), self.device)
+        _check(load_library().WorldMi355SamplesToPcm16(self.handle, yp, pp), "SamplesToPcm16")
         return pcm
+
+    def _analysis_out(self, where, out):
+        """analyze's (t, f0, sp, ap), fresh or the caller's four, checked: (the tensors, their pointers)."""
+        shapes = ((self.total_frames,), (self.total_frames,), (self.total_frames, self.bins), (self.total_frames, self.bins))
+        if out is None:
+            out = tuple(self._new(*s) for s in shapes)
+            return out, [_ptr(t) for t in out]
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise ValueError(f"{where}: out must be the four tensors (t, f0, sp, ap)")
+        return tuple(out), [self._f64(where, "out[%d]" % k, t, *s) for k, (t, s) in enumerate(zip(out, shapes))]
 
     def analyze(self, x, out=None):
         """Dio -> StoneMask -> CheapTrick -> D4C (test/analysis.cpp:243-390); with set_f0_estimator, Harvest in Dio's place
         and StoneMask or not."""
-        if out is None:
-            out = (self._new(self.total_frames), self._new(self.total_frames),
-                   self._new(self.total_frames, self.bins), self._new(self.total_frames, self.bins))
-        t, f0, sp, ap = out
-        _check(load_library().WorldMi355Analyze(self.handle, self._p(x), self._p(t), self._p(f0), self._p(sp),
-                                                self._p(ap)), "Analyze")
-        return t, f0, sp, ap
+        xp = self._f64("analyze", "x", x, self.total_samples)
+        out, ptrs = self._analysis_out("analyze", out)
+        _check(load_library().WorldMi355Analyze(self.handle, xp, *ptrs), "Analyze")
+        return out
 
     def analyze_synthesize(self, x, out=None, y=None):
         """analyze() then synthesize() of its own features as one call: the f0-only part of Synthesis overlaps
         CheapTrick and D4C on a second stream.  Returns (t, f0, sp, ap, y), bit-identical to the two calls."""
-        if out is None:
-            out = (self._new(self.total_frames), self._new(self.total_frames),
-                   self._new(self.total_frames, self.bins), self._new(self.total_frames, self.bins))
-        t, f0, sp, ap = out
-        y = y if y is not None else self._new(self.total_out)
-        _check(load_library().WorldMi355AnalyzeSynthesize(self.handle, self._p(x), self._p(t), self._p(f0),
-                                                          self._p(sp), self._p(ap), self._p(y)), "AnalyzeSynthesize")
-        return t, f0, sp, ap, y
+        xp = self._f64("analyze_synthesize", "x", x, self.total_samples)
+        out, ptrs = self._analysis_out("analyze_synthesize", out)
+        y, yp = self._out("analyze_synthesize", y, self.total_out, name="y")
+        _check(load_library().WorldMi355AnalyzeSynthesize(self.handle, xp, *ptrs, yp), "AnalyzeSynthesize")
+        return out + (y,)
 
     def synthesize(self, f0, sp, ap, out=None):
-        y = out if out is not None else self._new(self.total_out)
-        _check(load_library().WorldMi355Synthesis(self.handle, self._p(f0), self._p(sp), self._p(ap), self._p(y)),
-               "Synthesis")
+        args = self._f0_sp_ap("synthesize", f0, sp, ap)
+        y, yp = self._out("synthesize", out, self.total_out)
+        _check(load_library().WorldMi355Synthesis(self.handle, *args, yp), "Synthesis")
         return y
 
     def vibrato(self, lf0, segments):
         """The recipe's vibrato feature (data/scripts/Extract.py).  lf0: float32 cuda [total_frames];
         segments: per utterance a list of (start_frame, end_frame, note_pitch_hz).  Returns (vib, lf0_2col, n_too_long):
         float32 cuda tensors [total_frames][2] after the script's soprLog."""
-        import torch
-        assert lf0.dtype == torch.float32 and lf0.is_cuda and lf0.is_contiguous() and len(segments) == self.n_utt
+        lp = self._f32("vibrato", "lf0", lf0, self.total_frames)
+        if len(segments) != self.n_utt:
+            raise ValueError(f"vibrato: {len(segments)} segment lists for {self.n_utt} utterances")
         off = np.zeros(self.n_utt + 1, dtype=np.int32)
         off[1:] = np.cumsum([len(s) for s in segments])
         flat = [seg for s in segments for seg in s]
         ss = np.ascontiguousarray([int(v[0]) for v in flat], dtype=np.int32)
         se = np.ascontiguousarray([int(v[1]) for v in flat], dtype=np.int32)
         sp_ = np.ascontiguousarray([float(v[2]) for v in flat], dtype=np.float64)
-        vib = torch.empty(self.total_frames, 2, dtype=torch.float32, device="cuda")
-        out = torch.empty(self.total_frames, 2, dtype=torch.float32, device="cuda")
+        vib = self._new(self.total_frames, 2, dtype=torch.float32)
+        out = self._new(self.total_frames, 2, dtype=torch.float32)
         n = C.c_int(0)
-        _check(load_library().WorldMi355Vibrato(self.handle, C.c_void_p(lf0.data_ptr()), off.ctypes.data_as(_ip),
-                                                ss.ctypes.data_as(_ip), se.ctypes.data_as(_ip), sp_.ctypes.data_as(_dp),
-                                                C.c_void_p(vib.data_ptr()), C.c_void_p(out.data_ptr()), C.byref(n)),
-               "Vibrato")
+        _check(load_library().WorldMi355Vibrato(self.handle, lp, off.ctypes.data_as(_ip), ss.ctypes.data_as(_ip),
+                                                se.ctypes.data_as(_ip), sp_.ctypes.data_as(_dp), _ptr(vib), _ptr(out),
+                                                C.byref(n)), "Vibrato")
         return vib, out, n.value
 
     def utterance_status(self, x=None, f0=None, sp=None, ap=None):
         """int32 cuda tensor [n_utt] of WM_UTT_* flags (1 non-finite input, 2 too short for Dio -- not set when the batch's
-        estimator is Harvest --, 4 non-finite output)."""
-        import torch
-        st = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        ptr = lambda t: None if t is None else self._p(t)
-        _check(load_library().WorldMi355UtteranceStatus(self.handle, ptr(x), ptr(f0), ptr(sp), ptr(ap),
-                                                        C.c_void_p(st.data_ptr())), "UtteranceStatus")
+        estimator is Harvest --, 4 non-finite output).  x float64 [total_samples], f0, sp, ap as analyze's, each or None."""
+        xp = self._f64("utterance_status", "x", x, self.total_samples, optional=True)
+        args = self._f0_sp_ap("utterance_status", f0, sp, ap, optional=True)
+        st = self._new(self.n_utt, dtype=torch.int32, zero=True)
+        _check(load_library().WorldMi355UtteranceStatus(self.handle, xp, *args, _ptr(st)), "UtteranceStatus")
         return st
 
     # ---- feature codec (world/codec.h; SURVEY.md section 8(f)) ----
-    def code_spectral_envelope(self, sp, number_of_dimensions):
-        import torch
-        out = torch.empty(self.total_frames, number_of_dimensions, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355CodeSpectralEnvelope(self.handle, self._p(sp), number_of_dimensions,
-                                                             self._p(out)), "CodeSpectralEnvelope")
+    def _codec(self, where, call, name, t, cols, out_cols, *dims):
+        """One codec call: float64 [total_frames][cols] (None: free, passed on) -> float64 [total_frames][out_cols]."""
+        res = self._f64(where, name, t, self.total_frames, cols)
+        tp, *free = res if cols is None else (res,)
+        out = self._new(self.total_frames, out_cols)
+        _check(getattr(load_library(), "WorldMi355" + call)(self.handle, tp, *dims, *free, _ptr(out)), call)
         return out
+
+    def _n_aperiodicities(self):
+        return load_library().WorldMi355GetNumberOfAperiodicities(int(self.params.fs))
+
+    def code_spectral_envelope(self, sp, number_of_dimensions):
+        """sp float64 [total_frames][fft_size/2+1] -> float64 [total_frames][number_of_dimensions] (codec.cpp:268-295)."""
+        return self._codec("code_spectral_envelope", "CodeSpectralEnvelope", "sp", sp, self.bins, number_of_dimensions,
+                           number_of_dimensions)
 
     def decode_spectral_envelope(self, coded):
-        import torch
-        out = torch.empty(self.total_frames, self.fft_size // 2 + 1, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355DecodeSpectralEnvelope(self.handle, self._p(coded), int(coded.shape[1]),
-                                                               self._p(out)), "DecodeSpectralEnvelope")
-        return out
+        """coded float64 [total_frames][number of dimensions] -> sp [total_frames][fft_size/2+1] (codec.cpp:297-324)."""
+        return self._codec("decode_spectral_envelope", "DecodeSpectralEnvelope", "coded", coded, None, self.bins)
 
     def code_aperiodicity(self, ap):
-        import torch
-        nap = load_library().WorldMi355GetNumberOfAperiodicities(int(self.params.fs))
-        out = torch.empty(self.total_frames, nap, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355CodeAperiodicity(self.handle, self._p(ap), self._p(out)), "CodeAperiodicity")
-        return out
+        """ap float64 [total_frames][fft_size/2+1] -> float64 [total_frames][bands of fs] (codec.cpp:217-235)."""
+        return self._codec("code_aperiodicity", "CodeAperiodicity", "ap", ap, self.bins, self._n_aperiodicities())
 
     def decode_aperiodicity(self, coded):
-        import torch
-        out = torch.empty(self.total_frames, self.fft_size // 2 + 1, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355DecodeAperiodicity(self.handle, self._p(coded), self._p(out)),
-               "DecodeAperiodicity")
-        return out
+        """coded float64 [total_frames][bands of fs] -> ap [total_frames][fft_size/2+1] (codec.cpp:237-266)."""
+        return self._codec("decode_aperiodicity", "DecodeAperiodicity", "coded", coded, self._n_aperiodicities(), self.bins)
 
     def recipe_features(self, f0, sp, ap, spec_dim=50, ap_dim=25):
         """float32 lf0 / mgc / bap as the recipe's `analysis ... 5 2048 50 25` call writes them."""
-        import torch
-        lf0 = torch.empty(self.total_frames, dtype=torch.float32, device="cuda")
-        mgc = torch.empty(self.total_frames, spec_dim, dtype=torch.float32, device="cuda")
-        bap = torch.empty(self.total_frames, ap_dim, dtype=torch.float32, device="cuda")
-        _check(load_library().WorldMi355RecipeFeatures(self.handle, self._p(f0), self._p(sp), self._p(ap), spec_dim,
-                                                       ap_dim, C.c_void_p(lf0.data_ptr()), C.c_void_p(mgc.data_ptr()),
-                                                       C.c_void_p(bap.data_ptr())), "RecipeFeatures")
+        args = self._f0_sp_ap("recipe_features", f0, sp, ap)
+        lf0 = self._new(self.total_frames, dtype=torch.float32)
+        mgc = self._new(self.total_frames, spec_dim, dtype=torch.float32)
+        bap = self._new(self.total_frames, ap_dim, dtype=torch.float32)
+        _check(load_library().WorldMi355RecipeFeatures(self.handle, *args, spec_dim, ap_dim, _ptr(lf0), _ptr(mgc),
+                                                       _ptr(bap)), "RecipeFeatures")
         return lf0, mgc, bap
 
     def recipe_decode(self, lf0, mgc, bap):
-        """f0 / sp / ap from the recipe's float32 lf0 / mgc / bap, as the synth CLI rebuilds them
-        (test/synth.cpp:151-256); ap bins beyond the coding order are 0 (uninitialised in the reference)."""
-        import torch
-        for v in (lf0, mgc, bap):
-            assert v.dtype == torch.float32 and v.is_cuda and v.is_contiguous()
-        f0 = torch.empty(self.total_frames, dtype=torch.float64, device="cuda")
-        sp = torch.empty(self.total_frames, self.bins, dtype=torch.float64, device="cuda")
-        ap = torch.empty(self.total_frames, self.bins, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355RecipeDecode(self.handle, C.c_void_p(lf0.data_ptr()), C.c_void_p(mgc.data_ptr()),
-                                                     C.c_void_p(bap.data_ptr()), mgc.shape[1], bap.shape[1],
-                                                     self._p(f0), self._p(sp), self._p(ap)), "RecipeDecode")
+        """f0 / sp / ap from the recipe's float32 lf0 [total_frames] / mgc [total_frames][spec_dim] / bap
+        [total_frames][ap_dim], as the synth CLI rebuilds them (test/synth.cpp:151-256); ap bins beyond the coding order
+        are 0 (uninitialised in the reference)."""
+        lp = self._f32("recipe_decode", "lf0", lf0, self.total_frames)
+        mp, spec_dim = self._f32("recipe_decode", "mgc", mgc, self.total_frames, None)
+        bp, ap_dim = self._f32("recipe_decode", "bap", bap, self.total_frames, None)
+        f0, sp, ap = self._new(self.total_frames), self._new(self.total_frames, self.bins), self._new(self.total_frames, self.bins)
+        _check(load_library().WorldMi355RecipeDecode(self.handle, lp, mp, bp, spec_dim, ap_dim, _ptr(f0), _ptr(sp),
+                                                     _ptr(ap)), "RecipeDecode")
         return f0, sp, ap
+
+    def _mcep(self, where, call, src, order, alpha, itype, opt, *front):
+        """What the three mel-cepstrum calls share behind their checked input `src`: the option, (mc, status), the call
+        with `front` between the input and the option."""
+        o = _option(where, McepOption, "WorldMi355DefaultMcepOption",
+                    dict({"itype": itype}, **opt, order=int(order), alpha=float(alpha)), MCEP_OPTIONS)
+        mc = self._new(self.total_frames, max(int(order), 0) + 1)
+        status = self._new(self.total_frames, dtype=torch.int32)
+        _check(getattr(load_library(), "WorldMi355" + call)(self.handle, src, *front, C.byref(o), _ptr(mc), _ptr(status)),
+               call)
+        return mc, status
 
     def mel_cepstrum(self, spectrum, order=25, alpha=0.35, **opt):
         """SPTK's mcep per frame (test/sptkfunctions.cpp:11-184 with flng = fft_size): spectrum is float64 cuda
@@ -760,49 +867,15 @@ class WorldBatch:
         as WorldMi355McepOption's fields: itr1, itr2, dd, etype, e, f.  Returns (mc float64 [total_frames][order+1],
         status int32 [total_frames]: 0 converged, -1 itr2 steps without meeting dd, 1 singular pivot in theq,
         2 a periodogram value <= 0 or non-finite)."""
-        import torch
-        o = McepOption()
-        load_library().WorldMi355DefaultMcepOption(C.byref(o))
-        o.order, o.alpha = int(order), float(alpha)
-        for k, v in opt.items():
-            if k not in ("itr1", "itr2", "dd", "etype", "e", "f", "itype"):
-                raise TypeError(f"mel_cepstrum: unknown option {k!r}")
-            setattr(o, k, v)
-        if (tuple(spectrum.shape) != (self.total_frames, self.bins) or spectrum.dtype != torch.float64
-                or not spectrum.is_cuda or not spectrum.is_contiguous()):
-            raise ValueError(f"mel_cepstrum: spectrum must be a contiguous float64 cuda tensor "
-                             f"[{self.total_frames}][{self.bins}], got {spectrum.dtype} {tuple(spectrum.shape)}")
-        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MelCepstrum(self.handle, self._p(spectrum), C.byref(o), self._p(mc),
-                                                    C.c_void_p(status.data_ptr())), "MelCepstrum")
-        return mc, status
-
-    def _mcep_option(self, where, order, alpha, opt):
-        o = McepOption()
-        load_library().WorldMi355DefaultMcepOption(C.byref(o))
-        o.order, o.alpha, o.itype = int(order), float(alpha), 0
-        for k, v in opt.items():
-            if k not in ("itr1", "itr2", "dd", "etype", "e", "f", "itype"):
-                raise TypeError(f"{where}: unknown option {k!r}")
-            setattr(o, k, v)
-        return o
+        src = self._f64("mel_cepstrum", "spectrum", spectrum, self.total_frames, self.bins)
+        return self._mcep("mel_cepstrum", "MelCepstrum", src, order, alpha, 3, opt)
 
     def mel_cepstrum_of_frames(self, frames, order=25, alpha=0.35, **opt):
         """SPTK's mcep with itype 0 per frame (test/sptkfunctions.cpp:11-184 with flng = fft_size): frames is float64 cuda
         [total_frames][fft_size], windowed and zero-padded.  Options as mel_cepstrum's; etype 2 (the floor e < 0 dB below
         the frame's maximum) is taken here.  Returns (mc, status) as mel_cepstrum does."""
-        import torch
-        o = self._mcep_option("mel_cepstrum_of_frames", order, alpha, opt)
-        if (tuple(frames.shape) != (self.total_frames, self.fft_size) or frames.dtype != torch.float64
-                or not frames.is_cuda or not frames.is_contiguous()):
-            raise ValueError(f"mel_cepstrum_of_frames: frames must be a contiguous float64 cuda tensor "
-                             f"[{self.total_frames}][{self.fft_size}], got {frames.dtype} {tuple(frames.shape)}")
-        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MelCepstrumOfFrames(self.handle, self._p(frames), C.byref(o), self._p(mc),
-                                                            C.c_void_p(status.data_ptr())), "MelCepstrumOfFrames")
-        return mc, status
+        src = self._f64("mel_cepstrum_of_frames", "frames", frames, self.total_frames, self.fft_size)
+        return self._mcep("mel_cepstrum_of_frames", "MelCepstrumOfFrames", src, order, alpha, 0, opt)
 
     def mel_cepstrum_of_waveform(self, x, window, frame_length, frame_shift, order=25, alpha=0.35, pipe_float32=False,
                                  **opt):
@@ -810,29 +883,19 @@ class WorldBatch:
         cuda [total_samples]; window the host table of frame_length doubles (sptk_window's); the batch's f0_lengths must
         be sptk_frames of its x_lengths.  pipe_float32 rounds every windowed sample to float32 once, as SPTK's pipe does.
         Options as mel_cepstrum_of_frames'.  Returns (mc, status) as mel_cepstrum does."""
-        import torch
-        o = self._mcep_option("mel_cepstrum_of_waveform", order, alpha, opt)
-        if (tuple(x.shape) != (self.total_samples,) or x.dtype != torch.float64 or not x.is_cuda
-                or not x.is_contiguous()):
-            raise ValueError(f"mel_cepstrum_of_waveform: x must be a contiguous float64 cuda tensor "
-                             f"[{self.total_samples}], got {x.dtype} {tuple(x.shape)}")
+        src = self._f64("mel_cepstrum_of_waveform", "x", x, self.total_samples)
         w = np.ascontiguousarray(window, dtype=np.float64)
         if w.shape != (max(int(frame_length), 0),):
             raise ValueError(f"mel_cepstrum_of_waveform: window must hold frame_length = {frame_length} values, "
                              f"got {w.shape}")
-        mc = torch.empty(self.total_frames, max(int(order), 0) + 1, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MelCepstrumOfWaveform(
-            self.handle, self._p(x), w.ctypes.data_as(_dp), int(frame_length), int(frame_shift), 1 if pipe_float32 else 0,
-            C.byref(o), self._p(mc), C.c_void_p(status.data_ptr())), "MelCepstrumOfWaveform")
-        return mc, status
+        return self._mcep("mel_cepstrum_of_waveform", "MelCepstrumOfWaveform", src, order, alpha, 0, opt,
+                          w.ctypes.data_as(_dp), int(frame_length), int(frame_shift), 1 if pipe_float32 else 0)
 
     @staticmethod
-    def _mlsa_option(order=25, alpha=0.35, pade_order=4, frame_shift=100, pipe_float32=False, pade=None):
-        o = MlsaOption()
-        load_library().WorldMi355DefaultMlsaOption(C.byref(o))
-        o.order, o.alpha, o.pade_order, o.frame_shift = int(order), float(alpha), int(pade_order), int(frame_shift)
-        o.pipe_float32 = 1 if pipe_float32 else 0
+    def _mlsa_option(where, order=25, alpha=0.35, pade_order=4, frame_shift=100, pipe_float32=False, pade=None):
+        o = _option(where, MlsaOption, "WorldMi355DefaultMlsaOption",
+                    dict(order=int(order), alpha=float(alpha), pade_order=int(pade_order), frame_shift=int(frame_shift),
+                         pipe_float32=1 if pipe_float32 else 0))
         if pade is not None:
             row = [float(v) for v in pade]
             if len(row) != int(pade_order) + 1 or len(row) > 8:
@@ -847,27 +910,19 @@ class WorldBatch:
         t = np.ascontiguousarray(taps, dtype=np.float64)
         if t.ndim != 1:
             raise ValueError(f"{where}: {name} must be a list of taps, got shape {t.shape}")
-        return t
-
-    def _mlsa_rows(self, where, name, t, shape, dtype):
-        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{where}: {name} must be a contiguous {dtype} cuda tensor {list(shape)}, "
-                             f"got {t.dtype} {tuple(t.shape)}")
-        return C.c_void_p(t.data_ptr())
+        return t.ctypes.data_as(_dp), len(t), t
 
     def mlsa_excitation(self, pitch, lowpass, highpass, frame_shift=100, pipe_float32=False):
         """`excite -n -p frame_shift pit | dfs -b lowpass` plus `excite` of an all-zero pitch `| dfs -b highpass`
         (scripts/Training.pl:2873-2899): pitch float32 cuda [total_frames], the period in samples with 0 for unvoiced;
         lowpass, highpass the caller's taps (1 to 256 each, host).  The batch's y_lengths must be mlsa_samples of its
         f0_lengths.  Returns e float64 [total output samples]; an utterance with a non-finite or negative pitch is zeros."""
-        import torch
         where = "mlsa_excitation"
-        o = self._mlsa_option(frame_shift=frame_shift, pipe_float32=pipe_float32)
+        o = self._mlsa_option(where, frame_shift=frame_shift, pipe_float32=pipe_float32)
         lp, hp = self._mlsa_taps(where, "lowpass", lowpass), self._mlsa_taps(where, "highpass", highpass)
-        pp = self._mlsa_rows(where, "pitch", pitch, (self.total_frames,), torch.float32)
-        e = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
-        _check(load_library().WorldMi355MlsaExcitation(self.handle, pp, lp.ctypes.data_as(_dp), len(lp),
-                                                       hp.ctypes.data_as(_dp), len(hp), C.byref(o), self._p(e)),
+        pp = self._f32(where, "pitch", pitch, self.total_frames)
+        e = self._new(self.total_out)
+        _check(load_library().WorldMi355MlsaExcitation(self.handle, pp, *lp[:2], *hp[:2], C.byref(o), _ptr(e)),
                "MlsaExcitation")
         return e
 
@@ -876,17 +931,12 @@ class WorldBatch:
         output samples], mc float32 cuda [total_frames][order+1]; pade a caller's row of pade_order + 1 values in place of
         mlsa_pade's.  Returns (y float64 [total output samples], status int32 [n_utt]: 0 fine, 1 a non-finite coefficient
         -- the utterance is zeros --, 2 a non-finite output sample)."""
-        import torch
         where = "mlsa_filter"
-        if mc.dim() != 2:
-            raise ValueError(f"{where}: mc must be [total_frames][order+1], got {tuple(mc.shape)}")
-        o = self._mlsa_option(int(mc.shape[1]) - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
-        mp = self._mlsa_rows(where, "mc", mc, (self.total_frames, int(mc.shape[1])), torch.float32)
-        ep = self._mlsa_rows(where, "e", e, (self.total_out,), torch.float64)
-        y = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MlsaFilter(self.handle, ep, mp, C.byref(o), self._p(y),
-                                                   C.c_void_p(status.data_ptr())), "MlsaFilter")
+        mp, cols = self._f32(where, "mc", mc, self.total_frames, None)
+        ep = self._f64(where, "e", e, self.total_out)
+        o = self._mlsa_option(where, cols - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
+        y, status = self._new(self.total_out), self._new(self.n_utt, dtype=torch.int32)
+        _check(load_library().WorldMi355MlsaFilter(self.handle, ep, mp, C.byref(o), _ptr(y), _ptr(status)), "MlsaFilter")
         return y, status
 
     def mlsa_synthesis(self, pitch, mc, lowpass, highpass, order=None, alpha=0.35, pade_order=4, frame_shift=100,
@@ -894,29 +944,17 @@ class WorldBatch:
         """mlsa_excitation and mlsa_filter in one call, bit for bit, without the excitation in device memory beyond the
         block being filtered.  order, if given, must be mc's.  Returns (y, status) as mlsa_filter does; status 1 also for
         a non-finite or negative pitch."""
-        import torch
         where = "mlsa_synthesis"
-        if mc.dim() != 2 or (order is not None and int(order) != int(mc.shape[1]) - 1):
+        mp, cols = self._f32(where, "mc", mc, self.total_frames, None)
+        if order is not None and int(order) != cols - 1:
             raise ValueError(f"{where}: mc must be [total_frames][order+1], got {tuple(mc.shape)} at order {order}")
-        o = self._mlsa_option(int(mc.shape[1]) - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
+        pp = self._f32(where, "pitch", pitch, self.total_frames)
+        o = self._mlsa_option(where, cols - 1, alpha, pade_order, frame_shift, pipe_float32, pade)
         lp, hp = self._mlsa_taps(where, "lowpass", lowpass), self._mlsa_taps(where, "highpass", highpass)
-        pp = self._mlsa_rows(where, "pitch", pitch, (self.total_frames,), torch.float32)
-        mp = self._mlsa_rows(where, "mc", mc, (self.total_frames, int(mc.shape[1])), torch.float32)
-        y = torch.empty(self.total_out, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MlsaSynthesis(self.handle, pp, mp, lp.ctypes.data_as(_dp), len(lp),
-                                                      hp.ctypes.data_as(_dp), len(hp), C.byref(o), self._p(y),
-                                                      C.c_void_p(status.data_ptr())), "MlsaSynthesis")
+        y, status = self._new(self.total_out), self._new(self.n_utt, dtype=torch.int32)
+        _check(load_library().WorldMi355MlsaSynthesis(self.handle, pp, mp, *lp[:2], *hp[:2], C.byref(o), _ptr(y),
+                                                      _ptr(status)), "MlsaSynthesis")
         return y, status
-
-    @staticmethod
-    def _dtw_rows(where, name, t, n_rows):
-        import torch
-        if (not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
-                or int(t.shape[0]) != n_rows):
-            raise ValueError(f"{where}: {name} must be a contiguous float32 cuda tensor of {n_rows} rows, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        return C.c_void_p(t.data_ptr()), int(t.shape[1])
 
     def dtw_align(self, a, b, b_lengths, first=0, count=None):
         """The dynamic-time-warping path between the batch's utterances in `a` and their counterparts in `b`
@@ -926,22 +964,19 @@ class WorldBatch:
         on; 1 to 64 columns).  Returns (path int32 [sum(T_a + T_b - 1)][2] -- utterance u's pairs (i, j) from index
         frame_offsets[u] + b_offsets[u] - u on, (-1, -1) behind them --, path_len int32 [n_utt], cost float64 [n_utt],
         status int32 [n_utt]: bit 1 a non-finite value in the used columns, bit 2 an empty side; either way path_len 0)."""
-        import torch
         where = "dtw_align"
         off = _b_offsets(where, b_lengths, self.n_utt)
-        ap, ld_a = self._dtw_rows(where, "a", a, self.total_frames)
-        bp, ld_b = self._dtw_rows(where, "b", b, int(off[-1]))
+        ap, ld_a = self._f32(where, "a", a, self.total_frames, None)
+        bp, ld_b = self._f32(where, "b", b, int(off[-1]), None)
         if count is None:
             count = ld_a - int(first)
         cap = max(int(self.total_frames + off[-1] - self.n_utt), 0)
-        path = torch.empty(cap, 2, dtype=torch.int32, device="cuda")
-        path_len = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
-        cost = torch.empty(self.n_utt, dtype=torch.float64, device="cuda")
-        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        path = self._new(cap, 2, dtype=torch.int32)
+        path_len, status = self._new(self.n_utt, dtype=torch.int32), self._new(self.n_utt, dtype=torch.int32)
+        cost = self._new(self.n_utt)
         _check(load_library().WorldMi355DtwAlign(self.handle, ap, ld_a, bp, ld_b, off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                 int(first), int(count), C.c_void_p(path.data_ptr()),
-                                                 C.c_void_p(path_len.data_ptr()), self._p(cost),
-                                                 C.c_void_p(status.data_ptr())), "DtwAlign")
+                                                 int(first), int(count), _ptr(path), _ptr(path_len), _ptr(cost),
+                                                 _ptr(status)), "DtwAlign")
         return path, path_len, cost, status
 
     def feature_distortion(self, groups, b_lengths, path=None, path_len=None, b_mask=None, voiced_above=-1e9):
@@ -952,31 +987,24 @@ class WorldBatch:
         Returns float64 cuda [n_utt][n_groups][4]: kind 0 (sum e, sum e^2, counted pairs, 0); kind 1 (sum D^2 over the
         pairs voiced on both sides, those pairs, the pairs whose voicing differs, counted pairs).  pool_distortion makes
         the corpus figures of it."""
-        import torch
         where = "feature_distortion"
         off = _b_offsets(where, b_lengths, self.n_utt)
         groups = list(groups)
         arr = (DistortionGroup * max(1, len(groups)))()
         for g, (a, b, first, count, kind) in enumerate(groups):
-            ap, ld_a = self._dtw_rows(where, "a of group %d" % g, a, self.total_frames)
-            bp, ld_b = self._dtw_rows(where, "b of group %d" % g, b, int(off[-1]))
+            ap, ld_a = self._f32(where, "groups[%d][0]" % g, a, self.total_frames, None)
+            bp, ld_b = self._f32(where, "groups[%d][1]" % g, b, int(off[-1]), None)
             arr[g] = DistortionGroup(ap, ld_a, bp, ld_b, int(first), int(count), int(kind))
         if (path is None) != (path_len is None):
             raise ValueError(f"{where}: path and path_len come together")
         cap = max(int(self.total_frames + off[-1] - self.n_utt), 0)
-        for name, t, shape, dtype in (("path", path, (cap, 2), torch.int32), ("path_len", path_len, (self.n_utt,), torch.int32),
-                                      ("b_mask", b_mask, (int(off[-1]),), torch.uint8)):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError(f"{where}: {name} must be a contiguous {dtype} cuda tensor {list(shape)}, got {t.dtype} "
-                                 f"{tuple(t.shape)}")
-        o = DistortionOption()
-        load_library().WorldMi355DefaultDistortionOption(C.byref(o))
-        o.voiced_above = float(voiced_above)
-        out = torch.empty(self.n_utt, len(groups), 4, dtype=torch.float64, device="cuda")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        _check(load_library().WorldMi355FeatureDistortion(self.handle, ptr(path), ptr(path_len),
-                                                          off.ctypes.data_as(C.POINTER(C.c_int64)), ptr(b_mask), len(groups),
-                                                          arr, C.byref(o), self._p(out)), "FeatureDistortion")
+        pp = check_tensor(where, "path", path, torch.int32, (cap, 2), self.device, optional=True)
+        lp = check_tensor(where, "path_len", path_len, torch.int32, (self.n_utt,), self.device, optional=True)
+        mp = check_tensor(where, "b_mask", b_mask, torch.uint8, (int(off[-1]),), self.device, optional=True)
+        o = _option(where, DistortionOption, "WorldMi355DefaultDistortionOption", {"voiced_above": float(voiced_above)})
+        out = self._new(self.n_utt, len(groups), 4)
+        _check(load_library().WorldMi355FeatureDistortion(self.handle, pp, lp, off.ctypes.data_as(C.POINTER(C.c_int64)), mp,
+                                                          len(groups), arr, C.byref(o), _ptr(out)), "FeatureDistortion")
         return out
 
     def spectrum_from_mel_cepstrum(self, mc, alpha=0.35, gamma=0.0, out_format=0, phase=False):
@@ -985,20 +1013,15 @@ class WorldBatch:
         ln|H|, 3 |H|, 4 |H|^2 (as mel_cepstrum's itype).  Returns (spectrum float64 [total_frames][fft_size/2+1],
         status int32 [total_frames]: 0 fine, 1 a non-finite coefficient or 1 + gamma c0 <= 0, the row is zeros), with
         phase=True (spectrum, phase, status), phase being the transform's imaginary part."""
-        import torch
-        if (mc.dim() != 2 or mc.shape[0] != self.total_frames or mc.dtype != torch.float64 or not mc.is_cuda
-                or not mc.is_contiguous()):
-            raise ValueError(f"spectrum_from_mel_cepstrum: mc must be a contiguous float64 cuda tensor "
-                             f"[{self.total_frames}][order+1], got {mc.dtype} {tuple(mc.shape)}")
-        o = Mgc2spOption()
-        load_library().WorldMi355DefaultMgc2spOption(C.byref(o))
-        o.alpha, o.gamma, o.order, o.out_format = float(alpha), float(gamma), int(mc.shape[1]) - 1, int(out_format)
-        sp = torch.empty(self.total_frames, self.bins, dtype=torch.float64, device="cuda")
-        ph = torch.empty_like(sp) if phase else None
-        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MelCepstrumToSpectrum(
-            self.handle, self._p(mc), C.byref(o), self._p(sp), self._p(ph) if phase else None,
-            C.c_void_p(status.data_ptr())), "MelCepstrumToSpectrum")
+        where = "spectrum_from_mel_cepstrum"
+        mp, cols = self._f64(where, "mc", mc, self.total_frames, None)
+        o = _option(where, Mgc2spOption, "WorldMi355DefaultMgc2spOption",
+                    dict(alpha=float(alpha), gamma=float(gamma), order=cols - 1, out_format=int(out_format)))
+        sp = self._new(self.total_frames, self.bins)
+        ph = self._new(self.total_frames, self.bins) if phase else None
+        status = self._new(self.total_frames, dtype=torch.int32)
+        _check(load_library().WorldMi355MelCepstrumToSpectrum(self.handle, mp, C.byref(o), _ptr(sp), _ptr(ph),
+                                                              _ptr(status)), "MelCepstrumToSpectrum")
         return (sp, ph, status) if phase else (sp, status)
 
     def postfilter_mel_cepstrum(self, mc, alpha=0.35, beta=1.4, length=4096, gain=False):
@@ -1008,43 +1031,28 @@ class WorldBatch:
         bins.  Returns (out float64 [total_frames][order+1], status int32 [total_frames]: 0 fine, 1 a non-finite
         coefficient, 2 a sum that is not finite and positive; flagged rows are zeros), with gain=True
         (out, gain float64 [total_frames] = delta, status).  beta == 1 or order == 1 copies the rows."""
-        import torch
-        if (mc.dim() != 2 or mc.shape[0] != self.total_frames or mc.dtype != torch.float64 or not mc.is_cuda
-                or not mc.is_contiguous()):
-            raise ValueError(f"postfilter_mel_cepstrum: mc must be a contiguous float64 cuda tensor "
-                             f"[{self.total_frames}][order+1], got {mc.dtype} {tuple(mc.shape)}")
-        o = McpfOption()
-        load_library().WorldMi355DefaultMcpfOption(C.byref(o))
-        o.alpha, o.beta, o.order, o.length = float(alpha), float(beta), int(mc.shape[1]) - 1, int(length)
-        out = torch.empty_like(mc)
-        g = torch.empty(self.total_frames, dtype=torch.float64, device="cuda") if gain else None
-        status = torch.empty(self.total_frames, dtype=torch.int32, device="cuda")
-        _check(load_library().WorldMi355MelCepstrumPostfilter(
-            self.handle, self._p(mc), C.byref(o), self._p(out), self._p(g) if gain else None,
-            C.c_void_p(status.data_ptr())), "MelCepstrumPostfilter")
+        where = "postfilter_mel_cepstrum"
+        mp, cols = self._f64(where, "mc", mc, self.total_frames, None)
+        o = _option(where, McpfOption, "WorldMi355DefaultMcpfOption",
+                    dict(alpha=float(alpha), beta=float(beta), order=cols - 1, length=int(length)))
+        out = self._new(self.total_frames, cols)
+        g = self._new(self.total_frames) if gain else None
+        status = self._new(self.total_frames, dtype=torch.int32)
+        _check(load_library().WorldMi355MelCepstrumPostfilter(self.handle, mp, C.byref(o), _ptr(out), _ptr(g),
+                                                              _ptr(status)), "MelCepstrumPostfilter")
         return (out, g, status) if gain else (out, status)
 
-    def _mspf_rows(self, x, where):
-        import torch
-        if (x.dim() != 2 or x.shape[0] != self.total_frames or x.shape[1] < 1 or x.dtype != torch.float64
-                or not x.is_cuda or not x.is_contiguous()):
-            raise ValueError(f"{where}: x must be a contiguous float64 cuda tensor [{self.total_frames}][dim], "
-                             f"got {x.dtype} {tuple(x.shape)}")
-        return int(x.shape[1])
-
     @staticmethod
-    def _mspf_option(frame_length, fft_length, emphasis=1.0):
-        o = MspfOption()
-        load_library().WorldMi355DefaultMspfOption(C.byref(o))
-        o.frame_length, o.fft_length, o.emphasis = int(frame_length), int(fft_length), float(emphasis)
-        return o
+    def _mspf_option(where, frame_length, fft_length, emphasis=1.0):
+        return _option(where, MspfOption, "WorldMi355DefaultMspfOption",
+                       dict(frame_length=int(frame_length), fft_length=int(fft_length), emphasis=float(emphasis)))
 
     def utterance_means(self, x):
         """Column means per utterance of x, float64 cuda [total_frames][dim]: float64 [n_utt][dim], summed in a fixed
         order that depends on the utterance's length alone (a batch holds no utterance without frames)."""
-        dim = self._mspf_rows(x, "utterance_means")
+        xp, dim = self._f64("utterance_means", "x", x, self.total_frames, None)
         mean = self._new(self.n_utt, dim)
-        _check(load_library().WorldMi355ColumnMeans(self.handle, self._p(x), dim, self._p(mean)), "ColumnMeans")
+        _check(load_library().WorldMi355ColumnMeans(self.handle, xp, dim, _ptr(mean)), "ColumnMeans")
         return mean
 
     def modulation_spectrum_stats(self, x, frame_length=25, fft_length=64, mean=None):
@@ -1052,19 +1060,15 @@ class WorldBatch:
         [total_frames][dim]; mean None (each utterance's own column means) or float64 cuda [n_utt][dim] (silence
         removal: the whole utterance's).  Returns (sum, sumsq float64 cuda [dim][fft_length/2+1], n_frames int): add
         them across batches and hand them to mspf_finalize."""
-        import torch
-        dim = self._mspf_rows(x, "modulation_spectrum_stats")
-        if mean is not None and (tuple(mean.shape) != (self.n_utt, dim) or mean.dtype != torch.float64
-                                 or not mean.is_cuda or not mean.is_contiguous()):
-            raise ValueError(f"modulation_spectrum_stats: mean must be a contiguous float64 cuda tensor "
-                             f"[{self.n_utt}][{dim}], got {mean.dtype} {tuple(mean.shape)}")
-        o = self._mspf_option(frame_length, fft_length)
+        where = "modulation_spectrum_stats"
+        xp, dim = self._f64(where, "x", x, self.total_frames, None)
+        mp = self._f64(where, "mean", mean, self.n_utt, dim, optional=True)
+        o = self._mspf_option(where, frame_length, fft_length)
         K = int(fft_length) // 2 + 1
         s1, s2 = self._new(dim, K), self._new(dim, K)
         n = C.c_int64(0)
-        _check(load_library().WorldMi355ModulationSpectrumStats(
-            self.handle, self._p(x), dim, C.byref(o), self._p(mean) if mean is not None else None, self._p(s1),
-            self._p(s2), C.byref(n)), "ModulationSpectrumStats")
+        _check(load_library().WorldMi355ModulationSpectrumStats(self.handle, xp, dim, C.byref(o), mp, _ptr(s1), _ptr(s2),
+                                                                C.byref(n)), "ModulationSpectrumStats")
         return s1, s2, int(n.value)
 
     def postfilter_modulation_spectrum(self, x, mean_gen, std_gen, mean_nat, std_nat, emphasis=1.0, frame_length=25,
@@ -1074,46 +1078,39 @@ class WorldBatch:
         tables [dim][fft_length/2+1] (numpy or tensors; they are validated and uploaded by the library).  Returns
         (out float64 [total_frames][dim], status int32 [n_utt]: bit 1 a column with a non-finite input, bit 2 a result
         that is not finite; such a column is zeros in that utterance)."""
-        import torch
-        dim = self._mspf_rows(x, "postfilter_modulation_spectrum")
+        where = "postfilter_modulation_spectrum"
+        xp, dim = self._f64(where, "x", x, self.total_frames, None)
         K = int(fft_length) // 2 + 1
         tabs = []
         for name, t in (("mean_gen", mean_gen), ("std_gen", std_gen), ("mean_nat", mean_nat), ("std_nat", std_nat)):
             a = np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)
             if a.shape != (dim, K):
-                raise ValueError(f"postfilter_modulation_spectrum: {name} must be [{dim}][{K}], got {a.shape}")
+                raise ValueError(f"{where}: {name} must be [{dim}][{K}], got {a.shape}")
             tabs.append(a)
-        o = self._mspf_option(frame_length, fft_length, emphasis)
-        out = torch.empty_like(x)
-        status = torch.empty(self.n_utt, dtype=torch.int32, device="cuda")
+        o = self._mspf_option(where, frame_length, fft_length, emphasis)
+        out, status = self._new(self.total_frames, dim), self._new(self.n_utt, dtype=torch.int32)
         _check(load_library().WorldMi355ModulationSpectrumPostfilter(
-            self.handle, self._p(x), dim, C.byref(o), *[a.ctypes.data_as(C.c_void_p) for a in tabs], self._p(out),
-            C.c_void_p(status.data_ptr())), "ModulationSpectrumPostfilter")
+            self.handle, xp, dim, C.byref(o), *[a.ctypes.data_as(C.c_void_p) for a in tabs], _ptr(out), _ptr(status)),
+            "ModulationSpectrumPostfilter")
         return out, status
+
+    def _compose_streams(self, where, tensors, window_lists):
+        """What compose_cmp and compose_ffo share: the checked float32 [total_frames][dim] tensors as a pointer table and
+        their dims, the window tables, the output columns before any msd column: (n, data, dims, windows, columns)."""
+        n = len(tensors)
+        checked = [self._f32(where, "streams[%d][0]" % s, t, self.total_frames, None) for s, t in enumerate(tensors)]
+        data = (C.c_void_p * n)(*[p for p, _ in checked])
+        dims = (C.c_int * n)(*[d for _, d in checked])
+        return n, data, dims, _window_tables(window_lists), sum(d * len(w) for (_, d), w in zip(checked, window_lists))
 
     def compose_cmp(self, streams):
         """streams: list of (float32 cuda tensor [total_frames][dim], list of window coefficient lists).
         Returns float32 [total_frames][sum n_windows * dim] (window.pl + merge of the recipe's cmp stage)."""
-        import torch
-        n = len(streams)
-        data = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t, _ in streams])
-        dims = (C.c_int * n)(*[int(t.shape[1]) for t, _ in streams])
-        for t, _ in streams:
-            assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float32" and t.shape[0] == self.total_frames
-        nwin, wptrs, sptrs, keep = _window_tables([wins for _, wins in streams])
-        cols = sum(int(t.shape[1]) * len(w) for t, w in streams)
-        out = torch.empty(self.total_frames, cols, dtype=torch.float32, device="cuda")
-        _check(load_library().WorldMi355ComposeCmp(self.handle, n, data, dims, nwin, wptrs, sptrs,
-                                                   C.c_void_p(out.data_ptr())), "ComposeCmp")
+        n, data, dims, (nwin, wptrs, sptrs, keep), cols = self._compose_streams(
+            "compose_cmp", [t for t, _ in streams], [wins for _, wins in streams])
+        out = self._new(self.total_frames, cols, dtype=torch.float32)
+        _check(load_library().WorldMi355ComposeCmp(self.handle, n, data, dims, nwin, wptrs, sptrs, _ptr(out)), "ComposeCmp")
         return out
-
-    def _f32_rows(self, x, where, contiguous=True):
-        import torch
-        if (x.dim() != 2 or x.shape[0] != self.total_frames or x.shape[1] < 1 or x.dtype != torch.float32
-                or not x.is_cuda or x.stride(1) != 1 or (contiguous and not x.is_contiguous())):
-            raise ValueError(f"{where}: x must be a {'contiguous ' if contiguous else ''}float32 cuda tensor "
-                             f"[{self.total_frames}][dim], got {x.dtype} {tuple(x.shape)}")
-        return int(x.shape[1])
 
     def interpolate_gaps(self, x, ignore_value=-1e10):
         """data/scripts/interpolate.pl per utterance and column: x float32 cuda [total_frames][dim]; a value equal to
@@ -1121,16 +1118,14 @@ class WorldBatch:
         Returns (out float32 [total_frames][dim]: gaps between valid frames on the line through them, leading and
         trailing gaps at the nearest valid value, with the script's bits; voiced float32 [total_frames]: 1 where column
         0 is valid, else 0; status int32 [n_utt]: bit 1 a column without a valid value, which is zeros in out)."""
-        import torch
-        dim = self._f32_rows(x, "interpolate_gaps")
+        xp, dim = self._f32("interpolate_gaps", "x", x, self.total_frames, None)
         if not np.isfinite(float(ignore_value)):
             raise ValueError(f"interpolate_gaps: ignore_value must be finite, got {ignore_value}")
-        out = torch.empty_like(x)
-        voiced = torch.empty(self.total_frames, dtype=torch.float32, device="cuda")
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _check(load_library().WorldMi355InterpolateGaps(self.handle, ptr(x), dim, float(ignore_value), ptr(out),
-                                                        ptr(voiced), ptr(status)), "InterpolateGaps")
+        out = self._new(self.total_frames, dim, dtype=torch.float32)
+        voiced = self._new(self.total_frames, dtype=torch.float32)
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
+        _check(load_library().WorldMi355InterpolateGaps(self.handle, xp, dim, float(ignore_value), _ptr(out), _ptr(voiced),
+                                                        _ptr(status)), "InterpolateGaps")
         return out, voiced, status
 
     def compose_ffo(self, streams):
@@ -1138,25 +1133,17 @@ class WorldBatch:
         [total_frames][dim], list of window coefficient lists, msd float32 cuda [total_frames] or None).  A stream with
         msd gets that value as one column in front of its windows; the windows are compose_cmp's.  Returns float32
         [total_frames][row width]."""
-        import torch
-        n = len(streams)
-        if n < 1:
+        if len(streams) < 1:
             raise ValueError("compose_ffo: no streams")
-        for t, wins, msd in streams:
-            self._f32_rows(t, "compose_ffo")
-            if len(wins) < 1 or any(len(w) < 1 for w in wins):
-                raise ValueError("compose_ffo: a stream needs at least one window, a window at least one coefficient")
-            if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and msd.is_contiguous()
-                                        and tuple(msd.shape) == (self.total_frames,)):
-                raise ValueError(f"compose_ffo: msd must be a contiguous float32 cuda tensor [{self.total_frames}]")
-        nwin, wptrs, sptrs, keep = _window_tables([wins for _, wins, _ in streams])
-        data = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t, _, _ in streams])
-        msds = (C.c_void_p * n)(*[C.c_void_p(None if m is None else m.data_ptr()) for _, _, m in streams])
-        dims = (C.c_int * n)(*[int(t.shape[1]) for t, _, _ in streams])
-        cols = sum(int(t.shape[1]) * len(w) + (0 if m is None else 1) for t, w, m in streams)
-        out = torch.empty(self.total_frames, cols, dtype=torch.float32, device="cuda")
-        _check(load_library().WorldMi355ComposeFfo(self.handle, n, data, dims, nwin, wptrs, sptrs, msds,
-                                                   C.c_void_p(out.data_ptr())), "ComposeFfo")
+        if any(len(wins) < 1 or any(len(w) < 1 for w in wins) for _, wins, _ in streams):
+            raise ValueError("compose_ffo: a stream needs at least one window, a window at least one coefficient")
+        n, data, dims, (nwin, wptrs, sptrs, keep), cols = self._compose_streams(
+            "compose_ffo", [t for t, _, _ in streams], [wins for _, wins, _ in streams])
+        msds = (C.c_void_p * n)(*[self._f32("compose_ffo", "streams[%d][2]" % s, m, self.total_frames, optional=True)
+                                  for s, (_, _, m) in enumerate(streams)])
+        out = self._new(self.total_frames, cols + sum(m is not None for _, _, m in streams), dtype=torch.float32)
+        _check(load_library().WorldMi355ComposeFfo(self.handle, n, data, dims, nwin, wptrs, sptrs, msds, _ptr(out)),
+               "ComposeFfo")
         return out
 
     def label_features(self, feature_set, labels, out=None):
@@ -1167,7 +1154,6 @@ class WorldBatch:
         buffer works as it is); only its first n_features columns are written.  Returns (out float32 [total_frames]
         [n_features] with the script's bits, status int32 [n_utt]: bit 1 a value was clamped to 0 or 1 -- the script's
         "Out of range" warning --, bit 2 a state-related reserved feature met a phoneme-level file)."""
-        import torch
         if len(labels) != self.n_utt:
             raise ValueError(f"label_features: {len(labels)} label files for {self.n_utt} utterances")
         nf = feature_set.n_features
@@ -1188,20 +1174,15 @@ class WorldBatch:
         start, end, sidx = (np.ascontiguousarray(c, dtype=np.int32) for c in cols)
         level = np.ascontiguousarray([1 if lv else 0 for _, lv in labels], dtype=np.int32)
         if out is None:
-            out = torch.empty(self.total_frames, nf, dtype=torch.float32, device="cuda")
-        elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2
-              or out.shape[0] != self.total_frames or out.stride(1) != 1):
-            raise ValueError(f"label_features: out must be a float32 cuda tensor [{self.total_frames}][>= {nf}] with unit "
-                             "column stride")
-        ld = int(out.stride(0)) if self.total_frames > 1 else max(int(out.stride(0)), int(out.shape[1]))
-        if out.shape[1] < nf:
-            ld = min(ld, int(out.shape[1]))                      # refused by the library: ld_out < n_features
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+            out = self._new(self.total_frames, nf, dtype=torch.float32)
+        op, ld, width = self._f32("label_features", "out", out, self.total_frames, None, layout="rows")
+        ld = min(ld, width) if width < nf else ld                    # refused by the library: ld_out < n_features
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
         name_ptrs = (C.c_char_p * max(1, n))(*names)
         ip = lambda a: a.ctypes.data_as(_ip)
         _check(load_library().WorldMi355LabelFeatures(self.handle, feature_set.handle, ip(line_off), ip(start), ip(end),
-                                                      ip(sidx), name_ptrs, ip(level), C.c_void_p(out.data_ptr()), ld,
-                                                      C.c_void_p(status.data_ptr())), "LabelFeatures")
+                                                      ip(sidx), name_ptrs, ip(level), op, ld, _ptr(status)),
+               "LabelFeatures")
         return out[:, :nf], status
 
     def column_moments(self, x, width=None, ignore_value=None):
@@ -1210,24 +1191,19 @@ class WorldBatch:
         value equal to float32(ignore_value) is left out of its own column.  Returns (count int64, mean float64, m2
         float64), all cuda [n_utt][width]: the kept values, their mean, and the sum of (x - mean)^2 around it in double
         (two passes); a count of 0 gives mean 0 and m2 0.  The bits do not depend on the batch around an utterance."""
-        import torch
-        cols = self._f32_rows(x, "column_moments", contiguous=False)
+        xp, ld, cols = self._f32("column_moments", "x", x, self.total_frames, None, layout="rows")
         width = cols if width is None else int(width)
         if width < 1 or width > cols:
             raise ValueError(f"column_moments: width must be in 1 .. {cols}, got {width}")
-        ld = int(x.stride(0)) if self.total_frames > 1 else max(int(x.stride(0)), width)
-        if ld < width:
-            raise ValueError(f"column_moments: the row stride {ld} is smaller than width {width}")
         ig = None
         if ignore_value is not None:
             if not np.isfinite(float(ignore_value)):
                 raise ValueError(f"column_moments: ignore_value must be finite, got {ignore_value}")
             ig = C.byref(C.c_double(float(ignore_value)))
-        count = torch.empty(self.n_utt, width, dtype=torch.int64, device="cuda")
+        count = self._new(self.n_utt, width, dtype=torch.int64)
         mean, m2 = self._new(self.n_utt, width), self._new(self.n_utt, width)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _check(load_library().WorldMi355ColumnMoments(self.handle, ptr(x), ld, width, ig, ptr(count), ptr(mean),
-                                                      ptr(m2)), "ColumnMoments")
+        _check(load_library().WorldMi355ColumnMoments(self.handle, xp, ld, width, ig, _ptr(count), _ptr(mean), _ptr(m2)),
+               "ColumnMoments")
         return count, mean, m2
 
     def parameter_generation(self, streams, var_per_frame=False, edge=0, input_type=0, unvoiced_value=-1e10):
@@ -1245,25 +1221,21 @@ class WorldBatch:
         a = self._mlpg_args("parameter_generation", streams, var_per_frame, edge, input_type, unvoiced_value)
         _check(load_library().WorldMi355ParameterGeneration(
             self.handle, a.n, a.means, a.ld_mean, a.vars, a.ld_var, a.dims, a.nwin, a.wptrs, a.sptrs, a.msds,
-            C.byref(a.opt), a.out_ptrs, C.c_void_p(a.status.data_ptr())), "ParameterGeneration")
+            C.byref(a.opt), a.out_ptrs, _ptr(a.status)), "ParameterGeneration")
         return a.outs, a.status
 
     def _mlpg_args(self, who, streams, var_per_frame, edge, input_type, unvoiced_value):
         """What parameter_generation and parameter_generation_gv hand to their C calls: the checked streams on one row
         stride, the window tables, the option, and fresh outputs and status."""
-        import torch
         import types
         n = len(streams)
         tf = self.total_frames
-        for mean, var, wins, msd in streams:
-            if not (mean.is_cuda and mean.dtype == torch.float32 and mean.dim() == 2 and mean.shape[0] == tf
-                    and len(wins) >= 1 and mean.shape[1] % len(wins) == 0):
-                raise ValueError(f"{who}: mean must be float32 cuda [total_frames][n_windows * dim]")
-            want = (tf, mean.shape[1]) if var_per_frame else (mean.shape[1],)
-            if not (var.is_cuda and var.dtype == torch.float32 and tuple(var.shape) == want):
-                raise ValueError(f"{who}: var must be float32 cuda {want}, got {tuple(var.shape)}")
-            if msd is not None and not (msd.is_cuda and msd.dtype == torch.float32 and tuple(msd.shape) == (tf,)):
-                raise ValueError(f"{who}: msd must be float32 cuda [total_frames]")
+        for s, (mean, var, wins, msd) in enumerate(streams):
+            _, cols = self._f32(who, "streams[%d][0]" % s, mean, tf, None, layout="any")
+            if len(wins) < 1 or cols % len(wins) != 0:
+                raise ValueError(f"{who}: streams[{s}][0] must be [total_frames][n_windows * dim]")
+            self._f32(who, "streams[%d][1]" % s, var, *((tf, cols) if var_per_frame else (cols,)), layout="any")
+            self._f32(who, "streams[%d][3]" % s, msd, tf, layout="any", optional=True)
 
         ld_mean, means, msds, keep_m = _shared_row_stride([t for t, _, _, _ in streams], [m for _, _, _, m in streams], tf)
         if var_per_frame:
@@ -1274,17 +1246,15 @@ class WorldBatch:
         dims = (C.c_int * n)(*[int(t.shape[1]) // len(w) for t, _, w, _ in streams])
         nwin, wptrs, sptrs, keep = _window_tables([wins for _, _, wins, _ in streams])
         keep += [keep_m, keep_v, vars_]
-        outs = [torch.empty(tf, int(dims[s]), dtype=torch.float32, device="cuda") for s in range(n)]
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        o = MlpgOption()
-        load_library().WorldMi355DefaultMlpgOption(C.byref(o))
-        o.edge, o.var_per_frame, o.input_type = int(edge), 1 if var_per_frame else 0, int(input_type)
-        o.unvoiced_value = float(unvoiced_value)
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        outs = [self._new(tf, int(dims[s]), dtype=torch.float32) for s in range(n)]
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
+        o = _option(who, MlpgOption, "WorldMi355DefaultMlpgOption",
+                    dict(edge=int(edge), var_per_frame=1 if var_per_frame else 0, input_type=int(input_type),
+                         unvoiced_value=float(unvoiced_value)))
         return types.SimpleNamespace(
-            n=n, means=vpn(*[ptr(t) for t in means]), ld_mean=ld_mean, vars=vpn(*[ptr(t) for t in vars_]), ld_var=ld_var,
-            dims=dims, nwin=nwin, wptrs=wptrs, sptrs=sptrs, msds=vpn(*[ptr(t) for t in msds]), opt=o,
-            out_ptrs=vpn(*[ptr(t) for t in outs]), outs=outs, status=status, keep=keep)
+            n=n, means=vpn(*[_ptr(t) for t in means]), ld_mean=ld_mean, vars=vpn(*[_ptr(t) for t in vars_]), ld_var=ld_var,
+            dims=dims, nwin=nwin, wptrs=wptrs, sptrs=sptrs, msds=vpn(*[_ptr(t) for t in msds]), opt=o,
+            out_ptrs=vpn(*[_ptr(t) for t in outs]), outs=outs, status=status, keep=keep)
 
     def parameter_generation_gv(self, streams, gv_mean, gv_var, gv_mask=None, want_info=False, var_per_frame=False,
                                 edge=0, input_type=0, unvoiced_value=-1e10, max_iter=None, epsilon=None, step_init=None,
@@ -1300,35 +1270,28 @@ class WorldBatch:
         Returns (outs, status) as parameter_generation -- status further 1 for a gv_mean or gv_var that is not positive,
         4 for a column with fewer than two GV frames or no variance, both returned as parameter_generation's -- and with
         want_info (outs, status, info float64 [n_utt][sum of dims][4]: f at the start, f at the end, trials, accepts)."""
-        import torch
-        a = self._mlpg_args("parameter_generation_gv", streams, var_per_frame, edge, input_type, unvoiced_value)
+        who = "parameter_generation_gv"
+        a = self._mlpg_args(who, streams, var_per_frame, edge, input_type, unvoiced_value)
         if len(gv_mean) != a.n or len(gv_var) != a.n:
-            raise ValueError("parameter_generation_gv: one gv_mean and one gv_var per stream")
+            raise ValueError(f"{who}: one gv_mean and one gv_var per stream")
         gvs = []
         for name, rows in (("gv_mean", gv_mean), ("gv_var", gv_var)):
             for s, t in enumerate(rows):
-                if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (int(a.dims[s]),)):
-                    raise ValueError(f"parameter_generation_gv: {name}[{s}] must be float32 cuda [{int(a.dims[s])}]")
+                self._f32(who, "%s[%d]" % (name, s), t, int(a.dims[s]), layout="any")
             gvs.append([t.contiguous() for t in rows])
-        if gv_mask is not None and not (gv_mask.is_cuda and gv_mask.dtype == torch.uint8
-                                        and tuple(gv_mask.shape) == (self.total_frames,)):
-            raise ValueError("parameter_generation_gv: gv_mask must be uint8 cuda [total_frames]")
+        check_tensor(who, "gv_mask", gv_mask, torch.uint8, (self.total_frames,), self.device, layout="any", optional=True)
         mask = None if gv_mask is None else gv_mask.contiguous()
-        g = GvOption()
-        load_library().WorldMi355DefaultGvOption(C.byref(g))
-        for key, val in (("max_iter", max_iter), ("epsilon", epsilon), ("step_init", step_init), ("step_inc", step_inc),
-                         ("step_dec", step_dec), ("hmm_weight", hmm_weight), ("gv_weight", gv_weight)):
-            if val is not None:
-                setattr(g, key, int(val) if key == "max_iter" else float(val))
-        if scale is not None:
-            g.scale = 1 if scale else 0
-        info = torch.zeros(self.n_utt, sum(int(d) for d in a.dims), 4, dtype=torch.float64, device="cuda") if want_info else None
+        num = lambda v, kind: None if v is None else kind(v)
+        g = _option(who, GvOption, "WorldMi355DefaultGvOption",
+                    dict(max_iter=num(max_iter, int), epsilon=num(epsilon, float), step_init=num(step_init, float),
+                         step_inc=num(step_inc, float), step_dec=num(step_dec, float), hmm_weight=num(hmm_weight, float),
+                         gv_weight=num(gv_weight, float), scale=num(scale, lambda v: 1 if v else 0)))
+        info = self._new(self.n_utt, sum(int(d) for d in a.dims), 4, zero=True) if want_info else None
         vpn = C.c_void_p * a.n
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
         _check(load_library().WorldMi355ParameterGenerationGv(
             self.handle, a.n, a.means, a.ld_mean, a.vars, a.ld_var, a.dims, a.nwin, a.wptrs, a.sptrs, a.msds,
-            C.byref(a.opt), vpn(*[ptr(t) for t in gvs[0]]), vpn(*[ptr(t) for t in gvs[1]]), ptr(mask), C.byref(g),
-            a.out_ptrs, ptr(info), C.c_void_p(a.status.data_ptr())), "ParameterGenerationGv")
+            C.byref(a.opt), vpn(*[_ptr(t) for t in gvs[0]]), vpn(*[_ptr(t) for t in gvs[1]]), _ptr(mask), C.byref(g),
+            a.out_ptrs, _ptr(info), _ptr(a.status)), "ParameterGenerationGv")
         return (a.outs, a.status, info) if want_info else (a.outs, a.status)
 
     def trajectory_cost(self, streams, var, gv_var, msd_weight=1.0, gv_weight=1.0e-6, want_c=True, want_grad_pred=True,
@@ -1346,28 +1309,25 @@ class WorldBatch:
         [n_utt]: bit 1 a non-finite pred or obs or a variance that is not positive and finite, bit 2 a matrix that is
         not positive definite -- such an utterance has costs 0 and gradients 0).  An output that is not wanted is
         None and is not computed."""
-        import torch
+        who = "trajectory_cost"
         n, tf = len(streams), self.total_frames
-        for pred, obs, wins, msd in streams:
-            for t in (pred, obs):
-                if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == tf and len(wins) >= 1
-                        and t.shape[1] % len(wins) == 0 and t.shape == pred.shape):
-                    raise ValueError("trajectory_cost: pred and obs must be float32 cuda [total_frames][n_windows * dim]")
-            for t in msd or ():
-                if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (tf,)):
-                    raise ValueError("trajectory_cost: a voicing column must be float32 cuda [total_frames]")
+        for s, (pred, obs, wins, msd) in enumerate(streams):
+            _, cols = self._f32(who, "streams[%d][0]" % s, pred, tf, None, layout="any")
+            self._f32(who, "streams[%d][1]" % s, obs, tf, cols, layout="any")
+            if len(wins) < 1 or cols % len(wins) != 0:
+                raise ValueError(f"{who}: pred and obs must be float32 cuda [total_frames][n_windows * dim]")
             if msd is not None and len(msd) != 2:
-                raise ValueError("trajectory_cost: msd is None or (pred column, obs column)")
+                raise ValueError(f"{who}: msd is None or (pred column, obs column)")
+            for k, t in enumerate(msd or ()):
+                self._f32(who, "streams[%d][3][%d]" % (s, k), t, tf, layout="any")
         dims = [int(p.shape[1]) // len(w) for p, _, w, _ in streams]
         at, layout = 0, []                                             # (voicing column or None, first column, columns)
         for p, _, _, msd in streams:
             layout.append((at if msd is not None else None, at + (msd is not None), int(p.shape[1])))
             at = layout[-1][1] + layout[-1][2]
         width = at
-        if not (var.is_cuda and var.dtype == torch.float32 and tuple(var.shape) == (width,)):
-            raise ValueError(f"trajectory_cost: var must be float32 cuda [{width}], got {tuple(var.shape)}")
-        if not (gv_var.is_cuda and gv_var.dtype == torch.float32 and tuple(gv_var.shape) == (sum(dims),)):
-            raise ValueError(f"trajectory_cost: gv_var must be float32 cuda [{sum(dims)}], got {tuple(gv_var.shape)}")
+        self._f32(who, "var", var, width, layout="any")
+        self._f32(who, "gv_var", gv_var, sum(dims), layout="any")
         var, gv_var = var.contiguous(), gv_var.contiguous()
         # one row stride for pred, obs and the voicing columns: as given when they share one, else packed side by side
         rows = [t for p, o, _, _ in streams for t in (p, o)]
@@ -1378,15 +1338,13 @@ class WorldBatch:
         vpn = C.c_void_p * n
         nwin, wptrs, sptrs, keep = _window_tables([wins for _, _, wins, _ in streams])
         keep += [keep_rows, var, gv_var]
-        cost = torch.zeros(self.n_utt, 3, dtype=torch.float64, device="cuda")      # a batch of zero frames launches nothing
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        c = [torch.empty(tf, d, dtype=torch.float32, device="cuda") for d in dims] if want_c else None
-        grad_pred = torch.zeros(tf, width, dtype=torch.float32, device="cuda") if want_grad_pred else None
-        grad_var = torch.zeros(self.n_utt, width, dtype=torch.float64, device="cuda") if want_grad_var else None
-        o = TrajectoryOption()
-        load_library().WorldMi355DefaultTrajectoryOption(C.byref(o))
-        o.msd_weight, o.gv_weight = float(msd_weight), float(gv_weight)
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        cost = self._new(self.n_utt, 3, zero=True)                     # a batch of zero frames launches nothing
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
+        c = [self._new(tf, d, dtype=torch.float32) for d in dims] if want_c else None
+        grad_pred = self._new(tf, width, dtype=torch.float32, zero=True) if want_grad_pred else None
+        grad_var = self._new(self.n_utt, width, zero=True) if want_grad_var else None
+        o = _option(who, TrajectoryOption, "WorldMi355DefaultTrajectoryOption",
+                    dict(msd_weight=float(msd_weight), gv_weight=float(gv_weight)))
         esz, at = 4, 0
         gv_ptrs = []
         for d in dims:
@@ -1394,45 +1352,44 @@ class WorldBatch:
             at += d
         col = lambda t, k: None if t is None or k is None else C.c_void_p(t.data_ptr() + esz * k)
         _check(load_library().WorldMi355TrajectoryCost(
-            self.handle, n, vpn(*[ptr(t) for t in rows[0::2]]), vpn(*[ptr(t) for t in rows[1::2]]), ld,
+            self.handle, n, vpn(*[_ptr(t) for t in rows[0::2]]), vpn(*[_ptr(t) for t in rows[1::2]]), ld,
             vpn(*[col(var, c0) for _, c0, _ in layout]), vpn(*gv_ptrs), (C.c_int * n)(*dims),
             nwin, wptrs, sptrs,
-            vpn(*[ptr(m and m[0]) for m in msds]), vpn(*[ptr(m and m[1]) for m in msds]),
-            vpn(*[col(var, mc) for mc, _, _ in layout]), C.byref(o), ptr(cost),
-            None if c is None else vpn(*[ptr(t) for t in c]),
+            vpn(*[_ptr(m and m[0]) for m in msds]), vpn(*[_ptr(m and m[1]) for m in msds]),
+            vpn(*[col(var, mc) for mc, _, _ in layout]), C.byref(o), _ptr(cost),
+            None if c is None else vpn(*[_ptr(t) for t in c]),
             None if grad_pred is None else vpn(*[col(grad_pred, c0) for _, c0, _ in layout]),
-            None if grad_pred is None else vpn(*[col(grad_pred, mc) for mc, _, _ in layout]), width, ptr(grad_var),
-            ptr(status)), "TrajectoryCost")
+            None if grad_pred is None else vpn(*[col(grad_pred, mc) for mc, _, _ in layout]), width, _ptr(grad_var),
+            _ptr(status)), "TrajectoryCost")
         return cost, c, grad_pred, grad_var, status
 
+    def _model_rows(self, who, name, t, width):
+        """float32 [total_frames][width] passed by its row stride, a view whose strides do not fit copied first:
+        (the tensor to keep alive, its pointer, its row stride)."""
+        self._f32(who, name, t, self.total_frames, width, layout="any")
+        if t.stride(1) != 1 or (self.total_frames > 1 and t.stride(0) < width):
+            t = t.contiguous()
+        return (t,) + self._f32(who, name, t, self.total_frames, width, layout="rows")
+
+    def _model_tensor(self, who, name, t, shape, keep):
+        """A parameter of the model, float32 of `shape`: the address of its detached contiguous self, kept in `keep`."""
+        self._f32(who, name, t, *shape, layout="any")
+        keep.append(t.detach().contiguous())
+        return keep[-1].data_ptr()
+
     def _acoustic_model_args(self, who, model, x, spkr, obs, max_chunk_frames):
-        """What the three acoustic-model calls share: (descriptor, what it points to, the row-argument checker, x, ld_x,
-        obs, ld_obs, spkr array, (n_in, units, n_out, n_spkrs, sat))."""
-        import torch
+        """What the three acoustic-model calls share: (descriptor, what it points to, x's pointer, ld_x, obs' pointer or
+        None, ld_obs, spkr pointer or None, (n_in, units, n_out, n_spkrs, sat))."""
         m = model.kernel_args() if hasattr(model, "kernel_args") else model
-        tf = self.total_frames
         code = lambda a: ACTIVATIONS.index(a) if isinstance(a, str) else int(a)
         keep = []
-
-        def dev(t, shape, what):
-            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)):
-                raise ValueError(f"{who}: {what} must be float32 cuda {list(shape)}, got {tuple(t.shape)}")
-            t = t.detach().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        def rows(t, width, what):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and tuple(t.shape) == (tf, width)):
-                raise ValueError(f"{who}: {what} must be float32 cuda [{tf}][{width}]")
-            if tf > 0 and (t.stride(1) != 1 or (tf > 1 and t.stride(0) < width)):
-                t = t.contiguous()
-            keep.append(t)
-            return t, int(t.stride(0)) if tf > 1 else width
-
+        dev = lambda t, shape, what: self._model_tensor(who, "model." + what, t, shape, keep)
         weights, biases = list(m["weights"]), list(m["biases"])
         n_layers = len(weights) - 1
-        if n_layers < 0 or len(biases) != n_layers + 1 or weights[-1].dim() != 2 or any(w.dim() != 2 for w in weights):
+        if n_layers < 0 or len(biases) != n_layers + 1:
             raise ValueError(f"{who}: weights and biases are n_layers + 1 matrices and vectors")
+        for i, w in enumerate(weights):
+            self._f32(who, "model.weights[%d]" % i, w, None, None, layout="any")
         n_in, n_out, n_spkrs = int(weights[0].shape[0]), int(weights[-1].shape[1]), int(m.get("n_spkrs", 1))
         units = [int(w.shape[1]) for w in weights[:-1]]
         fan = [n_in] + units
@@ -1456,18 +1413,21 @@ class WorldBatch:
         if var is not None:
             d.variances = dev(var, (n_spkrs, n_out), "variances")
         d.max_chunk_frames = int(max_chunk_frames)
-        x, ld_x = rows(x, n_in, "x")
-        ld_obs = 0
+        x, xp, ld_x = self._model_rows(who, "x", x, n_in)
+        op, ld_obs = None, 0
         if obs is not None:
             if var is None:
                 raise ValueError(f"{who}: a cost needs the model's variances")
-            obs, ld_obs = rows(obs, n_out, "obs")
+            obs, op, ld_obs = self._model_rows(who, "obs", obs, n_out)
         sp = None
         if spkr is not None:
             sp = np.ascontiguousarray(spkr, dtype=np.int32)
             if sp.shape != (self.n_utt,):
                 raise ValueError(f"{who}: spkr has one index per utterance ({self.n_utt})")
-        return d, keep, rows, x, ld_x, obs, ld_obs, sp, (n_in, units, n_out, n_spkrs, sd is not None)
+            keep.append(sp)
+            sp = sp.ctypes.data_as(C.c_void_p)
+        keep += [x, obs]
+        return d, keep, xp, ld_x, op, ld_obs, sp, (n_in, units, n_out, n_spkrs, sd is not None)
 
     def acoustic_model_forward(self, model, x, spkr=None, obs=None, max_chunk_frames=0):
         """The forward pass of the recipe's acoustic model (DNNDefine.inference as DNNSynthesis.py runs it) and, with
@@ -1481,18 +1441,7 @@ class WorldBatch:
         utterance.  Returns (out float32 [total_frames][n_outputs], cost float64 [n_utt] or None without obs, status
         int32 [n_utt]: bit 1 a non-finite x or obs, bit 2 a non-finite output or, with a cost, a variance that is not
         positive and finite -- such an utterance has zero rows and cost 0)."""
-        import torch
-        d, keep, _, x, ld_x, obs, ld_obs, sp, (_, _, n_out, _, _) = self._acoustic_model_args(
-            "acoustic_model_forward", model, x, spkr, obs, max_chunk_frames)
-        tf = self.total_frames
-        out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda")
-        cost = torch.zeros(self.n_utt, dtype=torch.float64, device="cuda") if obs is not None else None
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        _check(load_library().WorldMi355AcousticModelForward(
-            self.handle, C.byref(d), ptr(x), ld_x, None if sp is None else sp.ctypes.data_as(C.c_void_p), ptr(out), n_out,
-            ptr(obs), ld_obs, ptr(cost), ptr(status)), "AcousticModelForward")
-        return out, cost, status
+        return self._model_forward("acoustic_model_forward", model, x, spkr, obs, max_chunk_frames)
 
     def acoustic_model_train_forward(self, model, x, spkr=None, obs=None, keep_prob=1.0, seed=0, offset=0, want_grads=False,
                                      max_chunk_frames=0):
@@ -1501,23 +1450,28 @@ class WorldBatch:
         frame-level cost.  Returns (out, cost or None, status), and with want_grads (obs is then required)
         (out, cost, status, grad_out float32 [total_frames][n_outputs], grad_var float64 [n_utt][n_outputs]): the
         gradients of every utterance's own cost.  With keep_prob 1 out equals acoustic_model_forward's bit for bit."""
-        import torch
-        d, keep, _, x, ld_x, obs, ld_obs, sp, (_, _, n_out, _, _) = self._acoustic_model_args(
-            "acoustic_model_train_forward", model, x, spkr, obs, max_chunk_frames)
-        if want_grads and obs is None:
-            raise ValueError("acoustic_model_train_forward: the cost gradients need obs")
-        tf = self.total_frames
         drop = Dropout(float(keep_prob), int(seed) & 0xffffffffffffffff, int(offset) & 0xffffffff)
-        out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda")
-        cost = torch.zeros(self.n_utt, dtype=torch.float64, device="cuda") if obs is not None else None
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
-        grad_out = torch.zeros(tf, n_out, dtype=torch.float32, device="cuda") if want_grads else None
-        grad_var = torch.zeros(self.n_utt, n_out, dtype=torch.float64, device="cuda") if want_grads else None
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        return self._model_forward("acoustic_model_train_forward", model, x, spkr, obs, max_chunk_frames, drop, want_grads)
+
+    def _model_forward(self, who, model, x, spkr, obs, max_chunk_frames, drop=None, want_grads=False):
+        """The two forward passes: the inference call without `drop`, the training call with it."""
+        d, keep, xp, ld_x, op, ld_obs, sp, (_, _, n_out, _, _) = self._acoustic_model_args(who, model, x, spkr, obs,
+                                                                                          max_chunk_frames)
+        if want_grads and obs is None:
+            raise ValueError(f"{who}: the cost gradients need obs")
+        tf = self.total_frames
+        out = self._new(tf, n_out, dtype=torch.float32, zero=True)
+        cost = self._new(self.n_utt, zero=True) if obs is not None else None
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
+        if drop is None:
+            _check(load_library().WorldMi355AcousticModelForward(self.handle, C.byref(d), xp, ld_x, sp, _ptr(out), n_out, op,
+                                                                 ld_obs, _ptr(cost), _ptr(status)), "AcousticModelForward")
+            return out, cost, status
+        grad_out = self._new(tf, n_out, dtype=torch.float32, zero=True) if want_grads else None
+        grad_var = self._new(self.n_utt, n_out, zero=True) if want_grads else None
         _check(load_library().WorldMi355AcousticModelTrainForward(
-            self.handle, C.byref(d), C.byref(drop), ptr(x), ld_x, None if sp is None else sp.ctypes.data_as(C.c_void_p),
-            ptr(out), n_out, ptr(obs), ld_obs, ptr(cost), ptr(grad_out), n_out, ptr(grad_var), ptr(status)),
-            "AcousticModelTrainForward")
+            self.handle, C.byref(d), C.byref(drop), xp, ld_x, sp, _ptr(out), n_out, op, ld_obs, _ptr(cost), _ptr(grad_out),
+            n_out, _ptr(grad_var), _ptr(status)), "AcousticModelTrainForward")
         if want_grads:
             return out, cost, status, grad_out, grad_var
         return out, cost, status
@@ -1529,26 +1483,24 @@ class WorldBatch:
         output.si_biases; float32 cuda, shaped as the parameters), and under "status" the int32 [n_utt] mask: bit 1 a
         non-finite x or grad_out, bit 2 a non-finite output -- such an utterance adds exact zeros.  grad_out: float32 cuda
         [total_frames][n_outputs], or a column view."""
-        import torch
-        d, keep, rows, x, ld_x, _, _, sp, (n_in, units, n_out, n_spkrs, sat) = self._acoustic_model_args(
-            "acoustic_model_backward", model, x, spkr, None, max_chunk_frames)
-        g, ld_g = rows(grad_out, n_out, "grad_out")
+        who = "acoustic_model_backward"
+        d, keep, xp, ld_x, _, _, sp, (n_in, units, n_out, n_spkrs, sat) = self._acoustic_model_args(
+            who, model, x, spkr, None, max_chunk_frames)
+        g, gp, ld_g = self._model_rows(who, "grad_out", grad_out, n_out)
         drop = Dropout(float(keep_prob), int(seed) & 0xffffffffffffffff, int(offset) & 0xffffffff)
         n_layers = len(units)
         fan, wid = [n_in] + units, units + [n_out]
         names = ["hidden%d" % i for i in range(n_layers)] + ["output"]
-        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device="cuda")
+        z = lambda *shape: self._new(*shape, dtype=torch.float32, zero=True)
         gw = [z(fan[i], wid[i]) for i in range(n_layers + 1)]
         gb = [z(wid[i]) for i in range(n_layers + 1)]
         gs = [z(n_spkrs, units[i]) for i in range(n_layers)] if sat else None
-        status = torch.zeros(self.n_utt, dtype=torch.int32, device="cuda")
+        status = self._new(self.n_utt, dtype=torch.int32, zero=True)
         arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
         wa, ba = arr(gw), arr(gb)
         sa = arr(gs) if sat else None
-        _check(load_library().WorldMi355AcousticModelBackward(
-            self.handle, C.byref(d), C.byref(drop), C.c_void_p(x.data_ptr()), ld_x,
-            None if sp is None else sp.ctypes.data_as(C.c_void_p), C.c_void_p(g.data_ptr()), ld_g, wa, ba, sa,
-            C.c_void_p(status.data_ptr())), "AcousticModelBackward")
+        _check(load_library().WorldMi355AcousticModelBackward(self.handle, C.byref(d), C.byref(drop), xp, ld_x, sp, gp, ld_g,
+                                                              wa, ba, sa, _ptr(status)), "AcousticModelBackward")
         res = {"status": status}
         for i, k in enumerate(names):
             res[k + ".si_weights"], res[k + ".si_biases"] = gw[i], gb[i]
@@ -1607,8 +1559,8 @@ def mspf_segment_frames() -> int:
 
 def write_files(items, threads=16):
     """items: [(path, numpy array)] -- every array written raw to its path by native threads in ONE library call
-    (WorldMi355WriteFiles: the interpreter lock is released for its duration).  The arrays must be C-contiguous and
-    stay alive until the call returns (they do: it is synchronous).  Host only."""
+    (WorldMi355WriteFiles: the interpreter lock is released for its duration).  The arrays must be C-contiguous
+    (ValueError) and stay alive until the call returns (they do: it is synchronous).  Host only."""
     n = len(items)
     if n == 0:
         return
@@ -1616,7 +1568,8 @@ def write_files(items, threads=16):
     ptrs = (C.c_void_p * n)()
     sizes = (C.c_size_t * n)()
     for k, (_, a) in enumerate(items):
-        assert a.flags["C_CONTIGUOUS"], "write_files: contiguous arrays only"
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"write_files: the array for {items[k][0]} is not C-contiguous")
         ptrs[k] = a.ctypes.data
         sizes[k] = a.nbytes
     _check(load_library().WorldMi355WriteFiles(n, paths, ptrs, sizes, int(threads)), "WriteFiles")

@@ -82,7 +82,7 @@ def test_native_file_writer(tmp_path):
         assert p.read_bytes() == b
     with pytest.raises(RuntimeError, match="no_such_dir"):
         W.write_files([(tmp_path / "no_such_dir" / "a.f0", slab[:3])], threads=2)
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError):
         W.write_files([(tmp_path / "t.f0", slab[:, 0])])   # a column of a slab is not contiguous
 
 
