@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+import codec_features as cf
 import synth_features as sf
 
 sd = importlib.import_module("hts-train-world_amd.synth_data")
@@ -181,6 +182,31 @@ def test_codec_vs_reference_vectors(oracle, name):
     np.testing.assert_array_equal(lf0, g["lf0"])
     np.testing.assert_allclose(mgc, g["mgc"], atol=2e-6, rtol=0)
     np.testing.assert_allclose(bap, g["bap"], atol=2e-6, rtol=0)
+
+
+@pytest.fixture(scope="module")
+def codec_handmade():
+    return np.load(os.path.join(GOLDEN, "codec_handmade.npz"))
+
+
+@pytest.mark.parametrize("k,case", list(enumerate(cf.golden_subset())), ids=lambda v: cf.case_id(v) if isinstance(v, tuple) else "")
+def test_codec_on_hand_made_rows_vs_reference_vectors(oracle, codec_handmade, k, case):
+    """The feature codec on the hand-made rows of tests/codec_features.py against what the compiled reference gave on
+    them (oracle/gen_golden_codec_handmade.py): coded outputs whole, decoded ones at every 8th bin, at the bounds of
+    tests/test_oracle_vs_ref.py, non-finite values in the same places.  The inputs' own check sums come first, so that
+    a drift of the generator shows as such."""
+    g = codec_handmade
+    assert str(g["cases"][k]) == cf.case_id(case) and len(g["cases"]) == len(cf.golden_subset())
+    chk = cf.input_check(case)
+    np.testing.assert_array_equal(chk, g["in_check"][k][:len(chk)])
+    outs = cf.outputs(oracle, case)
+    a, e = int(g["first"][k]), int(g["first"][k + 1])
+    assert e - a == len(outs)
+    for i, (got, bound) in enumerate(zip(outs, cf.ORACLE_BOUNDS[case[0]])):
+        got = cf.golden_view(case, i, got)
+        want = g["out"][int(g["offset"][a + i]):int(g["offset"][a + i + 1])].reshape(got.shape)
+        assert tuple(g["shape"][a + i]) == (got.shape + (1,))[:2]
+        assert cf.hold(got, want.astype(got.dtype), bound), "non-finite values in other places"
 
 
 CMP_WINDOWS = [[1.0], [-0.5, 0.0, 0.5], [1.0, -2.0, 1.0]]          # data/win/*.win1..3

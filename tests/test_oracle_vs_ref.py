@@ -5,6 +5,7 @@ import importlib
 import numpy as np
 import pytest
 
+import codec_features as cf
 import synth_features as sf
 
 sd = importlib.import_module("hts-train-world_amd.synth_data")
@@ -216,3 +217,38 @@ def test_synthesis_on_hand_made_features(oracle, reference, case):
     yo = oracle.synthesis(f0, sp, ap, F, fp, fs, n)
     assert np.isfinite(yr).all()
     np.testing.assert_allclose(yo, yr, atol=1e-9 * max(1.0, np.abs(yr).max()), rtol=0)
+
+
+# grid entries of tests/codec_features.py on which oracle and compiled reference put non-finite values in different
+# places (none on the present grid); tests/test_gpu_codec_features.py then asserts row isolation alone for them
+CODEC_MASK_DISAGREE = frozenset()
+
+
+@pytest.fixture(scope="module")
+def sptk():
+    from oracle.bindings import SptkReference
+    if not SptkReference.available():
+        pytest.skip("oracle/_ref/libsptk_ref.so not built")
+    return SptkReference()
+
+
+@pytest.mark.parametrize("case", cf.grid(), ids=cf.case_id)
+def test_codec_on_hand_made_rows(oracle, reference, sptk, case):
+    """The feature codec on rows that no analysis produces (tests/codec_features.py: rough, spiked, flat, denormal, zero
+    and overflowing envelopes, aperiodicities at their ends and around the recipe's snap of bap's coefficient 0, coded
+    rows from 1e-250 to 1e250, band rows on CheckVUV's gate, every width the kernels switch at), full arrays, at this
+    file's bounds for the codec.  Non-finite values must sit in the same places."""
+    kind = case[0]
+    got, want = cf.outputs(oracle, case), cf.outputs(reference, case, sptk.mgc2sp)
+    held = [cf.hold(g, w, bound) for g, w, bound in zip(got, want, cf.ORACLE_BOUNDS[kind])]
+    assert len(held) == len(got) == len(want)
+    assert (not all(held)) == (cf.case_id(case) in CODEC_MASK_DISAGREE)
+    if kind == "recipe_decode":                                     # the systolic freqt's model: bit for bit
+        F = case[3]
+        for row in cf.bap_rows(cf.inputs(case)[2]):
+            np.testing.assert_array_equal(oracle.freqt(row, F // 2, -0.55), sptk.freqt(row, F // 2, -0.55))
+        f0, sp, ap = oracle.recipe_decode(*cf.inputs(case), case[2], F)
+        order = got[2].shape[1]
+        assert np.array_equal(f0, got[0]) and np.array_equal(sp, got[1])          # the whole call is its parts
+        np.testing.assert_allclose(ap[:, :order], np.exp(got[2]) / 1e4, rtol=1e-15, atol=0)   # numpy's exp, libm's
+        assert not ap[:, order:].any()
