@@ -283,7 +283,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa, dtw;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa, dtw, modify;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -437,6 +437,11 @@ int launch_optimizer_step(Context& c, hipStream_t st, const WorldMi355OptimizerO
 int check_mcpf(const double* d_mc, const WorldMi355McpfOption* opt, const double* d_out);
 int launch_mcpf(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355McpfOption& opt, double* d_out,
                 double* d_gain, int* d_status);
+// modify.hip: F0 scaling and formant shift between analysis and synthesis; the factor arrays are HOST, one per utterance
+int check_modify(const Batch& b, const double* f0_scale, const double* formant_ratio, const double* d_f0,
+                 const double* d_sp, const double* d_f0_out, const double* d_sp_out);
+int launch_modify(Batch& b, hipStream_t st, const double* f0_scale, const double* formant_ratio, const double* d_f0,
+                  const double* d_sp, double* d_f0_out, double* d_sp_out);
 int check_column_means(const double* d_x, int dim, const double* d_mean);
 int launch_column_means(Batch& b, hipStream_t st, const double* d_x, int dim, double* d_mean);
 int check_mspf(const double* d_x, int dim, const WorldMi355MspfOption* opt, const double* mean_gen, const double* std_gen,

@@ -527,6 +527,12 @@ int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const 
   if (const int rc = check_mcpf(mc, opt, out)) return rc;                       // refused before any device call
   return on_batch(b, launch_mcpf, mc, *opt, out, gain, status);
 }
+int WorldMi355ModifyFeatures(WorldMi355Batch* b, const double* f0_scale, const double* formant_ratio, const double* f0,
+                             const double* sp, double* f0_out, double* sp_out) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_modify(b->b, f0_scale, formant_ratio, f0, sp, f0_out, sp_out)) return rc;   // before any device call
+  return on_batch(b, launch_modify, f0_scale, formant_ratio, f0, sp, f0_out, sp_out);
+}
 void WorldMi355DefaultMspfOption(WorldMi355MspfOption* o) {                     // the recipe's $mspfLength, $mspfFFTLen, $mspfe{'mgc'}
   if (!o) return;
   o->frame_length = 25;

@@ -29,7 +29,7 @@ import sys
 
 import numpy as np
 
-from . import recipe as R, world as W
+from . import modify as M, recipe as R, world as W
 
 SYNTHESIS_STREAMS = ("mgc", "lf0", "bap")            # what recipe_decode and synthesize take; any other stream is returned only
 FFT_SIZES = (512, 1024, 2048, 4096)                  # the sizes recipe_decode and synthesize are built for
@@ -86,7 +86,7 @@ class _Setup:
     """The arguments of Generator, checked and loaded on the host: nothing here opens a context or touches a device."""
 
     def __init__(self, config, frame_shift, model, spkr=None, streams=(), fs=48000, frame_period=5.0, fft_size=2048,
-                 alpha=0.55, postfilter=None, edge=0, unvoiced_value=-1.0e10):
+                 alpha=0.55, postfilter=None, edge=0, unvoiced_value=-1.0e10, f0_scale=None, formant_ratio=None):
         from . import training
         self.names, self.features = R.read_question_config(config) if isinstance(config, (str, os.PathLike)) else config
         nf = len(self.features)
@@ -126,6 +126,13 @@ class _Setup:
                 int(fft_size), FFT_SIZES[0], FFT_SIZES[-1], ", ".join(str(f) for f in FFT_SIZES)))
         self.fs, self.frame_period, self.fft_size = int(fs), float(frame_period), int(fft_size)
         self.alpha, self.edge, self.unvoiced_value = float(alpha), int(edge), float(unvoiced_value)
+        for name, v in (("f0_scale", f0_scale), ("formant_ratio", formant_ratio)):
+            if v is not None and np.ndim(v) != 0:
+                raise ValueError("%s is one number for every utterance, got %r" % (name, v))
+        M.factor_array("generate", "f0_scale", f0_scale, 1)
+        M.factor_array("generate", "formant_ratio", formant_ratio, 1, self.fft_size)
+        self.f0_scale = None if f0_scale is None else float(f0_scale)
+        self.formant_ratio = None if formant_ratio is None else float(formant_ratio)
         if postfilter is not None and postfilter[0] == "gv":
             self.postfilter, self.tables = self._gv(postfilter, [d for d, _, _ in self.streams])
         else:
@@ -217,6 +224,8 @@ class Generator:
                  --, or ("gv", gv_mean, gv_var, options) -- gen_param_gv_files' generation in MLPG's place and, as gen_wave
                  does with GV generation on, no postfilter after it; its status is the status word's mlpg field
     edge, unvoiced_value: as gen_param_files
+    f0_scale, formant_ratio: None, or a pitch and a formant knob (modify.modify_features) on the decoded f0 and spectral
+                 envelope, between recipe_decode and synthesize; with both None no such call is made
     ctx:         a world.Context, or None for one of its own (closed by close()).  The casts between the library's calls
                  are torch's: with a context on a caller's stream, call with that stream as torch's current one.
 
@@ -286,6 +295,8 @@ class Generator:
                 out, st_post = b.postfilter_modulation_spectrum(gen["mgc"].double(), *s.tables, *s.postfilter[1:])
                 p_mgc = out.float()
             f0, sp, ap = b.recipe_decode(gen["lf0"].reshape(-1), gen["mgc"] if p_mgc is None else p_mgc, gen["bap"])
+            if s.f0_scale is not None or s.formant_ratio is not None:                               # test.cpp:201-238
+                f0, sp = M.modify_features(b, f0, sp, s.f0_scale, s.formant_ratio, out=(f0, sp))
             y = b.synthesize(f0, sp, ap)                                                            # synth_files
             del f0, sp, ap
             samples = b.samples_to_pcm16(y) if pcm else None
@@ -307,7 +318,7 @@ class Generator:
 
 def generate_files(jobs, config, frame_shift, model, spkr=None, streams=(), fs=48000, frame_period=5.0, fft_size=2048,
                    alpha=0.55, postfilter=None, edge=0, unvoiced_value=-1.0e10, ctx=None, keep_dir=None,
-                   max_batch_frames=R.MAX_BATCH_FRAMES, io_threads=8, resume=False):
+                   max_batch_frames=R.MAX_BATCH_FRAMES, io_threads=8, resume=False, f0_scale=None, formant_ratio=None):
     """Labels to wavs for a file list: ffi_files, forward_files, gen_param_files, postfilter_files or mspf_files, and
     synth_files as one pass per batch (Generator, whose arguments these are), with no file between them.
 
@@ -316,6 +327,7 @@ def generate_files(jobs, config, frame_shift, model, spkr=None, streams=(), fs=4
               file's base name: <base>.ffi, <base>.ffo, <base>.var, <base>.<stream> for every stream, and <base>.p_mgc
               when a postfilter ran
     resume:   skip a job whose wav exists with the size write_wav gives its samples (wav_complete)
+    f0_scale, formant_ratio: Generator's; the kept files are the unmodified features' either way
     Rank-sharded by frame count.  An utterance flagged by the forward pass, MLPG or the postfilter is reported on stderr
     with the stage's name and gets no wav (its kept files are written, flagged rows being zeros as the stages leave them);
     the ffi warnings are counted as ffi_files counts them.  Every argument is checked before a context is opened.
@@ -324,7 +336,7 @@ def generate_files(jobs, config, frame_shift, model, spkr=None, streams=(), fs=4
     if any(len(j) != 2 for j in jobs):
         raise ValueError("generate_files: a job is (label_file, wav_out)")
     setup = _Setup(config, frame_shift, model, spkr, streams, fs, frame_period, fft_size, alpha, postfilter, edge,
-                   unvoiced_value)
+                   unvoiced_value, f0_scale, formant_ratio)
     labels = [R.read_label(j[0], setup.frame_shift) for j in jobs]
     frames = label_frames(labels, [j[0] for j in jobs])
     mine = R._my_jobs(frames, lambda i: not (resume and wav_complete(jobs[i][1], frames[i], setup.frame_period, setup.fs)))

@@ -57,6 +57,10 @@ scripts/Training.pl:1402-1491).  ffi_files() / `ffi` writes the other side of th
 input rows from aligned labels and a question config (make_train_data_dnn / make_gen_data_dnn, :1677-1723:
 data/scripts/makefeature.pl and x2x +af), which `dnn-train`, `dnn-forward` and `trj-eval` read.
 
+modify_files() / `modify` is the reference's own example program (test/test.cpp: `test in.wav out.wav [f0_scale
+[formant_ratio]]`) for a file list: analysis, F0 scaling and formant shift (modify.py, test.cpp:201-238), synthesis, wav
+to wav on the device.
+
 generate_files() / `generate` (generate.py) is the way back in one pass: `ffi`, `dnn-forward`, `gen-param`, the postfilter
 and `synth` on one device-resident batch, labels in and wavs out, with the staged commands' bytes.
 
@@ -415,6 +419,98 @@ def synth_files(jobs, frame_period, fft_size, fs, spec_dim=0, ap_dim=24, ctx=Non
                 yo = b.out_offsets
                 for k, i in enumerate(group):
                     stage.submit(write_wav, jobs[i][3], y[yo[k]:yo[k + 1]], fs)
+    return stage.frames
+
+
+# ---- voice modification (test/test.cpp: analysis, ParameterModification :201-238, synthesis) ------------------------
+MODIFY_D4C_THRESHOLD = 0.85           # InitializeD4COption's, which test.cpp:180-199 leaves as it is (analysis.cpp sets 0)
+
+
+def read_modify_list(path, f0_scale=None, formant_ratio=None):
+    """Lines `in.wav out.wav [f0_scale [formant_ratio]]`, test.cpp's argument order, as jobs (in, out, f0_scale,
+    formant_ratio): a value the line leaves out is the argument's, and None -- "not done" -- without one."""
+    jobs = []
+    with open(path) as f:
+        for ln in f:
+            w = ln.split()
+            if not w or ln.startswith("#"):
+                continue
+            if not 2 <= len(w) <= 4:
+                raise ValueError("a line is `in.wav out.wav [f0_scale [formant_ratio]]`: %r" % ln.strip())
+            try:
+                given = [float(v) for v in w[2:]]
+            except ValueError:
+                raise ValueError("a factor is a number: %r" % ln.strip()) from None
+            jobs.append((w[0], w[1], given[0] if len(given) > 0 else f0_scale, given[1] if len(given) > 1 else formant_ratio))
+    return jobs
+
+
+def modify_params(fs, frame_period=5.0, f0_floor=71.0, f0_ceil=800.0, d4c_threshold=MODIFY_D4C_THRESHOLD):
+    """test.cpp's analysis settings: the CLI's (analysis_params) but for D4C's threshold."""
+    p = analysis_params(fs, frame_period, f0_floor, f0_ceil)
+    p.d4c_threshold = float(d4c_threshold)
+    return p
+
+
+def modify_samples(n_samples, fs, frame_period):
+    """Samples of the wav made from one of n_samples: the batch's own y_length of its frame count (test.cpp:329-330)."""
+    return int((sharding.frame_count(n_samples, fs, frame_period) - 1) * frame_period / 1000.0 * fs) + 1
+
+
+def _put_wav16(path, pcm, fs):
+    n = len(pcm)
+    head = b"RIFF" + struct.pack("<I", 36 + n * 2) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, fs, fs * 2, 2, 16)
+    _put(path, pcm, head + b"data" + struct.pack("<I", n * 2))
+
+
+def _read_pcm16(path):
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2:
+            raise ValueError("%s: modify takes 16-bit samples, the file has %d-bit ones" % (path, 8 * w.getsampwidth()))
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+
+
+def modify_files(jobs, frame_period=5.0, f0_estimator="dio", f0_floor=71.0, f0_ceil=800.0,
+                 d4c_threshold=MODIFY_D4C_THRESHOLD, ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8,
+                 resume=False):
+    """jobs: [(wav_in, wav_out, f0_scale, formant_ratio)], a factor of None meaning "not done" (read_modify_list).
+    Writes what `test wav_in wav_out f0_scale formant_ratio` writes, with the f0 estimator named here in front:
+    samples_from_pcm16, modify.convert (analyze, modify_features, synthesize), samples_to_pcm16, all on the device.
+    A batch holds utterances of one sampling rate that give the same parts (a factor array covers a whole batch);
+    rank-sharded by frame count; with resume a job whose wav_out has exactly the size of its result is skipped.
+    Every factor is checked before a context is opened (ValueError).  Returns the frames converted by this rank."""
+    import torch  # noqa: F401 -- ahead of the first call into the library (analysis_files says why)
+    from . import modify as M
+    jobs = [tuple(j) for j in jobs]
+    if any(len(j) != 4 for j in jobs):
+        raise ValueError("modify_files: a job is (wav_in, wav_out, f0_scale, formant_ratio)")
+    W.f0_estimator_code(f0_estimator)
+    with ThreadPoolExecutor(io_threads) as pool:
+        heads = list(pool.map(lambda j: wav_header(j[0]), jobs))
+    for j, (_, fs) in zip(jobs, heads):
+        M.factor_array(j[0], "f0_scale", j[2], 1)
+        M.factor_array(j[0], "formant_ratio", j[3], 1, capi.cheaptrick_fft_size(fs))
+    frames = [sharding.frame_count(n, fs, frame_period) for n, fs in heads]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 44 + 2 * modify_samples(heads[i][0], heads[i][1],
+                                                                                                   frame_period))))
+    if not mine:
+        return 0
+    kind = lambda i: (heads[i][1], jobs[i][2] is not None, jobs[i][3] is not None)
+    with _Stage(ctx, io_threads) as stage:
+        for fs, do_f0, do_sp in sorted({kind(i) for i in mine}):
+            params = modify_params(fs, frame_period, f0_floor, f0_ceil, d4c_threshold)
+            for group in analysis_plan([i for i in mine if kind(i) == (fs, do_f0, do_sp)], frames, [h[0] for h in heads],
+                                       max_batch_frames, params, f0_estimator):
+                pcm = list(stage.pool.map(lambda i: _read_pcm16(jobs[i][0]), group))
+                with stage.batch(params, x_lengths=[len(a) for a in pcm], f0_estimator=f0_estimator) as b:
+                    x = b.samples_from_pcm16(_upload(np.concatenate(pcm), pinned=True))
+                    del pcm
+                    y = M.convert(b, x, [jobs[i][2] for i in group] if do_f0 else None,
+                                  [jobs[i][3] for i in group] if do_sp else None)
+                    out = b.samples_to_pcm16(y).cpu().numpy()
+                    yo = b.out_offsets
+                    for k, i in enumerate(group):
+                        stage.submit(_put_wav16, jobs[i][1], out[yo[k]:yo[k + 1]], int(fs))
     return stage.frames
 
 
@@ -2064,7 +2160,8 @@ def generate_arguments(ap, a):
         ap.error("--frame-shift must be positive")
     return dict(config=a.config, frame_shift=a.frame_shift, model=a.model, spkr=a.spkr, streams=a.stream, fs=a.fs,
                 frame_period=a.frame_period, fft_size=a.fft_size, alpha=a.alpha, postfilter=post, edge=a.edge,
-                unvoiced_value=a.unvoiced_value, keep_dir=a.keep_dir, max_batch_frames=a.max_batch_frames, resume=a.resume)
+                unvoiced_value=a.unvoiced_value, keep_dir=a.keep_dir, max_batch_frames=a.max_batch_frames, resume=a.resume,
+                f0_scale=a.f0_scale, formant_ratio=a.formant_ratio)
 
 
 def __getattr__(name):
@@ -2096,6 +2193,17 @@ def main(argv=None):
             p.add_argument("--f0-ceil", type=float, default=800.0, help="upper end of the estimator's search range in Hz")
         if name == "synth":
             p.add_argument("--fs", type=int, required=True)
+    p = sub.add_parser("modify", help="test.cpp for a file list: analysis, F0 scaling and formant shift, synthesis")
+    p.add_argument("--scp", required=True, help="job list: in.wav out.wav [f0_scale [formant_ratio]] per line")
+    p.add_argument("--f0-scale", type=float, default=None, help="for the lines that give none (default: not done)")
+    p.add_argument("--formant-ratio", type=float, default=None, help="for the lines that give none (default: not done)")
+    p.add_argument("--frame-period", type=float, default=5.0)
+    p.add_argument("--f0", choices=W.F0_ESTIMATORS, default="dio", help="the f0 estimator in front of the chain")
+    p.add_argument("--f0-floor", type=float, default=71.0, help="lower end of the estimator's search range in Hz")
+    p.add_argument("--f0-ceil", type=float, default=800.0, help="upper end of the estimator's search range in Hz")
+    p.add_argument("--d4c-threshold", type=float, default=MODIFY_D4C_THRESHOLD, help="D4C's voicing threshold (test.cpp's)")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose output wav is already complete")
+    p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
     p = sub.add_parser("gen-param", help="gen_param: mlpg on every stream of a list of ffo files")
     p.add_argument("--scp", required=True, help="job list: the ffo file, then one output path per stream")
     p.add_argument("--stream", action="append", required=True, type=parse_stream, metavar="DIM:MSD:WIN0,WIN1,...",
@@ -2293,6 +2401,9 @@ def main(argv=None):
                    "one file per stream and .p_mgc")
     p.add_argument("--resume", action="store_true", help="skip utterances whose wav is already complete")
     p.add_argument("--max-batch-frames", type=int, default=MAX_BATCH_FRAMES)
+    p.add_argument("--f0-scale", type=float, default=None, help="multiply the generated f0 by this ahead of synthesis")
+    p.add_argument("--formant-ratio", type=float, default=None, help="stretch the generated spectral envelope along the "
+                   "frequency axis by this ahead of synthesis")
     p = sub.add_parser("evaluate", help="objective measures of generated against natural feature files: mel-cepstral "
                        "distortion, lf0 RMSE, V/UV error, along a DTW path or by truncation")
     p.add_argument("--scp", required=True, help="job list: per --stream in order the generated then the natural file, and the "
@@ -2333,6 +2444,15 @@ def main(argv=None):
                 with open(a.per_utterance, "w") as f:
                     f.write("".join(ln + "\n" for ln in lines))
             print(json.dumps(obj))
+        return 0
+    if a.cmd == "modify":
+        try:
+            jobs = read_modify_list(a.scp, a.f0_scale, a.formant_ratio)
+            n = modify_files(jobs, a.frame_period, a.f0, a.f0_floor, a.f0_ceil, a.d4c_threshold,
+                             max_batch_frames=a.max_batch_frames, resume=a.resume)
+        except ValueError as err:
+            ap.error(str(err))
+        print("complete. %d frames" % n)
         return 0
     if a.cmd == "generate":
         from . import generate

@@ -329,6 +329,7 @@ def load_library():
     L.WorldMi355DefaultMcpfOption.restype = None
     L.WorldMi355DefaultMcpfOption.argtypes = [C.POINTER(McpfOption)]
     L.WorldMi355MelCepstrumPostfilter.argtypes = [vp, vp, C.POINTER(McpfOption), vp, vp, vp]
+    L.WorldMi355ModifyFeatures.argtypes = [vp, _dp, _dp, vp, vp, vp, vp]
     L.WorldMi355DefaultMspfOption.restype = None
     L.WorldMi355DefaultMspfOption.argtypes = [C.POINTER(MspfOption)]
     L.WorldMi355ModulationSpectrumPostfilter.argtypes = [vp, vp, C.c_int, C.POINTER(MspfOption), vp, vp, vp, vp, vp, vp]

@@ -702,6 +702,28 @@ void WorldMi355DefaultMcpfOption(WorldMi355McpfOption* opt);
  * stream; a batch of zero frames returns WM_OK. */
 int WorldMi355MelCepstrumPostfilter(WorldMi355Batch* b, const double* mc, const WorldMi355McpfOption* opt, double* out,
                                     double* gain, int* status);
+/* ---- Parameter modification: F0 scaling and formant shift, ParameterModification of the reference's own example
+ * (externs/WORLD_v2/test/test.cpp:201-238), the step between analysis and synthesis.  Per utterance u there are two
+ * factors, shift = f0_scale[u] and ratio = formant_ratio[u]:
+ *   f0_out[i] = f0[i] * shift: one product, an unvoiced 0 stays 0, nothing is clamped                      (:204-207)
+ *   per frame, F = fft_size, n = F / 2 + 1, l[j] = log(sp[j]):                                             (:211-227)
+ *     knots x1[j] = ratio * j / F * fs (left to right, in double), queries x2[i] = (double)i / F * fs,
+ *     out[i] = exp(interp1(x1, l, n, x2, n)[i]), interp1 being src/matlabfunctions.cpp:157-182 (histc :136-155):
+ *     k = clamp(#{j : x1[j] <= x2[i]}, 1, n - 1), s = (x2[i] - x1[k-1]) / (x1[k] - x1[k-1]), l[k-1] + s (l[k] - l[k-1])
+ *   if ratio < 1, c = int(F / 2.0 * ratio): out[j] = out[c - 1] for j = c .. F / 2                         (:228-232)
+ * k and s are the reference's, ties (s == 0) included, so non-finite values land where the reference puts them: a zero
+ * bin has l = -inf and finite + 0 * (-inf) is NaN (ratio 1.0: a zero at bin i gives NaN at i - 1 and i).  Nothing is
+ * repaired.  A ratio of exactly 1.0 still goes through exp(log(.)); only a NULL factor array skips its part.  The
+ * aperiodicity is not touched, as in the reference.
+ * f0_scale, formant_ratio: HOST double[n_utt], or NULL: that part is not done and its pointers are not read.
+ * f0, f0_out: DEVICE double[total_frames]; sp, sp_out: DEVICE double[total_frames][fft_size/2+1]; f0_out == f0 and
+ * sp_out == sp (in place) are allowed.  The factors are copied before the call returns.  WM_ERR_BAD_ARG before any
+ * device call: both factor arrays NULL; a factor that is not finite or not > 0; ratio < 2.0 / F (the reference would
+ * read out[-1]) or ratio > F; a NULL data pointer of a part that is asked for; an output that overlaps its input other
+ * than exactly.  fft_size other than 512 .. 4096 with a ratio: WM_ERR_UNSUPPORTED_FFT.  Asynchronous on the context's
+ * stream; a batch of zero frames returns WM_OK. */
+int WorldMi355ModifyFeatures(WorldMi355Batch* b, const double* f0_scale, const double* formant_ratio, const double* f0,
+                             const double* sp, double* f0_out, double* sp_out);
 /* ---- Modulation-spectrum postfilter: postfiltering_mspf (scripts/Training.pl:2950-3000, msmp2seq :3003-3038), which
  * gen_wave runs on every generated `.mgc` INSTEAD of postfiltering_mcp when the recipe is configured with USEMSPF=1,
  * and the sums behind its statistics files (make_mspf, :3133-3221).  Settings: frame_length Lw ($mspfLength, odd),
@@ -871,7 +893,7 @@ int WorldMi355Vibrato(WorldMi355Batch* b, const float* lf0, const int* seg_utt_o
 /* Per-kernel timing with HIP events recorded on the context's stream around each launch of the
  * named kernels ("dio_lowcut_kernel", "dio_band_kernel", "stonemask_kernel", "cheaptrick_kernel",
  * "d4c_lovetrain_kernel", "d4c_kernel", "synth_timebase_kernel", "synth_pulse_kernel",
- * "synth_ola_kernel", "mcep_kernel", "mgcep_kernel", "mlpg_kernel", "mcpf_kernel", "mspf_kernel", "mspf_stats_kernel",
+ * "synth_ola_kernel", "mcep_kernel", "mgcep_kernel", "mlpg_kernel", "mcpf_kernel", "modify_kernel", "mspf_kernel", "mspf_stats_kernel",
  * "interpolate_gaps_kernel", "ffo_compose_kernel", "column_moments_kernel", "trj_kernel": its
  * column kernels and trj_reduce_kernel as one record, "dnn_layer_kernel": all layers of a call as one record,
  * "dnn_cost_kernel", "optimizer_step_kernel", "label_match_kernel", "ffi_rows_kernel").  Enable clears earlier records; Query synchronises the stream and
