@@ -9,7 +9,7 @@ device-resident ``WorldBatch``.  All compute happens in ``libworld_mi355.so``
 library or a GPU is missing the calls raise.
 """
 from . import world, synth_data, sharding, capi  # noqa: F401
-from .world import WorldBatch, WorldParams, load_library, sptk_frames, sptk_window  # noqa: F401
+from .world import MgcConvertOption, WorldBatch, WorldParams, load_library, sptk_frames, sptk_window  # noqa: F401
 
 
 def __getattr__(name):

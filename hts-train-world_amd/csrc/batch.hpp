@@ -358,6 +358,9 @@ int launch_mel_cepstrum_of_waveform(Batch& b, hipStream_t st, const double* d_x,
 int check_mgc2sp(const Batch& b, const double* d_mc, const WorldMi355Mgc2spOption& opt, const double* d_sp);
 int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355Mgc2spOption& opt, double* d_sp,
                   double* d_phase, int* d_status);
+int check_mgc2mgc(int64_t total_rows, const double* d_in, const WorldMi355MgcConvertOption* opt, const double* d_out);
+int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt, double* d_out,
+                   int* d_status);
 // mlsa.hip: excite | dfs | mglsadf.  mode bits of check_mlsa: 1 the excitation's arguments, 2 the filter's
 int mlsa_samples(int n_frames, int frame_shift, int* n_samples);
 int mlsa_pade(int order, double* row);

@@ -342,6 +342,18 @@ int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const 
   if (const int rc = check_mgc2sp(b->b, mc, *opt, spectrum)) return rc;         // refused before any device call
   return on_batch(b, launch_mgc2sp, mc, *opt, spectrum, phase, status);
 }
+void WorldMi355DefaultMgcConvertOption(WorldMi355MgcConvertOption* o) {         // SPTK's mgc2mgc defaults
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->in_order = 25;
+  o->out_order = 25;
+}
+int WorldMi355MelGeneralizedCepstrumConvert(WorldMi355Batch* b, const double* in, const WorldMi355MgcConvertOption* opt,
+                                            double* out, int* status) {
+  if (!b || !opt) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mgc2mgc(b->b.total_f, in, opt, out)) return rc;      // refused before any device call
+  return on_batch(b, launch_mgc2mgc, in, *opt, out, status);
+}
 void WorldMi355DefaultMlsaOption(WorldMi355MlsaOption* o) {                     // SPTK's mglsadf defaults, Pade order 4
   if (!o) return;
   memset(o, 0, sizeof(*o));

@@ -32,7 +32,8 @@ of the per-utterance variances that `gv-data` writes, and parameter generation t
 (HMGenS with USEHMMGV = 1, scripts/Training.pl:1892-1903), after which gen_wave skips the postfilter (:749-757).
 gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
 model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is the step gen_wave takes between the two
-(scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With USEMSPF gen_wave takes
+(scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With GAMMA != 0 gen_wave's
+`mgc2mgc` steps (:2861-2868; postfiltering_lsp's :2702-2705) are mgc2mgc_files() / `mgc2mgc`.  With USEMSPF gen_wave takes
 postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
 `mspf-stats` write (make_mspf, :3133-3221).
 mgcep_files() / `mgcep` is the recipe's spectral analysis without WORLD (data/Makefile.in:134-137, the default
@@ -1581,6 +1582,66 @@ def postfilter_files(jobs, order, alpha, beta=1.4, length=4096, ctx=None, max_ba
     return stage.frames
 
 
+# ---- conversion between mel-generalized cepstra (SPTK's mgc2mgc: scripts/Training.pl:2861-2868, :2702-2705) ---------
+def sptk_gamma(g=None, c=None):
+    """SPTK's two ways to name a gamma: -g G as it is, -c N as -1 / N (N >= 1); neither: 0."""
+    if g is not None and c is not None:
+        raise ValueError("gamma is given by -g or by -c, not both")
+    if c is not None:
+        if c < 1:
+            raise ValueError("-c %d: at least 1" % c)
+        return -1.0 / c
+    return 0.0 if g is None else float(g)
+
+
+def mgc2mgc_check(order, alpha, gamma, out_order, out_alpha, out_gamma, multiplied=False, out_multiplied=False):
+    """ValueError for what WorldMi355MelGeneralizedCepstrumConvert refuses, before a file is read."""
+    if not (1 <= order <= 4095 and 1 <= out_order <= 4095 and min(order, out_order) <= 63):
+        raise ValueError("orders %d -> %d: 1 .. 4095 each, one of them at most 63" % (order, out_order))
+    if not (abs(alpha) < 1 and abs(out_alpha) < 1 and -1 <= gamma <= 1 and -1 <= out_gamma <= 1):
+        raise ValueError("|alpha| < 1 and -1 <= gamma <= 1 on both sides")
+    if (multiplied and gamma == 0) or (out_multiplied and out_gamma == 0):
+        raise ValueError("-u needs gamma != 0 on the input side, -U on the output side")
+
+
+def mgc2mgc_files(jobs, order, alpha, gamma, out_order, out_alpha, out_gamma, normalized=False, multiplied=False,
+                  out_normalized=False, out_multiplied=False, ctx=None, max_batch_frames=MAX_BATCH_FRAMES, io_threads=8,
+                  resume=False):
+    """SPTK's `mgc2mgc -m order -a alpha -g gamma [-n] [-u] -M out_order -A out_alpha -G out_gamma [-N] [-U]` for a
+    file list: the step gen_wave (scripts/Training.pl:2861-2868) and postfiltering_lsp (:2702-2705, :2739-2742) take
+    with GAMMA != 0 (flag semantics unpinned against SPTK's command: include/world_mi355.h is the definition).
+
+    jobs:  [(in, out)] -- float32 [T][order+1] in, float32 [T][out_order+1] out
+    SPTK's file contract: the rows are widened to double on the device, converted there, and rounded to float32 once on
+    the way out.  Rank-sharded by frame count; with resume, utterances whose output has its full size are skipped."""
+    jobs = list(jobs)
+    mgc2mgc_check(order, alpha, gamma, out_order, out_alpha, out_gamma, multiplied, out_multiplied)
+    width, out_width = int(order) + 1, int(out_order) + 1
+    frames = [_rows_in(j, width, 2, "one output path") for j in jobs]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 4 * out_width * frames[i])))
+    if not mine:
+        return 0
+    with _Stage(ctx, io_threads) as stage:
+        # the limit counts rows of at most 64 coefficients: rows of up to 4096 take their share of it
+        limit = max(1, max_batch_frames * 64 // max(64, width, out_width))
+        for group, batch in stage.batches(mine, frames, limit):
+            with batch as b:
+                rows = stage.load([jobs[i][0] for i in group], width)
+                out, status = b.convert_mel_generalized_cepstrum(rows.double(), alpha, gamma, out_order, out_alpha,
+                                                                 out_gamma, normalized, multiplied, out_normalized,
+                                                                 out_multiplied)
+                host = out.float().cpu().numpy()
+                st = status.cpu().numpy()
+                fo = b.frame_offsets
+                for k, i in enumerate(group):
+                    bad = np.nonzero(st[fo[k]:fo[k + 1]])[0]
+                    if len(bad):
+                        print("warning: %s: %d frames flagged (first: frame %d, status %d), written as zeros" % (
+                            jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
+                stage.put(b, host, [jobs[i][1] for i in group])
+    return stage.frames
+
+
 # ---- mel-cepstra from waveforms (data/Makefile.in:134-137: x2x +sf | frame | window | mgcep at gamma 0) ---------------
 def read_samples(path):
     """The int16 values of a headerless little-endian `.raw` file (what `x2x +sf` reads) or of a 16-bit wav, as float64
@@ -2292,6 +2353,21 @@ def main(argv=None):
     p.add_argument("--beta", type=float, default=1.4, help="the postfiltering coefficient (pf_mcp)")
     p.add_argument("--length", type=int, default=4096, help="bins of the energy sums (IMPLEN)")
     p.add_argument("--resume", action="store_true", help="skip utterances whose p_mgc file is already complete")
+    p = sub.add_parser("mgc2mgc", help="SPTK's mgc2mgc on a list of float32 files: another alpha, gamma or order")
+    p.add_argument("--scp", required=True, help="job list: the file to read, then the file to write")
+    p.add_argument("-m", type=int, default=25, dest="order", help="order of the input: a row holds m + 1 float32")
+    p.add_argument("-a", type=float, default=0.0, dest="alpha", help="alpha of the input")
+    p.add_argument("-g", type=float, default=None, dest="gamma", help="gamma of the input")
+    p.add_argument("-c", type=int, default=None, dest="c", help="gamma of the input = -1 / C")
+    p.add_argument("-n", action="store_true", dest="normalized", help="the input is gain-normalized")
+    p.add_argument("-u", action="store_true", dest="multiplied", help="the input is multiplied by gamma")
+    p.add_argument("-M", type=int, default=25, dest="out_order", help="order of the output")
+    p.add_argument("-A", type=float, default=0.0, dest="out_alpha", help="alpha of the output")
+    p.add_argument("-G", type=float, default=None, dest="out_gamma", help="gamma of the output")
+    p.add_argument("-C", type=int, default=None, dest="out_c", help="gamma of the output = -1 / C")
+    p.add_argument("-N", action="store_true", dest="out_normalized", help="gain-normalized output")
+    p.add_argument("-U", action="store_true", dest="out_multiplied", help="output multiplied by gamma")
+    p.add_argument("--resume", action="store_true", help="skip utterances whose output file is already complete")
     p = sub.add_parser("mgcep", help="x2x +sf | frame | window | mgcep at gamma 0: mel-cepstra of a list of raw or wav files")
     p.add_argument("--scp", required=True, help="job list: the .raw (int16) or wav file, then the mgc file to write")
     p.add_argument("--frame-length", type=int, default=1200, help="FRAMELEN")
@@ -2522,6 +2598,12 @@ def main(argv=None):
                                       a.pade_order, pipe_float32=not a.no_pipe_float32,
                                       max_batch_frames=a.max_batch_frames, resume=a.resume)
         print("complete. %d frames, %d utterances flagged" % (n, len(flagged)))
+        return 0
+    if a.cmd == "mgc2mgc":
+        n = mgc2mgc_files(_read_scp(a.scp, 2), a.order, a.alpha, sptk_gamma(a.gamma, a.c), a.out_order, a.out_alpha,
+                          sptk_gamma(a.out_gamma, a.out_c), a.normalized, a.multiplied, a.out_normalized, a.out_multiplied,
+                          resume=a.resume)
+        print("complete. %d frames" % n)
         return 0
     if a.cmd == "postfilter":
         n = postfilter_files(_read_scp(a.scp, 2), a.order, a.alpha, a.beta, a.length, resume=a.resume)

@@ -156,6 +156,13 @@ class Mgc2spOption(C.Structure):
     _fields_ = [("alpha", C.c_double), ("gamma", C.c_double), ("order", C.c_int), ("out_format", C.c_int)]
 
 
+class MgcConvertOption(C.Structure):
+    """include/world_mi355.h: WorldMi355MgcConvertOption (the arguments and flags of SPTK's mgc2mgc)."""
+    _fields_ = [("in_order", C.c_int), ("in_alpha", C.c_double), ("in_gamma", C.c_double), ("in_normalized", C.c_int),
+                ("in_multiplied", C.c_int), ("out_order", C.c_int), ("out_alpha", C.c_double), ("out_gamma", C.c_double),
+                ("out_normalized", C.c_int), ("out_multiplied", C.c_int)]
+
+
 class MlsaOption(C.Structure):
     """include/world_mi355.h: WorldMi355MlsaOption (SPTK's excite | dfs | mglsadf, gen_wave's first branch)."""
     _fields_ = [("alpha", C.c_double), ("order", C.c_int), ("pade_order", C.c_int), ("frame_shift", C.c_int),
@@ -326,6 +333,9 @@ def load_library():
     L.WorldMi355DefaultMgc2spOption.restype = None
     L.WorldMi355DefaultMgc2spOption.argtypes = [C.POINTER(Mgc2spOption)]
     L.WorldMi355MelCepstrumToSpectrum.argtypes = [vp, vp, C.POINTER(Mgc2spOption), vp, vp, vp]
+    L.WorldMi355DefaultMgcConvertOption.restype = None
+    L.WorldMi355DefaultMgcConvertOption.argtypes = [C.POINTER(MgcConvertOption)]
+    L.WorldMi355MelGeneralizedCepstrumConvert.argtypes = [vp, vp, C.POINTER(MgcConvertOption), vp, vp]
     L.WorldMi355DefaultMcpfOption.restype = None
     L.WorldMi355DefaultMcpfOption.argtypes = [C.POINTER(McpfOption)]
     L.WorldMi355MelCepstrumPostfilter.argtypes = [vp, vp, C.POINTER(McpfOption), vp, vp, vp]
@@ -616,7 +626,34 @@ def pool_distortion(out, kinds):
 MCEP_OPTIONS = ("order", "alpha", "itr1", "itr2", "dd", "etype", "e", "f", "itype")
 
 
-class WorldBatch:
+class _CepstrumConversions:
+    """The conversions between cepstral representations that WorldBatch offers: a base of WorldBatch, which supplies the
+    batch (handle, total_frames, device) and the shared argument checks."""
+
+    def convert_mel_generalized_cepstrum(self, mc, alpha, gamma, out_order, out_alpha, out_gamma, normalized=False,
+                                         multiplied=False, out_normalized=False, out_multiplied=False):
+        """SPTK's mgc2mgc per frame (the core: test/sptkfunctions.cpp:221-254; the flags as include/world_mi355.h
+        defines them, flag semantics unpinned against SPTK's command): mc is float64 cuda [total_frames][order+1] at
+        (alpha, gamma), the result float64 [total_frames][out_order+1] at (out_alpha, out_gamma).  normalized /
+        multiplied are -n / -u of the input, out_normalized / out_multiplied -N / -U of the output.  |alpha| < 1,
+        -1 <= gamma <= 1, orders 1 .. 4095 of which one is at most 63.  Returns (out, status int32 [total_frames]:
+        0 fine, 1 a non-finite coefficient or a gain that is not positive, 2 a non-finite result; flagged rows are
+        zeros)."""
+        where = "convert_mel_generalized_cepstrum"
+        mp, cols = self._f64(where, "mc", mc, self.total_frames, None)
+        o = _option(where, MgcConvertOption, "WorldMi355DefaultMgcConvertOption",
+                    dict(in_order=cols - 1, in_alpha=float(alpha), in_gamma=float(gamma), in_normalized=int(bool(normalized)),
+                         in_multiplied=int(bool(multiplied)), out_order=int(out_order), out_alpha=float(out_alpha),
+                         out_gamma=float(out_gamma), out_normalized=int(bool(out_normalized)),
+                         out_multiplied=int(bool(out_multiplied))))
+        out = self._new(self.total_frames, max(int(out_order), 0) + 1)
+        status = self._new(self.total_frames, dtype=torch.int32)
+        _check(load_library().WorldMi355MelGeneralizedCepstrumConvert(self.handle, mp, C.byref(o), _ptr(out),
+                                                                      _ptr(status)), "MelGeneralizedCepstrumConvert")
+        return out, status
+
+
+class WorldBatch(_CepstrumConversions):
     """A batch of utterances resident in HBM (torch cuda tensors, float64).
 
     x is the concatenation of the waveforms (see ``sample_offsets``); t, f0 have

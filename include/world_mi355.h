@@ -288,6 +288,53 @@ void WorldMi355DefaultMgc2spOption(WorldMi355Mgc2spOption* opt);
 int WorldMi355MelCepstrumToSpectrum(WorldMi355Batch* b, const double* mc, const WorldMi355Mgc2spOption* opt,
                                     double* spectrum, double* phase, int* status);
 
+/* ---- Conversion between mel-generalized cepstra: SPTK's `mgc2mgc`, the step gen_wave (scripts/Training.pl:2861-2868) and
+ * postfiltering_lsp (:2702-2705, :2739-2742) take with GAMMA != 0.  Rows c1[0 .. m1] at (alpha a1, gamma g1) become
+ * c2[0 .. m2] at (a2, g2).  The core is the CLIs' SPTK port, mgc2mgc(c1, m1, a1, g1, c2, m2, a2, g2)
+ * (test/sptkfunctions.cpp:221-254), in its own branches, with a = (a2 - a1) / (1 - a1 a2) in that expression (:238):
+ *   a == 0   gnorm(m1, g1) (:313-328), gc2gc(m1, g1 -> m2, g2) (:347-385), ignorm(m2, g2) (:330-345);
+ *   a != 0   freqt(m1 -> m2, a) (:596-631), gnorm over M2 coefficients with g1, gc2gc(m2, g1 -> m2, g2), ignorm(m2, g2).
+ * The four flags are those of SPTK's command line, which is not in the reference tree.  FLAG SEMANTICS UNPINNED AGAINST
+ * SPTK'S COMMAND: the yardstick is this definition, which tests/mgc2mgc_reference.py states in float64.
+ *   in_normalized  (-n)  before the core, c <- ignorm(c, m1, g1): c[k] <- K c[k], c[0] <- (K - 1) / g1 with
+ *                        K = pow(c[0], g1) (c[0] <- log c[0] at g1 == 0).  Takes precedence over in_multiplied's c[0] rule.
+ *   in_multiplied  (-u)  before the core and after -n's step, c[0] <- (c[0] - 1) / g1 (not with -n), then c[k] <- c[k] / g1
+ *                        for k >= 1.  WM_ERR_BAD_ARG at g1 == 0.
+ *   out_normalized (-N)  after the core, c <- gnorm(c, m2, g2): c[k] <- c[k] / (1 + g2 c[0]),
+ *                        c[0] <- pow(1 + g2 c[0], 1 / g2) (c[0] <- exp c[0] at g2 == 0).  Takes precedence over
+ *                        out_multiplied's c[0] rule.
+ *   out_multiplied (-U)  after the core and after -N's step, c[0] <- c[0] g2 + 1 (not with -N), then c[k] <- c[k] g2 for
+ *                        k >= 1.  WM_ERR_BAD_ARG at g2 == 0.
+ * The flag steps, gnorm's division and ignorm's product are these expressions without contraction; pow, exp and log are
+ * the device library's.  freqt is the reference's expression in its order: at g1 == g2 == 0 without flags c2[1 .. m2] are
+ * its bits.  Towards out_order <= 64 gc2gc's sums run in the reference's order with its roundings; towards more
+ * coefficients they run in another order and differ from the reference's by its rounding error. */
+typedef struct {
+  int in_order;             /* m1 */
+  double in_alpha;          /* a1 */
+  double in_gamma;          /* g1 */
+  int in_normalized;        /* -n */
+  int in_multiplied;        /* -u */
+  int out_order;            /* m2 */
+  double out_alpha;         /* a2 */
+  double out_gamma;         /* g2 */
+  int out_normalized;       /* -N */
+  int out_multiplied;       /* -U */
+} WorldMi355MgcConvertOption;
+/* SPTK's defaults: orders 25, alphas 0, gammas 0, no flag. */
+void WorldMi355DefaultMgcConvertOption(WorldMi355MgcConvertOption* opt);
+/* in: DEVICE double[total_frames][in_order+1]; out: DEVICE double[total_frames][out_order+1], no element shared with
+ * `in`; status: DEVICE int[total_frames] or NULL: 0 fine; 1 a non-finite input coefficient or a gain that is not positive
+ * (c[0] itself under in_normalized, else 1 + g1 c0 of the plain row for g1 != 0, and 1 + g1 c2[0] after freqt in the
+ * a != 0 branch, where the reference's pow returns NaN); 2 a non-finite result.  Flagged rows are zeros.  Rows never
+ * exchange data.  1 <= in_order, out_order <= 4095 with min(in_order, out_order) <= 63, |alpha| < 1 and
+ * -1 <= gamma <= 1 on both sides, else WM_ERR_BAD_ARG, as for a NULL `in` or `out` or ranges that share an element; all
+ * before any device call.  Timed as "mgc2mgc_kernel".  Asynchronous on the context's stream.
+ * Not offered: LSP in either direction (lpc2lsp, lsp2lpc, lspcheck), mglsadf and mgcep at gamma != 0, the energy sum of
+ * postfiltering_lsp, WorldMi355MelCepstrumToSpectrum of flagged input, host pointers, min(in_order, out_order) > 63. */
+int WorldMi355MelGeneralizedCepstrumConvert(WorldMi355Batch* b, const double* in, const WorldMi355MgcConvertOption* opt,
+                                            double* out, int* status);
+
 /* ---- Waveforms from mel-cepstra: the first branch of gen_wave (scripts/Training.pl:2873-2899), the synthesis half of the
  * recipe's default configuration (USEWORLD = 0, GAMMA = 0),
  *   sopr -m 0 pit | excite -n -p P | dfs -b highpass > unv
