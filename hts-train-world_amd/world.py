@@ -11,6 +11,7 @@ The library is mandatory: nothing here computes WORLD on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -595,6 +596,27 @@ def _b_offsets(where, b_lengths, n_utt):
     return off
 
 
+def factor_array(where, name, value, n_utt, fft_size=None):
+    """`value` -- None, a number, or one number per utterance -- as a float64 array [n_utt] (None stays None), checked as
+    the library checks it: finite and > 0, and for the formant ratio (fft_size given) inside [2 / fft_size, fft_size]:
+    below it the reference's fill reads the bin before the first, above it nothing is left to stretch.  ValueError."""
+    if value is None:
+        return None
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(n_utt, float(a))
+    if a.shape != (n_utt,):
+        raise ValueError(f"{where}: {name} must be a number or one per utterance ({n_utt}), got shape {list(a.shape)}")
+    a = np.ascontiguousarray(a)
+    for u, v in enumerate(a):
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"{where}: {name}[{u}] = {v!r} must be finite and > 0")
+        if fft_size is not None and not 2.0 / fft_size <= v <= fft_size:
+            raise ValueError(f"{where}: {name}[{u}] = {v!r} is outside [2 / fft_size, fft_size] = "
+                             f"[{2.0 / fft_size!r}, {fft_size}]")
+    return a
+
+
 def pool_distortion(out, kinds):
     """The corpus figures of WorldBatch.feature_distortion outputs.  out: [n_utt][n_groups][4] (numpy, or anything
     np.asarray takes; the rows of several batches or ranks stacked in any order); kinds: the n_groups kinds, 0 cepstral
@@ -602,7 +624,6 @@ def pool_distortion(out, kinds):
     pairs, "pairs": n}; kind 1 {"kind": 1, "rmse_cents": (1200 / ln 2) sqrt(sum D^2 / n) over the pairs voiced on
     both sides, "voiced_pairs": n, "vuv_error_percent": 100 differing / counted, "vuv_errors", "pairs"}.  A figure
     without pairs is nan.  Sums are math.fsum's, exact, so the result does not depend on how a job list was split."""
-    import math
     o = np.asarray(out, dtype=np.float64).reshape(-1, len(kinds), 4)
     res = []
     for g, kind in enumerate(kinds):
@@ -626,34 +647,7 @@ def pool_distortion(out, kinds):
 MCEP_OPTIONS = ("order", "alpha", "itr1", "itr2", "dd", "etype", "e", "f", "itype")
 
 
-class _CepstrumConversions:
-    """The conversions between cepstral representations that WorldBatch offers: a base of WorldBatch, which supplies the
-    batch (handle, total_frames, device) and the shared argument checks."""
-
-    def convert_mel_generalized_cepstrum(self, mc, alpha, gamma, out_order, out_alpha, out_gamma, normalized=False,
-                                         multiplied=False, out_normalized=False, out_multiplied=False):
-        """SPTK's mgc2mgc per frame (the core: test/sptkfunctions.cpp:221-254; the flags as include/world_mi355.h
-        defines them, flag semantics unpinned against SPTK's command): mc is float64 cuda [total_frames][order+1] at
-        (alpha, gamma), the result float64 [total_frames][out_order+1] at (out_alpha, out_gamma).  normalized /
-        multiplied are -n / -u of the input, out_normalized / out_multiplied -N / -U of the output.  |alpha| < 1,
-        -1 <= gamma <= 1, orders 1 .. 4095 of which one is at most 63.  Returns (out, status int32 [total_frames]:
-        0 fine, 1 a non-finite coefficient or a gain that is not positive, 2 a non-finite result; flagged rows are
-        zeros)."""
-        where = "convert_mel_generalized_cepstrum"
-        mp, cols = self._f64(where, "mc", mc, self.total_frames, None)
-        o = _option(where, MgcConvertOption, "WorldMi355DefaultMgcConvertOption",
-                    dict(in_order=cols - 1, in_alpha=float(alpha), in_gamma=float(gamma), in_normalized=int(bool(normalized)),
-                         in_multiplied=int(bool(multiplied)), out_order=int(out_order), out_alpha=float(out_alpha),
-                         out_gamma=float(out_gamma), out_normalized=int(bool(out_normalized)),
-                         out_multiplied=int(bool(out_multiplied))))
-        out = self._new(self.total_frames, max(int(out_order), 0) + 1)
-        status = self._new(self.total_frames, dtype=torch.int32)
-        _check(load_library().WorldMi355MelGeneralizedCepstrumConvert(self.handle, mp, C.byref(o), _ptr(out),
-                                                                      _ptr(status)), "MelGeneralizedCepstrumConvert")
-        return out, status
-
-
-class WorldBatch(_CepstrumConversions):
+class WorldBatch:
     """A batch of utterances resident in HBM (torch cuda tensors, float64).
 
     x is the concatenation of the waveforms (see ``sample_offsets``); t, f0 have
@@ -1061,6 +1055,59 @@ class WorldBatch(_CepstrumConversions):
         _check(load_library().WorldMi355MelCepstrumToSpectrum(self.handle, mp, C.byref(o), _ptr(sp), _ptr(ph),
                                                               _ptr(status)), "MelCepstrumToSpectrum")
         return (sp, ph, status) if phase else (sp, status)
+
+    def convert_mel_generalized_cepstrum(self, mc, alpha, gamma, out_order, out_alpha, out_gamma, normalized=False,
+                                         multiplied=False, out_normalized=False, out_multiplied=False):
+        """SPTK's mgc2mgc per frame (the core: test/sptkfunctions.cpp:221-254; the flags as include/world_mi355.h
+        defines them, flag semantics unpinned against SPTK's command): mc is float64 cuda [total_frames][order+1] at
+        (alpha, gamma), the result float64 [total_frames][out_order+1] at (out_alpha, out_gamma).  normalized /
+        multiplied are -n / -u of the input, out_normalized / out_multiplied -N / -U of the output.  |alpha| < 1,
+        -1 <= gamma <= 1, orders 1 .. 4095 of which one is at most 63.  Returns (out, status int32 [total_frames]:
+        0 fine, 1 a non-finite coefficient or a gain that is not positive, 2 a non-finite result; flagged rows are
+        zeros)."""
+        where = "convert_mel_generalized_cepstrum"
+        mp, cols = self._f64(where, "mc", mc, self.total_frames, None)
+        o = _option(where, MgcConvertOption, "WorldMi355DefaultMgcConvertOption",
+                    dict(in_order=cols - 1, in_alpha=float(alpha), in_gamma=float(gamma), in_normalized=int(bool(normalized)),
+                         in_multiplied=int(bool(multiplied)), out_order=int(out_order), out_alpha=float(out_alpha),
+                         out_gamma=float(out_gamma), out_normalized=int(bool(out_normalized)),
+                         out_multiplied=int(bool(out_multiplied))))
+        out = self._new(self.total_frames, max(int(out_order), 0) + 1)
+        status = self._new(self.total_frames, dtype=torch.int32)
+        _check(load_library().WorldMi355MelGeneralizedCepstrumConvert(self.handle, mp, C.byref(o), _ptr(out),
+                                                                      _ptr(status)), "MelGeneralizedCepstrumConvert")
+        return out, status
+
+    def modify_features(self, f0=None, sp=None, f0_scale=None, formant_ratio=None, out=None):
+        """f0 [total_frames] times f0_scale and sp [total_frames][bins] stretched by formant_ratio, per utterance
+        (WorldMi355ModifyFeatures, csrc/modify.hip; modify.py has the chain around it).
+
+        f0_scale, formant_ratio: None, a number for every utterance, or one number per utterance.  At least one is
+        given; the tensor of a part that is given must be given too.  out: None for fresh tensors, or (f0_out, sp_out)
+        with None for a part that is to be fresh; an output may be its own input (in place), not a shifted view of it.
+        Returns (f0_out, sp_out); a part that is not done is the argument as it came (None included).  Bad factors and
+        bad tensors raise ValueError before the library is called.  Asynchronous on the context's stream."""
+        where = "modify_features"
+        if f0_scale is None and formant_ratio is None:
+            raise ValueError(f"{where}: give f0_scale, formant_ratio or both")
+        shift = factor_array(where, "f0_scale", f0_scale, self.n_utt)
+        ratio = factor_array(where, "formant_ratio", formant_ratio, self.n_utt, self.fft_size)
+        if out is None:
+            out = (None, None)
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError(f"{where}: out must be (f0_out, sp_out), either of them None")
+        f0_out, sp_out = f0, sp
+        f0p = spp = f0op = spop = None
+        if shift is not None:
+            f0p = self._f64(where, "f0", f0, self.total_frames)
+            f0_out, f0op = self._out(where, out[0], self.total_frames, name="out[0]")
+        if ratio is not None:
+            spp = self._f64(where, "sp", sp, self.total_frames, self.bins)
+            sp_out, spop = self._out(where, out[1], self.total_frames, self.bins, name="out[1]")
+        _check(load_library().WorldMi355ModifyFeatures(
+            self.handle, None if shift is None else shift.ctypes.data_as(_dp),
+            None if ratio is None else ratio.ctypes.data_as(_dp), f0p, spp, f0op, spop), "ModifyFeatures")
+        return f0_out, sp_out
 
     def postfilter_mel_cepstrum(self, mc, alpha=0.35, beta=1.4, length=4096, gain=False):
         """The recipe's formant emphasis per frame (scripts/Training.pl:2642-2687, postfiltering_mcp): mc is float64

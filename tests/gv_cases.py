@@ -1,4 +1,4 @@
-"""The inputs that tests/test_gpu_mlpg_gv.py, tests/test_gpu_mlpg_gv_stream.py and tests/test_mlpg_gv_host.py share, and
+"""The inputs that tests/test_gpu_mlpg_gv.py, tests/test_gpu_caller_stream.py and tests/test_mlpg_gv_host.py share, and
 the numpy reference (tests/gv_reference.py) evaluated on them, once per process.  A helper, not a test."""
 import functools
 

@@ -13,8 +13,9 @@ Here the context sits on a torch side stream U (non-blocking), and every call is
      and the sample that utterance_status flags);
   2  one warm-up call on `stale` (tables, workspaces, function attributes, the randn table), then U.synchronize();
   3  on U: a delay kernel of about 50 ms, an event, the copy of `fresh` over `stale` -- and the library call at once;
-  4  right after the call returns the event must NOT have completed (entry points of ASYNC below: the call was issued
-     ahead of its input); the results are cloned on U, U alone is synchronised, and the clones meet the reference.
+  4  right after the call returns the event must NOT have completed (entry points of caller_stream_table.py's
+     ASYNC: the call was issued ahead of its input); the results are cloned on U, U alone is synchronised, and the
+     clones meet the reference.
 
 Work on stream 0, or on a side stream not forked from U, reads `stale`; work not joined back into U leaves the clone
 with the warm-up's result.  Either way the reference of `fresh` is missed.  Secondary: the clones equal, bit for bit, the
@@ -31,19 +32,29 @@ import os
 import numpy as np
 import pytest
 
+from caller_stream_table import ASYNC, COVERED, SYNCHRONISES
 from conftest import GOLDEN
 
 import dnn_reference as DR
 import dnn_train_reference as DT
+import dtw_cases as K_DTW
+import gv_cases as K_GV
 import mlpg_reference as M
+import mlsa_reference as R_MLSA
+import modify_reference as mr
 import optimizer_reference as O
 import test_gpu_dnn as T_DNN
 import test_gpu_dnn_train as T_TRAIN
 import test_gpu_ffo as T_FFO
 import test_gpu_label_features as T_LABEL
 import test_gpu_mel_cepstrum as T_MCEP
+import test_gpu_mgc2mgc as T_MGC2MGC
 import test_gpu_mgc2sp as T_MGC2SP
+import test_gpu_mgcep as T_MGCEP
 import test_gpu_mlpg as T_MLPG
+import test_gpu_mlpg_gv as T_GV
+import test_gpu_mlsa as T_MLSA
+import test_gpu_modify as T_MOD
 import test_gpu_mspf as T_MSPF
 import test_gpu_parity as T_WORLD
 import test_gpu_postfilter as T_MCPF
@@ -55,28 +66,6 @@ from test_gpu_parity import AP_TOL, F0_TOL, Y_TOL, cat, oracle_chain, sp_close
 
 pytestmark = pytest.mark.gpu
 sd = importlib.import_module("hts-train-world_amd.synth_data")
-
-# Which entry points return without a host round trip once their one-off set-ups are made (the warm-up): for these the
-# delay must still be running when the call returns.  Read from the code, not tried.
-ASYNC = ("dio", "harvest", "stonemask", "cheaptrick", "d4c", "analyze", "samples_from_pcm16", "samples_to_pcm16",
-         "utterance_status", "code_spectral_envelope", "decode_spectral_envelope", "code_aperiodicity",
-         "decode_aperiodicity", "recipe_features", "recipe_decode", "compose_cmp", "compose_ffo", "interpolate_gaps",
-         "column_moments", "utterance_means", "mel_cepstrum", "spectrum_from_mel_cepstrum", "postfilter_mel_cepstrum",
-         "modulation_spectrum_stats", "postfilter_modulation_spectrum", "parameter_generation", "trajectory_cost",
-         "acoustic_model_forward", "acoustic_model_train_forward", "acoustic_model_backward", "optimizer_step")
-# ... and the ones that wait for the stream inside, each with the line that does
-SYNCHRONISES = {
-    "synthesize": "synthesis.hip, synthesis_prepare_wait: hipStreamSynchronize(st) -- the pulse count read on the host "
-                  "sizes the response scratch (the split form waits once per part)",
-    "analyze_synthesize": "the same round trip of Synthesis's preparation, on the side stream forked from the caller's "
-                          "(cold: on the caller's stream itself)",
-    "vibrato": "vibrato.hip, launch_vibrato's last step: hipStreamSynchronize(st) -- the uploaded segment arrays are "
-               "call-local and *n_too_long is returned to the host",
-    "label_features": "ffi.hip, launch_label_features: hipStreamSynchronize(st) on every call of a batch but its first "
-                      "-- the upload image and the device block of the call before are reused",
-}
-COVERED = ASYNC[:-1] + tuple(SYNCHRONISES)          # WorldBatch methods; optimizer_step is the context's
-
 
 def _walk(obj, torch, f):
     """obj with f applied to every tensor in it (lists, tuples and dicts are walked; the rest is kept)."""
@@ -1019,6 +1008,126 @@ def test_host_pipeline_on_the_callers_stream(env, pkg):
         for a, c in zip(g, w):
             np.testing.assert_array_equal(a, c)
     pipe.close()
+
+
+# ---- the later stages: evaluation, MLSA synthesis, GV, cepstrum conversion, voice modification -------------------
+
+def frames_batch(env, lengths, fs=48000, y_lengths=None, **params):
+    return env.proxy.WorldBatch(env.ctx, env.W.default_params(fs, 5.0, **params), f0_lengths=list(lengths),
+                                y_lengths=y_lengths)
+
+
+def test_dtw_align_and_feature_distortion(env):
+    """Three ragged pairs: the path, its length and cost against dtw_cases.reference, the distortion along that path."""
+    torch = env.torch
+    pairs = ((65, 130), (7, 1), (129, 64))
+    a, b = K_DTW.batch_rows(pairs, **K_DTW.RAGGED_SHAPE)
+    da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    b_len = [tb for _, tb in pairs]
+    batch = frames_batch(env, [ta for ta, _ in pairs])
+    path, n, cost, status = batch.dtw_align(da, db, b_len, 1, 5)
+    out = batch.feature_distortion([(da, db, 1, 5, 0)], b_len, path, n,
+                                   _stale=[da.clone(), db.clone(), path.clone(), n.clone()])
+    path, n, cost, status, out = [host(t) for t in (path, n, cost, status, out)]
+    batch.close()
+    at = 0
+    for u, (ta, tb) in enumerate(pairs):
+        ref_path, ref_cost, _ = K_DTW.reference(ta, tb, 5)
+        assert status[u] == 0 and n[u] == len(ref_path)
+        assert np.array_equal(path[at:at + n[u]], ref_path) and (path[at + n[u]:at + ta + tb - 1] == -1).all()
+        assert abs(cost[u] - float(ref_cost)) <= K_DTW.cost_bound(ta, tb, 5, ref_cost)
+        assert out[u, 0, 2] == n[u] and out[u, 0, 0] > 0.0
+        at += ta + tb - 1
+
+
+def test_mlsa_synthesis_while_the_noise_table_grows(env):
+    """Ahead of every other MLSA call of the file's context: 195 samples at the most, then a batch with 5520 -- past the
+    first noise table's 4096 spare values, so that the table grows between the calls."""
+    torch = env.torch
+    order, alpha, pd = 12, 0.42, 4
+    rounds = [(5, [("voiced", 9), ("alternate", 40), ("unvoiced", 3)]), (80, [("alternate", 70), ("voiced", 3)])]
+    for k, (P, parts) in enumerate(rounds):
+        pitches, mcs = T_MLSA.synthesis_inputs(81 + k, parts, order)
+        Ts = [len(m) for m in mcs]
+        b = frames_batch(env, Ts, 16000, [R_MLSA.samples(t, P) for t in Ts])
+        y, status = b.mlsa_synthesis(T_MLSA.dev(torch, np.concatenate(pitches), np.float32),
+                                     T_MLSA.dev(torch, np.concatenate(mcs), np.float32), T_MLSA.LP16, T_MLSA.HP16,
+                                     alpha=alpha, pade_order=pd, frame_shift=P)
+        y, status = host(y), host(status)
+        b.close()
+        assert (status == 0).all()
+        es = T_MLSA.run_excitation(env.gpu, pitches, T_MLSA.LP16, T_MLSA.HP16, P)
+        for u, p in enumerate(pitches):
+            x = R_MLSA.excite(p, P)[0]
+            g = R_MLSA.noise(len(x))
+            want = R_MLSA.fir(T_MLSA.LP16, x) + R_MLSA.fir(T_MLSA.HP16, g)
+            bound = 64.0 * np.spacing(np.abs(T_MLSA.LP16).sum() * max(np.abs(x).max(), 1e-300)
+                                      + np.abs(T_MLSA.HP16).sum() * np.abs(g).max())
+            assert np.abs(es[u] - want).max() <= bound
+        T_MLSA.check_filter("on the caller's stream, round %d" % k, T_MLSA.split(y, Ts, P), es, mcs, alpha,
+                            R_MLSA.pade(pd), P)
+
+
+def test_mlsa_excitation_and_filter(env):
+    T_MLSA.test_synthesis_is_the_two_calls(env.gpu, False)
+
+
+def test_parameter_generation_considering_global_variance(env):
+    torch = env.torch
+    lengths = (3, 33, 200)
+    data, voiced = K_GV.inputs(lengths, False)
+    streams, gm, gv = T_GV.device_streams(torch, data, voiced)
+    mask = torch.from_numpy(K_GV.holes(lengths)).cuda()
+    b = frames_batch(env, lengths)
+    outs, status, info = b.parameter_generation_gv(streams, gm, gv, gv_mask=mask, want_info=True,
+                                                   unvoiced_value=T_GV.UNVOICED, max_iter=5, epsilon=0.0)
+    c0, _ = b.parameter_generation([(m, v, w, None) for m, v, w, _ in streams])
+    c0s, outs, status = [host(o) for o in c0], [host(o) for o in outs], host(status)
+    b.close()
+    opts = dict(max_iter=5, epsilon=0.0)
+    r64 = K_GV.reference(lengths, data, voiced, c0s, K_GV.holes(lengths), 0, np.float64, **opts)
+    rld = K_GV.reference(lengths, data, voiced, c0s, K_GV.holes(lengths), 0, np.longdouble, **opts)
+    T_GV.compare(lengths, voiced, outs, status, c0s, r64, rld, "on the caller's stream")
+
+
+def test_mel_generalized_cepstrum_conversion(env):
+    """The parity case (24, .42, -1/3 -> 65, 0, -1/3) of test_gpu_mgc2mgc.py on uneven utterance lengths."""
+    fx = np.load(T_MGC2MGC.gen.PATH)
+    key = T_MGC2MGC.gen.PARITY_STREAM
+    m1, a1, g1, n, u, m2, a2, g2, N, U = T_MGC2MGC.gen.OPTIONS[key][0]
+    assert (m1, m2, a2) == (24, 65, 0.0)
+    rows = fx[key + "/in"]
+    b = frames_batch(env, T_MGC2MGC.uneven(len(rows)))
+    mc = env.torch.from_numpy(np.ascontiguousarray(rows)).cuda()
+    out, st = b.convert_mel_generalized_cepstrum(mc, a1, g1, m2, a2, g2)
+    out, st = host(out), host(st)
+    b.close()
+    assert (st == 0).all()
+    T_MGC2MGC.check_rows(out, fx[key + "/out"], fx[key + "/sens"], key + " on a caller's stream")
+
+
+def test_mel_cepstra_of_frames_and_waveforms(env):
+    fx = load("sptk_mgcep.npz")
+    fewest = lambda keys: min(keys, key=lambda k: len(fx[k + "/exits"]))
+    T_MGCEP.test_rows_mode_against_reference(env.gpu, fx, fewest(T_MGCEP.ROW_KEYS))
+    T_MGCEP.test_waveform_mode_against_reference_and_rows_mode(env.gpu, fx, fewest(T_MGCEP.WAVE_KEYS))
+
+
+def test_modify_features(env):
+    """test_gpu_modify.py's 64 speech rows as utterances of 7 and 57 frames, a factor pair each: f0 with numpy's bits,
+    the envelope within modify_reference.bound."""
+    FS, F = T_MOD.FS, T_MOD.F
+    lengths, rs, shifts = [7, 57], [0.75, 1.2], [1.37, 0.5]
+    speech64, f0h = T_MOD.speech_rows(), mr.f0_contour(64)
+    b = frames_batch(env, lengths, FS, fft_size=F)
+    got = b.modify_features(T_MOD.dev(env.torch, f0h), T_MOD.dev(env.torch, speech64), f0_scale=shifts, formant_ratio=rs)
+    f0_out, sp_out = (host(t) for t in got)
+    b.close()
+    want = np.concatenate([mr.modify_f0(f0h[:7], shifts[0]), mr.modify_f0(f0h[7:], shifts[1])])
+    assert f0_out.tobytes() == want.tobytes()
+    want = np.concatenate([mr.modify_sp(speech64[:7], rs[0], FS, F), mr.modify_sp(speech64[7:], rs[1], FS, F)])
+    err = np.abs(sp_out - want) / want
+    assert (err.max(axis=1) <= [mr.bound(r) for r in speech64]).all()
 
 
 def test_the_table_of_asynchronous_entry_points(env, request):

@@ -54,9 +54,13 @@ def run_sp(gpu, pkg, fs, fft_size, rows, ratio, lengths=None, **kw):
         b.close()
 
 
+def speech_rows():
+    return np.concatenate([mr.rows("speech", F, seed=s) for s in range(22)])[:64]
+
+
 @pytest.fixture(scope="module")
 def speech64():
-    return np.concatenate([mr.rows("speech", F, seed=s) for s in range(22)])[:64]
+    return speech_rows()
 
 
 @pytest.fixture(scope="module")
@@ -251,38 +255,6 @@ def test_refusals_queue_nothing(gpu, pkg, speech64):
     finally:
         ctx.timing_enable(False)
         b.close()
-
-
-def test_on_the_callers_stream(gpu, pkg, speech64):
-    """The context on a non-blocking torch stream, the call queued behind a delay and the copy of its inputs, as
-    tests/test_gpu_mlsa_stream.py makes it: the call returns ahead of its input, reads the fresh rows, and gives the
-    bits of the stream-0 context."""
-    import test_gpu_caller_stream as CS
-    torch, W, ctx0 = gpu
-    env = CS.Env(torch, W, ctx0)
-    mod = pkg.modify.modify_features
-    try:
-        lengths, rs, shifts = [7, 57], [0.75, 1.2], [1.37, 0.5]
-        with torch.cuda.stream(env.U):
-            b = CS.DelayedBatch(env, env.ctx, W.default_params(FS, 5.0, fft_size=F), f0_lengths=lengths)
-            f0, sp = dev(torch, mr.f0_contour(64)), dev(torch, speech64)
-            env.U.synchronize()
-            got = env.pending_call("modify_features", lambda *a, **k: mod(b._b, *a, **k), lambda *a, **k: mod(b._twin, *a, **k),
-                                   (f0, sp), dict(f0_scale=shifts, formant_ratio=rs), (f0, sp))
-            assert env.pending["modify_features"] == [True], "the call waited for the stream"
-            assert env.mismatches == [], "other bits than on the stream-0 context"
-            f0_out, sp_out = (t.cpu().numpy() for t in got)
-            env.U.synchronize()
-            b.close()
-        f0h = mr.f0_contour(64)
-        assert f0_out.tobytes() == np.concatenate([mr.modify_f0(f0h[:7], shifts[0]), mr.modify_f0(f0h[7:], shifts[1])]).tobytes()
-        want = np.concatenate([mr.modify_sp(speech64[:7], rs[0], FS, F), mr.modify_sp(speech64[7:], rs[1], FS, F)])
-        err = np.abs(sp_out - want) / want
-        assert (err.max(axis=1) <= [mr.bound(r) for r in speech64]).all()
-    finally:
-        with torch.cuda.stream(env.U):
-            env.ctx.close()
-        torch.cuda.synchronize()
 
 
 def test_convert_chain(gpu, pkg, oracle):

@@ -160,10 +160,12 @@ def test_accepted_factors_reach_the_library(pkg, batch):
     assert a.dtype == np.float64 and a.tolist() == [1.5, 1.5, 1.5] and pkg.modify.factor_array("w", "n", None, 3) is None
 
 
-def test_uses_no_assert_and_adds_no_batch_method(pkg):
+def test_uses_no_assert_and_forwards_to_the_batch_method(pkg):
     text = open(os.path.join(ROOT, "hts-train-world_amd", "modify.py")).read()
     assert not re.search(r"^\s*assert\b", text, re.M)
-    assert not hasattr(pkg.world.WorldBatch, "modify_features") and not hasattr(pkg.world.WorldBatch, "convert")
+    assert "modify_features" in vars(pkg.world.WorldBatch) and not hasattr(pkg.world.WorldBatch, "convert")
+    assert pkg.modify.factor_array is pkg.world.factor_array
+    assert not re.search(r"\._(f64|out)\b", text)                      # the batch's private checks stay in world.py
 
 
 def test_header_and_export(pkg):

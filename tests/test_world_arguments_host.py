@@ -12,6 +12,8 @@ import types
 import numpy as np
 import pytest
 
+from caller_stream_table import ASYNC, NO_DEVICE_WORK, SYNCHRONISES
+
 torch = pytest.importorskip("torch")
 
 NU, TS, TF, TO, FFT, BINS = 2, 2000, 27, 2000, 1024, 513
@@ -118,6 +120,11 @@ TABLE = {
                            [arg("groups", 0, 0, free=(1,)), arg("groups", 0, 1, free=(1,)), arg("path"), arg("path_len"),
                             arg("b_mask")]),
     "spectrum_from_mel_cepstrum": (lambda: dict(mc=z(F64, TF, 26)), [arg("mc", free=(1,))]),
+    "convert_mel_generalized_cepstrum": (lambda: dict(mc=z(F64, TF, 26), alpha=0.42, gamma=-0.5, out_order=30,
+                                                      out_alpha=0.0, out_gamma=1.0), [arg("mc", free=(1,))]),
+    "modify_features": (lambda: dict(f0=z(F64, TF), sp=z(F64, TF, BINS), f0_scale=1.2, formant_ratio=[0.8, 1.25],
+                                     out=[z(F64, TF), z(F64, TF, BINS)]),
+                        [arg("f0"), arg("sp"), arg("out", 0), arg("out", 1)]),
     "postfilter_mel_cepstrum": (lambda: dict(mc=z(F64, TF, 26)), [arg("mc", free=(1,))]),
     "utterance_means": (lambda: dict(x=z(F64, TF, 4)), [arg("x", free=(1,))]),
     "modulation_spectrum_stats": (lambda: dict(x=z(F64, TF, 4), mean=z(F64, NU, 4)), [arg("x", free=(1,)), arg("mean")]),
@@ -157,6 +164,13 @@ OPTIMIZER = (lambda W: dict(option=W.default_optimizer_option("adam"), params=[z
 def test_the_table_covers_every_public_method(W):
     public = {n for n in vars(W.WorldBatch) if not n.startswith("_")}
     assert set(TABLE) | NO_TENSORS == public and not set(TABLE) & NO_TENSORS
+
+
+def test_the_caller_stream_tables_cover_every_public_method(W):
+    """tests/test_gpu_caller_stream.py's tables: every public name is asynchronous, waits inside, or queues nothing."""
+    a, s, n = set(ASYNC) - {"optimizer_step"}, set(SYNCHRONISES), NO_DEVICE_WORK     # optimizer_step is the context's
+    assert not a & s and not a & n and not s & n and len(a) == len(ASYNC) - 1
+    assert a | s | n == {name for name in vars(W.WorldBatch) if not name.startswith("_")}
 
 
 def rendered(path):
@@ -230,6 +244,8 @@ def test_optional_tensors_and_fix_ups_still_pass(batch):
     """None where a call takes it, and the layouts a call repairs itself, reach the library like the plain call."""
     cases = [(batch.utterance_status, dict(x=z(F64, TS))), (batch.utterance_status, dict()),
              (batch.analyze, dict(x=z(F64, TS))), (batch.modulation_spectrum_stats, dict(x=z(F64, TF, 4))),
+             (batch.modify_features, dict(f0=z(F64, TF), f0_scale=1.2)),
+             (batch.modify_features, dict(sp=z(F64, TF, BINS), formant_ratio=0.8)),
              (batch.compose_ffo, dict(streams=[[z(F32, TF, 3), WIN, None]])),
              (batch.label_features, dict(feature_set=types.SimpleNamespace(n_features=3, handle=None),
                                          labels=[([(0, 11, "a", 2)], True), ([(0, 16, "b", 2)], True)],
