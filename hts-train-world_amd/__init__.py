@@ -15,7 +15,7 @@ from .world import MgcConvertOption, WorldBatch, WorldParams, load_library, sptk
 def __getattr__(name):
     # `recipe` is also a command (python -m hts-train-world_amd.recipe): imported on first use, not with the package;
     # `training` needs torch
-    if name in ("recipe", "sweep", "pipeline", "training", "generate", "modify"):
+    if name in ("recipe", "sweep", "pipeline", "training", "generate", "modify", "lsp"):
         import importlib
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

@@ -283,7 +283,7 @@ struct Batch {
   int* d_part_cnt_d4c = nullptr;     // [total_f / 1024 + 2]
   int* d_part_n_d4c = nullptr;       // [4]
   // each stage's own state, built on its first use (see StageWs): the struct is private to the stage's .hip file
-  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa, dtw, modify;
+  std::unique_ptr<StageWs> dio, d4c, syn, harvest, codec, vibrato, mlpg, mlpg_gv, mspf, trj, dnn, ffi, mgcep, mlsa, dtw, modify, lsp;
   bool syn_warm = false;                    // launch_analyze_synthesize has succeeded once on this batch
   // the f0 front end of the one-call forms (launch_f0; WorldMi355BatchSetF0Estimator): WM_F0_DIO or WM_F0_HARVEST, and
   // whether StoneMask follows it.  The stage entry points (WorldMi355Dio, WorldMi355Harvest, ...) do not read them.
@@ -361,6 +361,22 @@ int launch_mgc2sp(Batch& b, hipStream_t st, const double* d_mc, const WorldMi355
 int check_mgc2mgc(int64_t total_rows, const double* d_in, const WorldMi355MgcConvertOption* opt, const double* d_out);
 int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt, double* d_out,
                    int* d_status);
+// the energy form: d_ene[row] = 1/2 ln sum_k c2[k]^2 of the row's conversion, NaN where the storing form flags the row
+int launch_mgc2mgc_energy(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt,
+                          double* d_ene);
+// lsp.hip: lspcheck | lsp2lpc, the way on to MGC rows, and postfiltering_lsp
+int check_lsp(int64_t total_rows, const double* d_lsp, const WorldMi355LspOption* opt, const double* d_lpc,
+              const double* d_checked);
+int launch_lsp_to_lpc(Batch& b, hipStream_t st, const double* d_lsp, const WorldMi355LspOption& opt, double* d_lpc,
+                      double* d_checked, int* d_status);
+int check_lsp_to_mgc(int64_t total_rows, const double* d_lsp, const WorldMi355LspOption* opt, int out_order,
+                     double out_alpha, double out_gamma, const double* d_out, const int* d_status);
+int launch_lsp_to_mgc(Batch& b, hipStream_t st, const double* d_lsp, const WorldMi355LspOption& opt, int out_order,
+                      double out_alpha, double out_gamma, double* d_out, int* d_status);
+int check_lsp_postfilter(int64_t total_rows, const double* d_lsp, const WorldMi355LspPostfilterOption* opt,
+                         const double* d_out, const double* d_ene1, const double* d_ene2, const int* d_status);
+int launch_lsp_postfilter(Batch& b, hipStream_t st, const double* d_lsp, const WorldMi355LspPostfilterOption& opt,
+                          double* d_out, double* d_ene1, double* d_ene2, int* d_status);
 // mlsa.hip: excite | dfs | mglsadf.  mode bits of check_mlsa: 1 the excitation's arguments, 2 the filter's
 int mlsa_samples(int n_frames, int frame_shift, int* n_samples);
 int mlsa_pade(int order, double* row);

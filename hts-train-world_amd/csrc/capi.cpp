@@ -354,6 +354,44 @@ int WorldMi355MelGeneralizedCepstrumConvert(WorldMi355Batch* b, const double* in
   if (const int rc = check_mgc2mgc(b->b.total_f, in, opt, out)) return rc;      // refused before any device call
   return on_batch(b, launch_mgc2mgc, in, *opt, out, status);
 }
+void WorldMi355DefaultLspOption(WorldMi355LspOption* o) {                       // lspcheck -r 0.1 -G 1e-10, SPTK's orders
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->order = 25;
+  o->alpha = 0.35;
+  o->gamma = -1.0;
+  o->min_distance = 0.1;
+  o->min_gain = 1e-10;
+}
+void WorldMi355DefaultLspPostfilterOption(WorldMi355LspPostfilterOption* o) {   // $pf_lsp 0.7, IMPLEN 4096
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+  o->order = 25;
+  o->alpha = 0.35;
+  o->gamma = -1.0;
+  o->min_distance = 0.1;
+  o->min_gain = 1e-10;
+  o->beta = 0.7;
+  o->length = 4096;
+}
+int WorldMi355LspToLpc(WorldMi355Batch* b, const double* lsp, const WorldMi355LspOption* opt, double* lpc,
+                       double* checked, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_lsp(b->b.total_f, lsp, opt, lpc, checked)) return rc;   // refused before any device call
+  return on_batch(b, launch_lsp_to_lpc, lsp, *opt, lpc, checked, status);
+}
+int WorldMi355LspToMelGeneralizedCepstrum(WorldMi355Batch* b, const double* lsp, const WorldMi355LspOption* opt,
+                                          int out_order, double out_alpha, double out_gamma, double* out, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_lsp_to_mgc(b->b.total_f, lsp, opt, out_order, out_alpha, out_gamma, out, status)) return rc;
+  return on_batch(b, launch_lsp_to_mgc, lsp, *opt, out_order, out_alpha, out_gamma, out, status);
+}
+int WorldMi355LspPostfilter(WorldMi355Batch* b, const double* lsp, const WorldMi355LspPostfilterOption* opt, double* out,
+                            double* ene1, double* ene2, int* status) {
+  if (!b) return WM_ERR_BAD_ARG;
+  if (const int rc = check_lsp_postfilter(b->b.total_f, lsp, opt, out, ene1, ene2, status)) return rc;
+  return on_batch(b, launch_lsp_postfilter, lsp, *opt, out, ene1, ene2, status);
+}
 void WorldMi355DefaultMlsaOption(WorldMi355MlsaOption* o) {                     // SPTK's mglsadf defaults, Pade order 4
   if (!o) return;
   memset(o, 0, sizeof(*o));

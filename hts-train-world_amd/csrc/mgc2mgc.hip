@@ -48,9 +48,42 @@ struct Mgc2mgcArgs {
   int in_norm, in_mul, out_norm, out_mul;
 };
 
+// The energy form's sum of squares, an unevaluated pair h + l per lane: a square enters exactly (the product and its
+// rounding error by one fma each), the additions keep their rounding errors (two-sum), so the total is good to the last
+// bit of a double and beyond.  It has to be: for a row whose gain is tiny the sum is 1 - 2 K and the energy, 1/2 ln of
+// it, is -K -- what a sum rounded to 1e-16 would bury.
+struct SquareSum {
+  double h = 0.0, l = 0.0;
+  __device__ __forceinline__ void add_square(double v) {
+#pragma clang fp contract(off)
+    const double p = v * v, pe = __builtin_fma(v, v, -p);
+    const double t = h + p, b = t - h;
+    l = l + (((h - (t - b)) + (p - b)) + pe);
+    h = t;
+  }
+  template <int CTRL, int ROW_MASK> __device__ __forceinline__ void add_lanes() {
+#pragma clang fp contract(off)
+    const double oh = dpp_get<CTRL, ROW_MASK, 0xf>(h), ol = dpp_get<CTRL, ROW_MASK, 0xf>(l);   // 0 where there is no source
+    const double t = h + oh, b = t - h;
+    l = (l + ol) + ((h - (t - b)) + (oh - b));
+    h = t;
+  }
+  // 1/2 ln of the wave's total, by wave_scan_incl()'s fixed tree: a row's bits depend on nothing but the row
+  __device__ __forceinline__ double half_log_total() {
+    add_lanes<0x111, 0xf>();
+    add_lanes<0x112, 0xf>();
+    add_lanes<0x114, 0xf>();
+    add_lanes<0x118, 0xf>();
+    add_lanes<0x142, 0xa>();
+    add_lanes<0x143, 0xc>();
+    const double th = lane63(h), tl = lane63(l);
+    return 0.5 * (log(th) + tl / th);
+  }
+};
+
 extern __shared__ double mgc2mgc_row[];   // the plain input row of the lane-per-output freqt (m1 > 63): m1 + 1 doubles
 
-template <int M>
+template <int M, bool ENERGY = false>
 __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ in, Mgc2mgcArgs o, int64_t total_rows,
                                                      double* __restrict__ out, int* __restrict__ status) {
   constexpr int N = 64 * M;                            // the class holds outputs 1 .. N
@@ -66,7 +99,7 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
   for (int64_t row = blockIdx.x; row < total_rows; row += gridDim.x) {
     const int lane = opaque_lane(lane0);
     const double* src = in + row * (int64_t)(m1 + 1);
-    double* dst = out + row * (int64_t)(m2 + 1);
+    double* dst = ENERGY ? out : out + row * (int64_t)(m2 + 1);   // the energy form stores no coefficient
     wave_sync();
     // ---- the row as given: every coefficient finite, c[0] to every lane
     bool bad = false;
@@ -183,7 +216,12 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
         return v;
       };
       bool nonfinite = !(fabs(c20) < __builtin_inf());
-      if (lane == 0) dst[0] = c20;
+      SquareSum esum;                                  // the energy form: this lane's c2[k]^2, in ascending k
+      if constexpr (ENERGY) {
+        if (lane == 0) esum.add_square(c20);
+      } else {
+        if (lane == 0) dst[0] = c20;
+      }
       if (g1 == 0.0 && g2 == 0.0) {
         // gc2gc between gamma 0 and gamma 0 leaves ca (:379, :381 with both factors 0)
 #pragma unroll
@@ -192,7 +230,8 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
           if (i <= m2) {
             const double v = finish(caz[64 + i]);
             nonfinite = nonfinite || !(fabs(v) < __builtin_inf());
-            dst[i] = v;
+            if constexpr (ENERGY) esum.add_square(v);
+            else dst[i] = v;
           }
         }
       } else if (M == 1) {
@@ -225,7 +264,8 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
         }
         if (lane < m2) {
           nonfinite = nonfinite || !(fabs(vout) < __builtin_inf());
-          dst[lane + 1] = vout;
+          if constexpr (ENERGY) esum.add_square(vout);
+          else dst[lane + 1] = vout;
         }
       } else {
         const double gs = g1 + g2;
@@ -265,7 +305,8 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
           if (i_own <= m2) {
             const double v = finish(__builtin_fma(w, su[0], __builtin_fma(g2, sc[0], cai)));
             nonfinite = nonfinite || !(fabs(v) < __builtin_inf());
-            dst[i_own] = v;
+            if constexpr (ENERGY) esum.add_square(v);
+            else dst[i_own] = v;
           }
 #pragma unroll
           for (int d = 0; d + 1 < M; ++d) {
@@ -279,9 +320,18 @@ __global__ __launch_bounds__(64) void mgc2mgc_kernel(const double* __restrict__ 
         ok = false;
         code = 2;
       }
+      if constexpr (ENERGY) {
+        const double ene = esum.half_log_total();
+        ok = ok && fabs(ene) < __builtin_inf();
+        if (ok && lane == 0) dst[row] = ene;
+      }
     }
-    if (!ok)
-      for (int k = lane; k <= m2; k += 64) dst[k] = 0.0;
+    if constexpr (ENERGY) {
+      if (!ok && lane == 0) dst[row] = __builtin_nan("");   // what the storing form flags
+    } else {
+      if (!ok)
+        for (int k = lane; k <= m2; k += 64) dst[k] = 0.0;
+    }
     if (status != nullptr && lane == 0) status[row] = ok ? 0 : code;
   }
 }
@@ -316,11 +366,9 @@ int check_mgc2mgc(int64_t total_rows, const double* d_in, const WorldMi355MgcCon
   return WM_OK;
 }
 
-int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt, double* d_out,
-                   int* d_status) {
-  const int64_t tf = b.total_f;
-  if (const int rc = check_mgc2mgc(tf, d_in, &opt, d_out)) return rc;
-  if (tf <= 0) return WM_OK;
+namespace {
+
+Mgc2mgcArgs mgc2mgc_args(const WorldMi355MgcConvertOption& opt) {
   Mgc2mgcArgs a;
   {
 #pragma clang fp contract(off)
@@ -335,6 +383,17 @@ int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi35
   a.in_mul = opt.in_multiplied != 0;
   a.out_norm = opt.out_normalized != 0;
   a.out_mul = opt.out_multiplied != 0;
+  return a;
+}
+
+}  // namespace
+
+int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt, double* d_out,
+                   int* d_status) {
+  const int64_t tf = b.total_f;
+  if (const int rc = check_mgc2mgc(tf, d_in, &opt, d_out)) return rc;
+  if (tf <= 0) return WM_OK;
+  const Mgc2mgcArgs a = mgc2mgc_args(opt);
   // the lane-per-output freqt reads its input row from LDS
   const int dyn = a.a != 0.0 && a.m1 > 63 ? (int)sizeof(double) * (a.m1 + 1) : 0;
   TimedScope ts_(b.ctx, st, "mgc2mgc_kernel");
@@ -343,6 +402,37 @@ int launch_mgc2mgc(Batch& b, hipStream_t st, const double* d_in, const WorldMi35
     const int per_ = persistent_grid(*b.ctx, mgc2mgc_kernel<MM>, 64, (int64_t)1 << 40);                     \
     hipLaunchKernelGGL((mgc2mgc_kernel<MM>), dim3((int)(tf < per_ ? tf : per_)), dim3(64), dyn, st, d_in, a, tf, d_out, \
                        d_status);                                                                           \
+  } break;
+  switch (size_class(a.m2)) {
+    WM_MGC2MGC_CASE(1)
+    WM_MGC2MGC_CASE(2)
+    WM_MGC2MGC_CASE(4)
+    WM_MGC2MGC_CASE(8)
+    WM_MGC2MGC_CASE(16)
+    WM_MGC2MGC_CASE(32)
+    WM_MGC2MGC_CASE(64)
+  }
+#undef WM_MGC2MGC_CASE
+  return wm_check(hipGetLastError());
+}
+
+// The energy form (postfiltering_lsp's `mgc2mgc | vopr -m | vsum | sopr -LN -m 0.5`, scripts/Training.pl:2702-2705): the
+// same rows through the same chain, each c2[k] squared into its lane's sum where the storing form writes it, one double per
+// row out.  d_ene and d_in share no element: both are the caller's own workspace (lsp.hip).
+int launch_mgc2mgc_energy(Batch& b, hipStream_t st, const double* d_in, const WorldMi355MgcConvertOption& opt,
+                          double* d_ene) {
+  const int64_t tf = b.total_f;
+  if (!d_ene) return WM_ERR_BAD_ARG;
+  if (const int rc = check_mgc2mgc(0, d_in, &opt, d_ene)) return rc;
+  if (tf <= 0) return WM_OK;
+  const Mgc2mgcArgs a = mgc2mgc_args(opt);
+  const int dyn = a.a != 0.0 && a.m1 > 63 ? (int)sizeof(double) * (a.m1 + 1) : 0;
+  TimedScope ts_(b.ctx, st, "mgc2mgc_kernel");
+#define WM_MGC2MGC_CASE(MM)                                                                                 \
+  case MM: {                                                                                                \
+    const int per_ = persistent_grid(*b.ctx, mgc2mgc_kernel<MM, true>, 64, (int64_t)1 << 40);               \
+    hipLaunchKernelGGL((mgc2mgc_kernel<MM, true>), dim3((int)(tf < per_ ? tf : per_)), dim3(64), dyn, st, d_in, a, tf, \
+                       d_ene, (int*)nullptr);                                                               \
   } break;
   switch (size_class(a.m2)) {
     WM_MGC2MGC_CASE(1)

@@ -33,7 +33,9 @@ of the per-utterance variances that `gv-data` writes, and parameter generation t
 gen_param_files() / `gen-param` is the first stage of the way back (scripts/Training.pl:2755-2810: SPTK mlpg on a
 model's `ffo` rows), in front of synth.  postfilter_files() / `postfilter` is the step gen_wave takes between the two
 (scripts/Training.pl:2642-2687, postfiltering_mcp: `.mgc` in, `.p_mgc` out).  With GAMMA != 0 gen_wave's
-`mgc2mgc` steps (:2861-2868; postfiltering_lsp's :2702-2705) are mgc2mgc_files() / `mgc2mgc`.  With USEMSPF gen_wave takes
+`mgc2mgc` steps (:2861-2868; postfiltering_lsp's :2702-2705) are mgc2mgc_files() / `mgc2mgc`; the whole line from MGC-LSP
+rows, `lspcheck | lsp2lpc | mgc2mgc -n -u`, is lsp2mgc_files() / `lsp2mgc`, and postfiltering_lsp (:2690-2752) is
+postfilter_lsp_files() / `postfilter-lsp`.  With USEMSPF gen_wave takes
 postfiltering_mspf instead (:2950-3038): mspf_files() / `mspf`, on the statistics files that mspf_stats_files() /
 `mspf-stats` write (make_mspf, :3133-3221).
 mgcep_files() / `mgcep` is the recipe's spectral analysis without WORLD (data/Makefile.in:134-137, the default
@@ -1642,6 +1644,85 @@ def mgc2mgc_files(jobs, order, alpha, gamma, out_order, out_alpha, out_gamma, no
     return stage.frames
 
 
+# ---- MGC-LSP rows to MGC rows and the LSP postfilter (scripts/Training.pl:2861-2868, :2690-2752) -----------------------
+def lsp_check(order, alpha, gamma, out_order=None, out_alpha=None, out_gamma=None, beta=None, length=None):
+    """ValueError for what WorldMi355LspToMelGeneralizedCepstrum (beta None) or WorldMi355LspPostfilter refuses, before a
+    file is read."""
+    if not 1 <= order <= 63:
+        raise ValueError("order %d: 1 .. 63" % order)
+    if not (abs(alpha) < 1 and -1 <= gamma < 0):
+        raise ValueError("|alpha| < 1 and -1 <= gamma < 0: MGC-LSP rows exist at gamma != 0 only")
+    if beta is None:
+        mgc2mgc_check(order, alpha, gamma, order if out_order is None else out_order,
+                      alpha if out_alpha is None else out_alpha, gamma if out_gamma is None else out_gamma, True)
+        return
+    if not np.isfinite(beta):
+        raise ValueError("beta must be finite")
+    if not (64 <= length <= 4096 and length & (length - 1) == 0):
+        raise ValueError("length %d: a power of two, 64 .. 4096" % length)
+
+
+def _lsp_stage(jobs, order, out_width, call, ctx, max_batch_frames, io_threads, resume):
+    """The file loop of lsp2mgc_files and postfilter_lsp_files: float32 [T][order+1] in, float32 [T][out_width] out of
+    call(batch, float64 rows) -> (rows, status)."""
+    jobs = list(jobs)
+    width = int(order) + 1
+    frames = [_rows_in(j, width, 2, "one output path") for j in jobs]
+    mine = _my_jobs(frames, lambda i: not (resume and _size_is(jobs[i][1], 4 * out_width * frames[i])))
+    if not mine:
+        return 0
+    with _Stage(ctx, io_threads) as stage:
+        for group, batch in stage.batches(mine, frames, max_batch_frames):
+            with batch as b:
+                rows = stage.load([jobs[i][0] for i in group], width)
+                out, status = call(b, rows.double())
+                host = out.float().cpu().numpy()
+                st = status.cpu().numpy()
+                fo = b.frame_offsets
+                for k, i in enumerate(group):
+                    bad = np.nonzero(st[fo[k]:fo[k + 1]] & 12)[0]
+                    if len(bad):
+                        print("warning: %s: %d frames flagged (first: frame %d, status %d), written as zeros" % (
+                            jobs[i][0], len(bad), int(bad[0]), int(st[fo[k] + bad[0]])), file=sys.stderr)
+                stage.put(b, host, [jobs[i][1] for i in group])
+    return stage.frames
+
+
+def lsp2mgc_files(jobs, order, alpha, gamma, log_gain=False, out_order=None, out_alpha=None, out_gamma=None, ctx=None,
+                  max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """gen_wave's `lspcheck -c -r 0.1 -g -G 1e-10 | lsp2lpc | mgc2mgc -n -u` (scripts/Training.pl:2861-2868) for a file
+    list: MGC-LSP rows [gain, lsp_1 .. lsp_m] to plain MGC rows (lsp.lsp_to_mel_generalized_cepstrum; include/world_mi355.h
+    is the definition, parity with SPTK's lspcheck and lsp2lpc is unpinned).
+
+    jobs:  [(in, c_mgc_out)] -- float32 [T][order+1] in, float32 [T][out_order+1] out
+    out_order, out_alpha, out_gamma: None for the input's own, which is gen_wave's call.
+    The rows are widened to double on the device and rounded to float32 once on the way out.  Rank-sharded by frame
+    count; with resume, utterances whose output has its full size are skipped."""
+    from . import lsp as L
+    lsp_check(order, alpha, gamma, out_order, out_alpha, out_gamma)
+    out_width = int(order if out_order is None else out_order) + 1
+    return _lsp_stage(jobs, order, out_width,
+                      lambda b, rows: L.lsp_to_mel_generalized_cepstrum(b, rows, alpha, gamma, out_order, out_alpha,
+                                                                        out_gamma, log_gain),
+                      ctx, max_batch_frames, io_threads, resume)
+
+
+def postfilter_lsp_files(jobs, order, alpha, gamma, beta=0.7, length=4096, log_gain=False, compensate=False, ctx=None,
+                         max_batch_frames=MAX_BATCH_FRAMES, io_threads=8, resume=False):
+    """`postfiltering_lsp` (scripts/Training.pl:2690-2752) for a file list, the step gen_wave takes on MGC-LSP rows
+    where it takes postfiltering_mcp on mel-cepstra (:2846-2860).
+
+    jobs:  [(in, p_mgc_out)] -- float32 [T][order+1] in, float32 of the same shape out
+    beta, length: $pf_lsp, $fl.  compensate: put the energy difference into the gain, which the script as written does
+    not (lsp.postfilter_lsp).  Rank-sharded by frame count; with resume, utterances whose output has the input's size
+    are skipped."""
+    from . import lsp as L
+    lsp_check(order, alpha, gamma, beta=beta, length=length)
+    return _lsp_stage(jobs, order, int(order) + 1,
+                      lambda b, rows: L.postfilter_lsp(b, rows, alpha, gamma, beta, length, compensate, log_gain),
+                      ctx, max_batch_frames, io_threads, resume)
+
+
 # ---- mel-cepstra from waveforms (data/Makefile.in:134-137: x2x +sf | frame | window | mgcep at gamma 0) ---------------
 def read_samples(path):
     """The int16 values of a headerless little-endian `.raw` file (what `x2x +sf` reads) or of a 16-bit wav, as float64
@@ -2368,6 +2449,24 @@ def main(argv=None):
     p.add_argument("-N", action="store_true", dest="out_normalized", help="gain-normalized output")
     p.add_argument("-U", action="store_true", dest="out_multiplied", help="output multiplied by gamma")
     p.add_argument("--resume", action="store_true", help="skip utterances whose output file is already complete")
+    for name, text in (("lsp2mgc", "lspcheck | lsp2lpc | mgc2mgc -n -u: MGC-LSP files to plain MGC (.c_mgc) files"),
+                       ("postfilter-lsp", "postfiltering_lsp: the LSP postfilter on a list of MGC-LSP files (.p_mgc out)")):
+        p = sub.add_parser(name, help=text)
+        p.add_argument("--scp", required=True, help="job list: the MGC-LSP file to read, then the file to write")
+        p.add_argument("--order", type=int, required=True, help="order of the rows: a row holds gain and order LSPs")
+        p.add_argument("--alpha", type=float, required=True, help="frequency warping of the mgc stream")
+        p.add_argument("--gamma", type=float, required=True, help="gamma of the mgc stream, -1 <= gamma < 0")
+        p.add_argument("--log-gain", action="store_true", help="the gain is stored as its logarithm (LNGAIN)")
+        p.add_argument("--resume", action="store_true", help="skip utterances whose output file is already complete")
+        if name == "lsp2mgc":
+            p.add_argument("--out-order", type=int, default=None, help="order of the output (default: the input's)")
+            p.add_argument("--out-alpha", type=float, default=None, help="alpha of the output (default: the input's)")
+            p.add_argument("--out-gamma", type=float, default=None, help="gamma of the output (default: the input's)")
+        else:
+            p.add_argument("--beta", type=float, default=0.7, help="the postfiltering coefficient (pf_lsp)")
+            p.add_argument("--length", type=int, default=4096, help="samples of the energy sums (IMPLEN)")
+            p.add_argument("--compensate", action="store_true", help="put the energy difference into the gain, which "
+                           "the script as written does not")
     p = sub.add_parser("mgcep", help="x2x +sf | frame | window | mgcep at gamma 0: mel-cepstra of a list of raw or wav files")
     p.add_argument("--scp", required=True, help="job list: the .raw (int16) or wav file, then the mgc file to write")
     p.add_argument("--frame-length", type=int, default=1200, help="FRAMELEN")
@@ -2603,6 +2702,22 @@ def main(argv=None):
         n = mgc2mgc_files(_read_scp(a.scp, 2), a.order, a.alpha, sptk_gamma(a.gamma, a.c), a.out_order, a.out_alpha,
                           sptk_gamma(a.out_gamma, a.out_c), a.normalized, a.multiplied, a.out_normalized, a.out_multiplied,
                           resume=a.resume)
+        print("complete. %d frames" % n)
+        return 0
+    if a.cmd in ("lsp2mgc", "postfilter-lsp"):
+        try:
+            if a.cmd == "lsp2mgc":
+                lsp_check(a.order, a.alpha, a.gamma, a.out_order, a.out_alpha, a.out_gamma)
+            else:
+                lsp_check(a.order, a.alpha, a.gamma, beta=a.beta, length=a.length)
+        except ValueError as err:
+            ap.error(str(err))
+        if a.cmd == "lsp2mgc":
+            n = lsp2mgc_files(_read_scp(a.scp, 2), a.order, a.alpha, a.gamma, a.log_gain, a.out_order, a.out_alpha,
+                              a.out_gamma, resume=a.resume)
+        else:
+            n = postfilter_lsp_files(_read_scp(a.scp, 2), a.order, a.alpha, a.gamma, a.beta, a.length, a.log_gain,
+                                     a.compensate, resume=a.resume)
         print("complete. %d frames" % n)
         return 0
     if a.cmd == "postfilter":

@@ -164,6 +164,17 @@ class MgcConvertOption(C.Structure):
                 ("out_normalized", C.c_int), ("out_multiplied", C.c_int)]
 
 
+class LspOption(C.Structure):
+    """include/world_mi355.h: WorldMi355LspOption (lspcheck | lsp2lpc | mgc2mgc -n -u; the functions are lsp.py's)."""
+    _fields_ = [("order", C.c_int), ("alpha", C.c_double), ("gamma", C.c_double), ("log_gain", C.c_int),
+                ("min_distance", C.c_double), ("min_gain", C.c_double)]
+
+
+class LspPostfilterOption(C.Structure):
+    """include/world_mi355.h: WorldMi355LspPostfilterOption (the recipe's postfiltering_lsp)."""
+    _fields_ = LspOption._fields_ + [("beta", C.c_double), ("length", C.c_int), ("compensation", C.c_int)]
+
+
 class MlsaOption(C.Structure):
     """include/world_mi355.h: WorldMi355MlsaOption (SPTK's excite | dfs | mglsadf, gen_wave's first branch)."""
     _fields_ = [("alpha", C.c_double), ("order", C.c_int), ("pade_order", C.c_int), ("frame_shift", C.c_int),
@@ -337,6 +348,14 @@ def load_library():
     L.WorldMi355DefaultMgcConvertOption.restype = None
     L.WorldMi355DefaultMgcConvertOption.argtypes = [C.POINTER(MgcConvertOption)]
     L.WorldMi355MelGeneralizedCepstrumConvert.argtypes = [vp, vp, C.POINTER(MgcConvertOption), vp, vp]
+    L.WorldMi355DefaultLspOption.restype = None
+    L.WorldMi355DefaultLspOption.argtypes = [C.POINTER(LspOption)]
+    L.WorldMi355DefaultLspPostfilterOption.restype = None
+    L.WorldMi355DefaultLspPostfilterOption.argtypes = [C.POINTER(LspPostfilterOption)]
+    L.WorldMi355LspToLpc.argtypes = [vp, vp, C.POINTER(LspOption), vp, vp, vp]
+    L.WorldMi355LspToMelGeneralizedCepstrum.argtypes = [vp, vp, C.POINTER(LspOption), C.c_int, C.c_double, C.c_double, vp,
+                                                        vp]
+    L.WorldMi355LspPostfilter.argtypes = [vp, vp, C.POINTER(LspPostfilterOption), vp, vp, vp, vp]
     L.WorldMi355DefaultMcpfOption.restype = None
     L.WorldMi355DefaultMcpfOption.argtypes = [C.POINTER(McpfOption)]
     L.WorldMi355MelCepstrumPostfilter.argtypes = [vp, vp, C.POINTER(McpfOption), vp, vp, vp]

@@ -330,10 +330,99 @@ void WorldMi355DefaultMgcConvertOption(WorldMi355MgcConvertOption* opt);
  * exchange data.  1 <= in_order, out_order <= 4095 with min(in_order, out_order) <= 63, |alpha| < 1 and
  * -1 <= gamma <= 1 on both sides, else WM_ERR_BAD_ARG, as for a NULL `in` or `out` or ranges that share an element; all
  * before any device call.  Timed as "mgc2mgc_kernel".  Asynchronous on the context's stream.
- * Not offered: LSP in either direction (lpc2lsp, lsp2lpc, lspcheck), mglsadf and mgcep at gamma != 0, the energy sum of
- * postfiltering_lsp, WorldMi355MelCepstrumToSpectrum of flagged input, host pointers, min(in_order, out_order) > 63. */
+ * Not offered: lpc2lsp (LSP from LPC; the way back is WorldMi355LspToLpc below), mglsadf and mgcep at gamma != 0,
+ * WorldMi355MelCepstrumToSpectrum of flagged input, host pointers, min(in_order, out_order) > 63.  The energy sum of
+ * postfiltering_lsp is part of WorldMi355LspPostfilter below. */
 int WorldMi355MelGeneralizedCepstrumConvert(WorldMi355Batch* b, const double* in, const WorldMi355MgcConvertOption* opt,
                                             double* out, int* status);
+
+/* ---- MGC-LSP rows to MGC rows, and the LSP postfilter.  With GAMMA != 0 the recipe's `mgc` stream holds MGC-LSP rows
+ * [gain, lsp_1 .. lsp_m] (data/Makefile.in:138-146, 186-192); gen_wave and postfiltering_lsp (scripts/Training.pl:2690-2752,
+ * :2846-2868) take them back by `lspcheck -c -r 0.1 -g -G 1e-10 | lsp2lpc | mgc2mgc -n -u`.  SPTK's lspcheck and lsp2lpc
+ * are not in the reference tree.  PARITY WITH SPTK'S COMMANDS IS UNPINNED: the yardstick is the definition below, which
+ * tests/lsp_reference.py states in float64.  Everything is in double; the float32 of the commands' pipes and files
+ * appears only at the recipe's file ends.  One row is x[0 .. m]: x[0] the gain, w[i] = x[i], i = 1 .. m, radians meant to
+ * lie in (0, pi); r = min_distance, G = min_gain, d = r pi / (m + 1) in that expression, pi the double nearest to it.
+ *
+ * 1. Check (lspcheck -c -r r -g -G G [-L]), the steps in this order, plain expressions without contraction:
+ *      range     w <- |w|, then w <- 2 pi - w where w > pi;
+ *      order     sorted ascending (the outcome of the command's repeated adjacent swaps);
+ *      distance  ONE pass, i = 1 .. m-1 ascending, each step on the values the steps before it left: t = w[i+1] - w[i];
+ *                if t < d: s = 0.5 (d - t), w[i] -= s, w[i+1] += s;
+ *      gain      K = exp(x[0]) under log_gain (the device library's exp), else x[0].  K < G: K <- G, and the checked row's
+ *                gain is log(G) (the host library's log) under log_gain, else G.  Otherwise the gain keeps its bits.
+ *    status bits: 1 a range, order or distance step changed a value; 2 the gain was raised; 4 a non-finite input value:
+ *    the row and everything derived from it are zeros; 8 a non-finite result: zeros; 16 the checked LSPs are not strictly
+ *    increasing inside (0, pi) -- the single pass does not guarantee it; the row is converted all the same.
+ * 2. lsp2lpc: A(z) = (P(z) + Q(z)) / 2 with f_i(z) = 1 - 2 cos(w[i]) z^-1 + z^-2, P the product of the f_i of odd i
+ *    (1, 3, ...), Q of even i; for even m P takes the further factor (1 + z^-1) and Q (1 - z^-1), for odd m Q takes
+ *    (1 - z^-2).  The row is [K, a_1 .. a_m] (a_0 = 1 dropped), K linear whatever log_gain is.  cos is the device
+ *    library's.  Order of the products: both start from 1; the quadratic factors of P and of Q are taken in turn, each
+ *    polynomial's own in the bit-reversed order of their positions (position j = 0, 1, ... among its factors in ascending
+ *    i, sorted by the reversal of j's binary digits over ceil(log2 n) bits: at m = 7, i = 1, 2, 5, 6, 3, 4, 7), each as
+ *    c[k] <- (c[k] + p_i c[k-1]) + c[k-2] with p_i = -2 cos(w[i]); then the further factor as c[k] +- c[k-1] (c[k] - c[k-2]);
+ *    then a_k = 0.5 (P[k] + Q[k]); no contraction anywhere.  (In ascending i the partial products grow to 1e8 at m = 63
+ *    and P + Q keeps no digit; in this order they stay small.)
+ * 3. LSP -> MGC (gen_wave, :2861-2868): steps 1 and 2, then WorldMi355MelGeneralizedCepstrumConvert's core on the LPC row
+ *    with in_normalized = in_multiplied = 1 at (alpha, gamma) towards (out_order, out_alpha, out_gamma), plain output;
+ *    its rules and refusals are unchanged.  gamma < 0 is required.
+ * 4. LSP postfilter (postfiltering_lsp, :2690-2752), factor beta = $pf_lsp, length L = $fl (IMPLEN).  From the RAW row,
+ *    as the script reads the file itself (:2709): for i = 2 .. m-1, d1 = beta (w[i+1] - w[i]), d2 = beta (w[i] - w[i-1]),
+ *      p[i] = w[i-1] + d2 + (d2 d2 ((w[i+1] - w[i-1]) - (d1 + d2))) / ((d2 d2) + (d1 d1)),
+ *    p[1] = w[1], p[m] = w[m], all from the unfiltered neighbours in exactly this expression; where d1 == 0 and d2 == 0
+ *    (Perl would die) p[i] = w[i].  The script reads the values through `x2x +fa`'s text: that rounding is NOT modelled.
+ *    Energies (:2702-2705, :2739-2742): ene = 1/2 ln sum_{k < L} c2[k]^2, c2 being step 3 towards (L - 1, alpha 0, gamma 1)
+ *    of the CHECKED row -- the command's output as it is: c2[0] is the gamma = 1 coefficient, not the response's first
+ *    sample.  ene1 is of the raw row, ene2 of [gain, p].  The output row is [gain', p], its LSPs NOT checked (the script
+ *    merges the .lsp file as written, :2747).  compensation 0 (default) is the script as written: :2745 divides ene2 by
+ *    itself, so gain' = gain bit for bit, and no energy is computed unless ene1 / ene2 are asked for.  compensation 1 is
+ *    what the two energy files evidently exist for: gain' = gain + (ene1 - ene2) under log_gain, else
+ *    gain exp(ene1 - ene2).  beta == 1 or m <= 2 is the identity: rows copied bit for bit, status 0, energies (where
+ *    asked for) 0, nothing computed; gen_wave skips the step at 1.0 (:2853).
+ *    status: 4 a non-finite input value; 8 a non-finite p, energy or gain', or a row the conversion refuses (its status
+ *    1 or 2); such rows and their energies are zeros.  Where energies are computed, bits 1, 2 and 16 of the two checks
+ *    are or-ed in; they change nothing in the output row. */
+typedef struct {
+  int order;                /* m: 1 .. 63 */
+  double alpha;             /* of the MGC-LSP stream, |alpha| < 1 */
+  double gamma;             /* of the MGC-LSP stream, -1 <= gamma < 0 */
+  int log_gain;             /* -L / $lg: x[0] is ln K */
+  double min_distance;      /* -r: 0 .. 1 */
+  double min_gain;          /* -G: finite, > 0 */
+} WorldMi355LspOption;
+typedef struct {
+  int order;
+  double alpha;
+  double gamma;
+  int log_gain;
+  double min_distance;
+  double min_gain;
+  double beta;              /* $pf_lsp */
+  int length;               /* $fl: a power of two, 64 .. 4096 */
+  int compensation;         /* 0 the script as written, 1 gain' carries ene1 - ene2 */
+} WorldMi355LspPostfilterOption;
+/* order 25, alpha 0.35, gamma -1, log_gain 0, min_distance 0.1, min_gain 1e-10; beta 0.7, length 4096, compensation 0. */
+void WorldMi355DefaultLspOption(WorldMi355LspOption* opt);
+void WorldMi355DefaultLspPostfilterOption(WorldMi355LspPostfilterOption* opt);
+/* All three: lsp DEVICE double[total_frames][order+1]; asynchronous on the context's stream; WM_OK on zero frames; rows
+ * never exchange data.  WM_ERR_BAD_ARG before any device call for order outside 1 .. 63, not |alpha| < 1, gamma outside
+ * [-1, 0), min_distance outside [0, 1], a min_gain that is not finite and positive, a non-finite beta, a length that is no
+ * power of two in 64 .. 4096, a NULL required pointer, and ranges that share an element (the postfilter's out may be
+ * exactly lsp).  Timed as "lsp_kernel" and "mgc2mgc_kernel".
+ * LspToLpc: steps 1 and 2.  lpc DEVICE double[total_frames][order+1]; checked (the checked rows, gain as step 1 leaves it)
+ * the same shape or NULL; status DEVICE int[total_frames] or NULL. */
+int WorldMi355LspToLpc(WorldMi355Batch* b, const double* lsp, const WorldMi355LspOption* opt, double* lpc,
+                       double* checked, int* status);
+/* Step 3.  out DEVICE double[total_frames][out_order+1]; status DEVICE int[total_frames], required: step 1's bits, and 8
+ * where the conversion flags the row (zeros).  out_order, out_alpha, out_gamma as WorldMi355MgcConvertOption's. */
+int WorldMi355LspToMelGeneralizedCepstrum(WorldMi355Batch* b, const double* lsp, const WorldMi355LspOption* opt,
+                                          int out_order, double out_alpha, double out_gamma, double* out, int* status);
+/* Step 4.  out DEVICE double[total_frames][order+1], or lsp itself; ene1, ene2 DEVICE double[total_frames] or NULL;
+ * status DEVICE int[total_frames], required.  The energies are summed inside the conversion kernel as each c2[k] becomes
+ * final: no row of `length` coefficients exists in device memory, the call's workspace is two LPC rows and two doubles
+ * per frame, and an energy's bits do not depend on how rows are batched. */
+int WorldMi355LspPostfilter(WorldMi355Batch* b, const double* lsp, const WorldMi355LspPostfilterOption* opt, double* out,
+                            double* ene1, double* ene2, int* status);
 
 /* ---- Waveforms from mel-cepstra: the first branch of gen_wave (scripts/Training.pl:2873-2899), the synthesis half of the
  * recipe's default configuration (USEWORLD = 0, GAMMA = 0),
@@ -729,8 +818,9 @@ int WorldMi355OptimizerStep(WorldMi355Context* ctx, const WorldMi355OptimizerOpt
  * script's co = 2047 leaves out at most twice sum_{n > co} |freqt(w c)[n]| (5e-431 at order 49, alpha 0.55), far
  * below the float32 rounding of its intermediate files (1e-7).  Fields: alpha the `mgc` stream's warp ($fw), beta $pf_mcp
  * (config default 1.4), order m, length $fl = IMPLEN (4096), independent of the batch's fft_size.  hts_engine's -b
- * postfilter (:810) and the LSP postfilter (:2690-2752) are not offered; the modulation-spectrum postfilter (:2950),
- * which gen_wave runs INSTEAD of this one with USEMSPF, is WorldMi355ModulationSpectrumPostfilter below. */
+ * postfilter (:810) is not offered; the LSP postfilter (:2690-2752) is WorldMi355LspPostfilter above; the
+ * modulation-spectrum postfilter (:2950), which gen_wave runs INSTEAD of this one with USEMSPF, is
+ * WorldMi355ModulationSpectrumPostfilter below. */
 typedef struct {
   double alpha;
   double beta;
